@@ -2,7 +2,14 @@
 """Headline benchmark: V-cycle iterations/sec + fine-level SpMV GB/s (% of the MI355X HBM
 roofline) -- BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c3j|c4s|small] [--no-extras]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c3j|c4s|small] [--full [--no-extras]] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: it builds the hierarchy, ships it, warms up, times exactly K steps
+and prints the line (metric / value / unit / higher_is_better / dtype / ms_per_step).  --full adds everything else described
+below: the SpMV roofline and its counter passes, the sweep table, the order-exact leg, time to tolerance, the accelerated
+solve, the reference's CPU baseline and parity runs, the reference-only setup, the modelled N-GPU curve and the extra legs.
+--dump-outputs DIR writes what the timed path computed in its last step (a seeded sample of the iterate and the residual
+norm of the final iterate, float64 .npy files); the same arguments give the same inputs in every run.
 
 A *step* is one pass of the hot path: one multigrid V-cycle on the device-resident hierarchy
 followed by the convergence-check residual norm ||b - A x|| (exactly one iteration of the
@@ -14,7 +21,7 @@ pyamg_amd.aggregation.device_setup (--host-setup: the reference alone; "host" re
 shipped to HBM once.
 
 N = 1: the workload is BASELINE.json configs[2], the north star's problem: 3-D 7-pt Poisson 256^3,
-smoothed aggregation, symmetric Gauss-Seidel V(1,1), fp64.  The line also carries, under "sharded", the
+smoothed aggregation, symmetric Gauss-Seidel V(1,1), fp64.  With --full the line also carries, under "sharded", the
 Chebyshev(3) cycle of configs[3] on the same hierarchy run by the resident engine AND by the row-sharded C++ driver
 (pamg_dist_*, one rank, no peers: what the driver costs over the resident cycle), and under "extra": configs[1]
 (2000^2, weighted Jacobi), configs[4] on one GPU (3-D elasticity, block GS and block Jacobi), configs[0] (the README
@@ -25,9 +32,9 @@ of a multi-GPU run is configs[3], the workload the north star shards: 3-D Poisso
 row-sharded over the N GPUs (RCCL halo exchange over xGMI overlapped with the interior rows, coarse levels collapsed),
 "scaling": "strong" -- the same problem for every N; its N = 1 point is "extra.c4" of the N = 1 line.  The hierarchy is
 built ONCE, on rank 0, and shipped to the ranks array by array (DistMultilevelSolver.from_rank0).  N independent
-replicas of the Gauss-Seidel workload are reported under "extra.replicas".
+replicas of the Gauss-Seidel workload are reported under "extra.replicas" (with --full).
 
-Prints ONE JSON line (rank 0): metric/value/unit/... + "roofline" (fine-level CSR SpMV
+Prints ONE JSON line (rank 0): metric/value/unit/... and, with --full, "roofline" (fine-level CSR SpMV
 kernel: algorithmic bytes / HIP-event time vs 8 TB/s) + "cpu_baseline" (the reference's own
 serial solve on this host, same hierarchy, same b) + "parity" (residual norms of this run's
 GPU cycles vs the reference's cycles).
@@ -37,6 +44,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 # the host-side sweep planners first-touch gigabytes from a hundred threads: 2 MB pages where the kernel grants them (csrc/pamg_plan_vec.h; -0.3 s of the
 # 256^3 upload on the GPU box, slower inside a small container -- hence an application's choice, not the library's default)
@@ -279,6 +288,28 @@ def measure_traffic(grid, nrows, general=False):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_MAX_VALUES = 1 << 22       # 32 MB of float64: a larger iterate is dumped as a fixed, seeded sample of this many entries
+
+
+def dump_sample_index(n):
+    """the entries of an n-vector that --dump-outputs writes: all of them, or the same sorted seeded sample in every run"""
+    if n <= DUMP_MAX_VALUES:
+        return None
+    return np.sort(np.random.default_rng(SEED).choice(n, size=DUMP_MAX_VALUES, replace=False))
+
+
+def dump_outputs(dirpath, x, residual_norm):
+    """--dump-outputs: what the timed path computed in its last step -- the iterate (x.npy; see dump_sample_index) and
+    ||b - A x|| of that iterate (residual_norm.npy) -- as float64 .npy files"""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    x = np.asarray(x, dtype=np.float64)
+    idx = dump_sample_index(x.size)
+    np.save(d / "x.npy", x if idx is None else x[idx])
+    np.save(d / "residual_norm.npy", np.array([residual_norm], dtype=np.float64))
+    return sorted(p.name for p in d.glob("*.npy"))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks here (one process per GPU, the same
     environment contract torch.distributed.run provides), pass rank 0's JSON line through, fail if any rank fails."""
@@ -318,7 +349,14 @@ def main():
     ap.add_argument("--kernel-map", default=None, help="write the launch -> (level, operator, bytes) map of the main workload's cycle here (tools/summarize_prof.py joins it with a rocprofv3 trace)")
     ap.add_argument("--shard-workload", default=os.environ.get("PAMG_SHARD_WORKLOAD", "c4x"), choices=sorted(WORKLOADS),
                     help="N > 1: the row-sharded headline workload (BASELINE configs[3] = c4x, 512^3 Chebyshev)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: roofline and counter passes, sweep table, order-exact leg, time to tolerance, accelerated "
+                         "solve, CPU baseline and parity, reference-only setup, modelled scaling, extra legs (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the iterate and residual norm of the last timed step to DIR/*.npy (float64; a seeded sample of a large iterate)")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs: one GPU only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)
@@ -745,7 +783,7 @@ def main():
         info = d2.native.info() if d2.native is not None else {}
         # fine-level residual kernel on this rank's shard (interior + boundary ranges = the whole shard), HIP events
         roofline = None
-        if rank == 0:
+        if rank == 0 and args.full:
             A0, p0 = d2.A[0], d2.sh.plans[0]
             op0 = d2.sh.A[0]
             by = 12 * op0.nnz + 4 * (p0.n_owned_s + 1) + 8 * p0.n_local_s + 8 * p0.n_owned_s + 8 * p0.n_owned_s
@@ -781,7 +819,7 @@ def main():
         # the same cycles by the resident single-GPU engine on rank 0 (the engine whose parity with the reference the
         # N = 1 line establishes): sharding must not change a bit of the iterates, the norms agree to all-reduce rounding
         check = None
-        if rank == 0 and os.environ.get("PAMG_SHARD_CHECK", "1") != "0":
+        if rank == 0 and args.full and os.environ.get("PAMG_SHARD_CHECK", "1") != "0":
             try:
                 d1 = DeviceMultilevelSolver(spec, device=local_rank, graph=not args.no_graph)
                 xd, bd = capi.DeviceArray.from_host(x0), capi.DeviceArray.from_host(b)
@@ -817,7 +855,7 @@ def main():
         sys.excepthook = _excepthook
         # extras: N independent replicas of the Gauss-Seidel workload (what does not shard)
         wd = start_watchdog(float(os.environ.get("PAMG_EXTRAS_TIMEOUT", "600")), "the replica leg")
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             try:
                 wlr = WORKLOADS[args.workload]
                 A, ml, ts = build(wlr)
@@ -857,6 +895,48 @@ def main():
             log(f"  level {i}: n={L.A.shape[0]} nnz={L.A.nnz} ({L.A.format}) row_ranges={inf['row_blocks']} "
                 f"gs_levels fwd/bwd={inf['gs_levels_fwd']}/{inf['gs_levels_bwd']}")
     wall, ev_ms, res_gpu, xd, bd = time_resident(dml, b, x0, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        stream = dml.stream()
+        dml.store_device(xd, stream=stream)                       # the iterate after the last timed step
+        ss = capi.DeviceArray(1, np.float64)
+        dml.A[0].resid_sumsq(xd, bd, ss, stream=stream)           # ||b - A x||^2 of it, the step's convergence check
+        barrier()
+        files = dump_outputs(args.dump_outputs, xd.download(), float(np.sqrt(ss.download()[0])))
+        ss.free()
+        log(f"outputs of the last timed step: {files} in {args.dump_outputs}")
+
+    def write_kernel_map(ceiling):
+        try:
+            from tools.kernel_map import kernel_map
+            sm = wl["smoother"]
+            kind = sm if isinstance(sm, str) else sm[0]
+            Path(args.kernel_map).write_text(json.dumps({"workload": args.workload, "peak_GBps": HBM_PEAK_GBPS, "ceiling": ceiling,
+                                                         "entries": kernel_map(dml, kind)}, indent=1))
+        except Exception as e:                                  # noqa: BLE001
+            log(f"kernel map not written: {e!r}")
+
+    if not args.full:
+        # a plain run: the headline and nothing else (the legs below are --full)
+        if args.kernel_map and rank == 0:
+            write_kernel_map(None)
+        if rank == 0:
+            box["out"] = {
+                "metric": "vcycle_iterations_per_sec", "value": round(world * args.steps / wall, 3), "unit": "cycles/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(wall * 1e3 / args.steps, 4), "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                "config": {"workload": wl["label"], "key": args.workload, "n": int(n), "nnz": int(A.nnz),
+                           "levels": len(ml.levels), "cycle": "V(1,1)", "graph": not args.no_graph,
+                           "parallelism": "1 GPU", "hierarchy_setup": SETUP_NOTE, "gs_order": dml.order, "full": False},
+                "event_ms_per_step": round(ev_ms / args.steps, 4),
+                "roofline": None, "cpu_baseline": None,
+                "host": {"setup_s": round(t_setup, 1), "upload_s": round(t_upload, 1), "operator_assembly_s": round(t_assembly, 1),
+                         "renumber_s": round(getattr(dml, "renumber_seconds", 0.0), 2), "cores": os.cpu_count(),
+                         "cpu_quota_cores": cpu_quota_cores(), "setup": SETUP_NOTE},
+                "residuals_gpu": [float(v) for v in res_gpu],
+            }
+            emit()
+        return box["out"]
 
     # ---- roofline of the dominant bandwidth kernel: fine-level CSR SpMV (r = b - A x), HIP events
     #      on the solver's stream, algorithmic bytes of SURVEY.md 8(d)
@@ -1042,14 +1122,7 @@ def main():
             exact_leg = {"error": repr(e)[:300]}
 
     if args.kernel_map and rank == 0:
-        try:
-            from tools.kernel_map import kernel_map
-            sm = wl["smoother"]
-            kind = sm if isinstance(sm, str) else sm[0]
-            Path(args.kernel_map).write_text(json.dumps({"workload": args.workload, "peak_GBps": HBM_PEAK_GBPS, "ceiling": ceiling,
-                                                         "entries": kernel_map(dml, kind)}, indent=1))
-        except Exception as e:                                  # noqa: BLE001
-            log(f"kernel map not written: {e!r}")
+        write_kernel_map(ceiling)
 
     ttt = None
     if rank == 0 and world == 1:
@@ -1108,6 +1181,7 @@ def main():
             "time_to_tol_1e-8": ttt,
         }
         out["config"]["gs_order"] = dml.order
+        out["config"]["full"] = True
         if accel_main:
             out["accel"] = accel_main
         if sweeps:

@@ -86,7 +86,8 @@ def available() -> bool:
 def build(force: bool = False) -> bool:
     """Build oracle/_ref.  Returns False (and does nothing) when the reference
     tree is absent (e.g. on the GPU box, which only uses the prebuilt files)."""
-    if not (REF / "pyamg" / "amg_core" / "relaxation_bind.cpp").exists():
+    # os.path.isfile, not Path.exists: a reference tree this user may not read counts as absent (Path.exists raises on EACCES)
+    if not os.path.isfile(REF / "pyamg" / "amg_core" / "relaxation_bind.cpp"):
         return available()
     (DEST / "pyamg" / "amg_core").mkdir(parents=True, exist_ok=True)
     n = _bytecompile_tree()

@@ -359,3 +359,46 @@ def test_bench_headline_stays_small():
     # a failed multi-GPU run's line passes through
     hf = bench.headline({"metric": "m", "value": None, "error": "e" * 1000, "config": {"workload": "w"}})
     assert hf["value"] is None and len(hf["error"]) <= 300
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_options():
+    """--full (everything besides the headline) and --dump-outputs DIR are on the command line; --dump-outputs is one GPU only"""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--dump-outputs", "x"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "one GPU only" in r.stderr
+
+
+def test_bench_dump_outputs_seeded_and_small(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files, at most 64 MB in all, the same entries of a large iterate in every run,
+    a small iterate whole"""
+    bench = _bench_module()
+    n = bench.DUMP_MAX_VALUES + 12345
+    x = np.arange(n, dtype=np.float64) * 0.5
+    files = bench.dump_outputs(tmp_path / "a", x, 3.25)
+    bench.dump_outputs(tmp_path / "b", x, 3.25)
+    assert files == ["residual_norm.npy", "x.npy"]
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+        total += (tmp_path / "a" / f).stat().st_size
+    assert total <= 64 << 20
+    xs = np.load(tmp_path / "a" / "x.npy")
+    idx = (xs * 2).astype(np.int64)
+    assert xs.size == bench.DUMP_MAX_VALUES and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(idx, bench.dump_sample_index(n))
+    assert np.load(tmp_path / "a" / "residual_norm.npy").tolist() == [3.25]
+    small = np.linspace(0.0, 1.0, 1000)
+    bench.dump_outputs(tmp_path / "c", small.astype(np.float32), 1.0)
+    assert np.array_equal(np.load(tmp_path / "c" / "x.npy"), small.astype(np.float32).astype(np.float64))

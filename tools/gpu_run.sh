@@ -9,6 +9,7 @@
 #   dist2[:args]            bench.py --gpus 2 as two ranks sharing the one GPU (gloo transport): rehearsal of the N > 1 line
 #   pmc:<workload>[:args]   two more passes with --pmc FETCH_SIZE / --pmc WRITE_SIZE (kernel trace only) into the same directory
 #   smoke             __graft_entry__.smoke()
+# Every bench.py call here passes --full: these steps record the run with its roofline, sweeps and other legs.
 export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
@@ -24,22 +25,22 @@ for step in "$@"; do
             suffix=${PYTAG:-}
             timeout ${PYTIMEOUT:-900} python tools/$args > gpurun_out/${TAG}_${name}${suffix}.log 2>&1; echo "$name rc=$?"; tail -${PYTAIL:-40} gpurun_out/${TAG}_${name}${suffix}.log ;;
         bench)
-            args=${rest//,/ }; suffix=${BENCHTAG:-_n1}
+            args="--full ${rest//,/ }"; suffix=${BENCHTAG:-_n1}
             timeout 1500 python bench.py $args > gpurun_out/${TAG}_bench${suffix}.json 2> gpurun_out/${TAG}_bench${suffix}.err; echo "bench rc=$?"; tail -c 1500 gpurun_out/${TAG}_bench${suffix}.json ;;
         dist2)
             # two ranks on the ONE GPU, gloo host-callback transport: rehearsal of the N > 1 line (the rate means nothing)
-            args=${rest//,/ }
+            args="--full ${rest//,/ }"
             PAMG_BENCH_BACKEND=gloo PAMG_BENCH_ONE_GPU=1 timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
                 bench.py --gpus 2 --steps 5 --warmup 2 $args > gpurun_out/${TAG}_bench_2ranks_one_gpu.json 2> gpurun_out/${TAG}_bench_2ranks_one_gpu.err; echo "dist2 rc=$?"; tail -c 2500 gpurun_out/${TAG}_bench_2ranks_one_gpu.json ;;
         prof)
-            wl=${rest%%:*}; extra=""; [[ "$rest" == *:* ]] && extra=${rest#*:}; extra=${extra//,/ }
+            wl=${rest%%:*}; extra=""; [[ "$rest" == *:* ]] && extra=${rest#*:}; extra="--full ${extra//,/ }"
             OUT=$PWD/gpurun_out/prof_${TAG}_$wl; mkdir -p $OUT
             (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python /root/repo/bench.py --workload $wl --steps 10 --warmup 2 --cpu-cycles 0 --no-extras --no-pmc --no-setup-compare --kernel-map $OUT/kernel_map.json $extra > $OUT/trace_bench.json 2> $OUT/trace.log)
             python tools/summarize_prof.py $OUT $wl $TAG > $OUT/summarize.log 2>&1
             find $OUT -name "*.csv" -size +4M -delete
             head -12 $OUT/kernel_stats_summary.txt; head -30 $OUT/kernel_roofline.txt ;;
         pmc)
-            wl=${rest%%:*}; extra=""; [[ "$rest" == *:* ]] && extra=${rest#*:}; extra=${extra//,/ }
+            wl=${rest%%:*}; extra=""; [[ "$rest" == *:* ]] && extra=${rest#*:}; extra="--full ${extra//,/ }"
             OUT=$PWD/gpurun_out/prof_${TAG}_$wl; mkdir -p $OUT
             for c in FETCH_SIZE WRITE_SIZE; do
                 sub=pmc_fetch; [ $c = WRITE_SIZE ] && sub=pmc_write
