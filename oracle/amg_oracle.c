@@ -41,6 +41,20 @@
 #undef RFABS
 #undef REPS
 
+/* 80-bit extended precision (x86-64 long double, 64-bit significand): the yardstick of the device's fast-order sweeps, whose
+ * rounding is compared against that of the fp64 sequential sweep (tests/test_gpu_midsize.py) */
+#define REAL long double
+#define FN(x) orc_##x##_f80
+#define RSQRT sqrtl
+#define RFABS fabsl
+#define REPS LDBL_EPSILON
+#include "amg_oracle_impl.h"
+#undef REAL
+#undef FN
+#undef RSQRT
+#undef RFABS
+#undef REPS
+
 
 /* Greedy aggregation of a strength graph.  Follows amg_core standard_aggregation, smoothed_aggregation.h:137-268:
  * pass 1 -- in index order a node none of whose neighbours (nor itself) is taken founds an aggregate of itself and

@@ -54,6 +54,8 @@ def _sfx(dt):
         return "f64", C.c_double
     if dt == np.float32:
         return "f32", C.c_float
+    if dt == np.longdouble and dt.itemsize > 8:
+        return "f80", C.c_longdouble
     raise TypeError(f"oracle: unsupported dtype {dt}")
 
 

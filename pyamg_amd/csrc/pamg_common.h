@@ -232,6 +232,7 @@ struct pamg_matrix_s {
     // fast order of the BSR POINT sweep (amg_core::bsr_gauss_seidel): the same rows in the same order are the scalar Gauss-Seidel sweep of the
     // flattened view, so a block operator swept in fast order owns a scalar CSR twin of itself that carries the lane / merged / line schedules
     pamg_matrix_s *point_twin = nullptr;
+    size_t point_twin_bytes = 0;     // what the twin added to `bytes` when it was made
     bool point_twin_unfit = false;   // no fast-order form fits the flattened rows (or the twin could not be built): the exact block kernels sweep
     pamg::LineSchedule *ls[4] = {nullptr, nullptr, nullptr, nullptr};  // Kaczmarz sweeps over this operator's rows
     size_t bytes = 0;
@@ -254,6 +255,8 @@ int stream_launch_part(pamg_matrix_s *A, int part, int epi, const void *x, const
                        double omega, double *partial, hipStream_t s);
 int matrix_split_ranges(pamg_matrix_s *A, int64_t n_owned_cols);
 void matrix_drop_value_codes(pamg_matrix_s *A);
+void matrix_drop_point_twin(pamg_matrix_s *A);
+void matrix_drop_schedules(pamg_matrix_s *A);
 int gs_sweep(pamg_matrix_s *A, int epi, void *x, const void *b, double omega, int row_start,
              int row_stop, int row_step, hipStream_t s);
 int reduce_partials(const double *partial, int n, double *out, hipStream_t s);

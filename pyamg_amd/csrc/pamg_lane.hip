@@ -1079,13 +1079,7 @@ static int lane_launch_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, cons
 int lane_launch(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, const void *b, double omega, hipStream_t s)
 {
     if (g->lanem && epi != EPI_SOR && A->dtype == PAMG_F64) return lanem_launch(A, g, x, b, s);
-    if (!g->lane) {
-        // an SOR sweep on an operator that holds the merged layout only (a bare operator tuned by hand; a solver announces SOR before its
-        // schedules are built, pamg_solver.hip: prebuild_schedules): the unmerged layout is built now -- allocations, so not inside a graph capture
-        const size_t before = g->bytes;
-        PAMG_TRY(build_lane_part(A, g));
-        A->bytes += g->bytes - before;
-    }
+    if (!g->lane) return PAMG_E_STATE;                       // built by the caller (pamg_matrix.hip: gs_sweep_scalar_t)
     if (A->dtype == PAMG_F64) return lane_launch_t<double>(A, g, epi, x, b, omega, s);
     return lane_launch_t<float>(A, g, epi, x, b, omega, s);
 }

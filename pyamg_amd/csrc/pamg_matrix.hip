@@ -864,6 +864,43 @@ namespace pamg {
 // the operator's values are about to change in place (setup kernels rescale a resident operator): its value codes go
 void matrix_drop_value_codes(pamg_matrix_s *A) { if (A) drop_val8(A); }
 
+// the scalar twin of a block operator (the point sweep's fast order) holds a snapshot of the values and the lane keys of the moment it
+// was made: when either changes it goes, and the next point sweep makes a fresh one (or finds again that none fits)
+void matrix_drop_point_twin(pamg_matrix_s *A)
+{
+    if (!A) return;
+    pamg_matrix_s *T = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_sched_mu);
+        T = A->point_twin;
+        if (T) A->bytes -= std::min(A->bytes, A->point_twin_bytes);
+        A->point_twin = nullptr;
+        A->point_twin_bytes = 0;
+        A->point_twin_unfit = false;
+    }
+    if (T) pamg_matrix_destroy(T);
+}
+
+// the operator's values are about to change in place: every sweep schedule holds copies of them (rebuilt at the next sweep)
+void matrix_drop_schedules(pamg_matrix_s *A)
+{
+    if (!A) return;
+    for (int k = 0; k < 4; ++k) {
+        GsSchedule *g = nullptr;
+        LineSchedule *l = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(g_sched_mu);
+            g = A->gs[k]; l = A->ls[k];
+            if (g) A->bytes -= std::min(A->bytes, g->bytes);
+            if (l) A->bytes -= std::min(A->bytes, l->bytes);       // its Kaczmarz lane part included
+            A->gs[k] = nullptr; A->ls[k] = nullptr;
+        }
+        free_schedule(g);
+        if (l) free_line_schedule(l);
+    }
+    matrix_drop_point_twin(A);
+}
+
 // Row ranges of a row shard in local numbering [owned | halo] cut in two: INTERIOR ranges touch owned columns only
 // (they can run while the halo is still in flight), BOUNDARY ranges read at least one halo column.  Two index lists
 // into the existing plan -- no operator data is copied.
@@ -1173,9 +1210,9 @@ int ensure_point_twin(pamg_matrix_s *A, GsSchedule *g)
             if (st != PAMG_OK) { A->point_twin_unfit = true; return st == PAMG_E_UNSUPPORTED || st == PAMG_E_ARG ? PAMG_OK : st; }
             T->gs_order = 1;
             T->lane_L = A->lane_L; T->lane_G = A->lane_G; T->lane_flags = A->lane_flags; T->lane_merge = A->lane_merge; T->line_scan = A->line_scan;
-            T->lane_wide = A->lane_wide;
+            T->lane_wide = A->lane_wide; T->lanem_rpw = A->lanem_rpw; T->lanem_ahead10 = A->lanem_ahead10; T->gran_xcd = A->gran_xcd;
             A->point_twin = T;
-            { std::lock_guard<std::mutex> lk2(g_sched_mu); A->bytes += T->bytes; }
+            { std::lock_guard<std::mutex> lk2(g_sched_mu); A->bytes += T->bytes; A->point_twin_bytes = T->bytes; }
         }
     }
     GsSchedule *tg = nullptr;
@@ -1241,6 +1278,23 @@ static int gs_sweep_scalar_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, 
 {
     PAMG_TRY(ensure_parts(A, g));
     if (want_lines(A, g)) return line_launch(A, g, epi, x, b, omega, s);
+    if (want_lanes(A, g) && !g->lane && !(g->lanem && epi != EPI_SOR && A->dtype == PAMG_F64)) {
+        // an SOR sweep on an operator that holds the merged layout only (a bare operator tuned by hand; a solver decides SOR before its
+        // schedules are built, pamg_solver_finalize): the unmerged layout is built now -- allocations, so never inside a graph capture
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        PAMG_HIP(hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone) return PAMG_E_STATE;
+        const size_t before = g->bytes;
+        const int st = build_lane_part(A, g);
+        if (st == PAMG_OK) { std::lock_guard<std::mutex> lk(g_sched_mu); A->bytes += g->bytes - before; }
+        else if (st != PAMG_E_ARG) return st;
+        else {
+            // does not fit: the exact schedulers take the sweep.  lane_unfit also retires the merged layout of this schedule (lane_eligible
+            // reads it), so its Gauss-Seidel sweeps move to the exact schedulers as well: one layout per schedule
+            g->lane_unfit = true;
+            PAMG_TRY(ensure_parts(A, g));
+        }
+    }
     if (want_lanes(A, g)) return lane_launch(A, g, epi, x, b, omega, s);
     if (want_tiles(A, g)) return tile_launch<T>(A, g, epi, x, b, omega, s);
     StreamArgs<T> a = base_args<T>(A, x, b, x, 0.0, omega, nullptr);
@@ -1917,7 +1971,7 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
         case 3: if (value < 0 || value > 256) return PAMG_E_ARG; A->flow_cap = value; return PAMG_OK;
         case 5: if (value < 0 || value > 5) return PAMG_E_ARG; A->gs_mode = value; return PAMG_OK;
         case 6: if (value < 0) return PAMG_E_ARG; A->gran_cap = value; return PAMG_OK;
-        case 7: if (value < 0 || value > 2) return PAMG_E_ARG; A->gran_xcd = value; return PAMG_OK;
+        case 7: if (value < 0 || value > 2) return PAMG_E_ARG; A->gran_xcd = value; matrix_drop_point_twin(A); return PAMG_OK;
         case 8: if (value < 0 || value > 63) return PAMG_E_ARG; A->stream_flags = value; return PAMG_OK;
         case 11: A->gs_prof = value != 0; return PAMG_OK;
         case 12: if (value < 0) return PAMG_E_ARG; A->tile_G = value; break;
@@ -1931,23 +1985,25 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
         case 20: if (value != 0 && (value < 64 || value > 2048)) return PAMG_E_ARG; A->gs_cap = value & ~3; break;
         case 24: if (value < 0 || value > 1) return PAMG_E_ARG; A->gs_order = value; return PAMG_OK;
         case 25: if (value != 0 && value != 4 && value != 8 && value != 16 && value != 32 && value != 64) return PAMG_E_ARG; A->lane_L = value; break;
-        case 26: if (value < 0) return PAMG_E_ARG; A->lane_G = value; return PAMG_OK;
-        case 27: if (value < 0 || value > 1) return PAMG_E_ARG; A->lane_wide = value; return PAMG_OK;
+        case 26: if (value < 0) return PAMG_E_ARG; A->lane_G = value; matrix_drop_point_twin(A); return PAMG_OK;
+        case 27: if (value < 0 || value > 1) return PAMG_E_ARG; A->lane_wide = value; matrix_drop_point_twin(A); return PAMG_OK;
         case 33: if (value < 0 || value > 8) return PAMG_E_ARG; A->lane_merge = value; break;
         case 35: if (value < 0 || value > 2) return PAMG_E_ARG; A->lanem_rpw = value; break;
         case 36: if (value < 0 || value > 98304) return PAMG_E_ARG; A->lds_pad = value & ~15; return PAMG_OK;
-        case 34: if (value < 1 || value > 400) return PAMG_E_ARG; A->lanem_ahead10 = value; return PAMG_OK;
+        case 34: if (value < 1 || value > 400) return PAMG_E_ARG; A->lanem_ahead10 = value; matrix_drop_point_twin(A); return PAMG_OK;
         case 30:                                               // 2: also where the estimate favours the lane form
             if (value < 0 || value > 2) return PAMG_E_ARG;
             A->line_scan = value;
+            matrix_drop_point_twin(A);
             for (int k = 0; k < 4; ++k) if (A->gs[k]) A->gs[k]->line_unfit = false;      // a schedule the planner declined on its estimate is asked again
             return PAMG_OK;
         case 31: if (value != 2 && value != 4 && value != 8) return PAMG_E_ARG; A->rowmask_kz = value; return PAMG_OK;
         case 32: if (value < 0 || value > 7) return PAMG_E_ARG; A->rowmask_flags = value; return PAMG_OK;
-        case 28: if (value < 0 || value > 15 || (value & 6)) return PAMG_E_ARG; A->lane_flags = value; return PAMG_OK;      // bits 1, 2: retired (slab form, old values through the L1)
+        case 28: if (value < 0 || value > 15 || (value & 6)) return PAMG_E_ARG; A->lane_flags = value; matrix_drop_point_twin(A); return PAMG_OK;      // bits 1, 2: retired (slab form, old values through the L1)
         default: return PAMG_E_ARG;
     }
-    if (key == 25 || key == 33 || key == 35) {         // lane geometry / merging: drop the lane parts only
+    if (key == 25 || key == 33 || key == 35) {         // lane geometry / merging: drop the lane parts only (and the point twin, which copied the keys)
+        matrix_drop_point_twin(A);
         for (int k = 0; k < 4; ++k) {
             GsSchedule *g = A->gs[k];
             if (g) g->lane_unfit = false;
@@ -1969,6 +2025,7 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
         return PAMG_OK;
     }
     for (int k = 0; k < 4; ++k) { if (A->gs[k]) A->bytes -= A->gs[k]->bytes; free_schedule(A->gs[k]); A->gs[k] = nullptr; }
+    matrix_drop_point_twin(A);                          // it sweeps for the schedules just dropped
     return replan(A);
 }
 

@@ -1253,7 +1253,7 @@ int pamg_matrix_scale_rows(pamg_matrix_t A, const double *d)
     if (!A || !d) return PAMG_E_ARG;
     if (A->dtype != PAMG_F64) return PAMG_E_UNSUPPORTED;
     if (A->borrowed) return PAMG_E_STATE;
-    for (int k = 0; k < 4; ++k) if (A->gs[k] || A->ls[k]) return PAMG_E_STATE;   // schedules hold copies of the values
+    matrix_drop_schedules(A);                          // schedules and the point twin hold copies of the values (rebuilt at the next sweep)
     drop_block_view(A);
     const int m = (int)A->nrows;
     double *dd = nullptr;
@@ -1274,7 +1274,7 @@ int pamg_matrix_scale_values(pamg_matrix_t A, double alpha)
     if (!A) return PAMG_E_ARG;
     if (A->dtype != PAMG_F64) return PAMG_E_UNSUPPORTED;
     if (A->borrowed) return PAMG_E_STATE;
-    for (int k = 0; k < 4; ++k) if (A->gs[k] || A->ls[k]) return PAMG_E_STATE;
+    matrix_drop_schedules(A);
     drop_block_view(A);
     matrix_drop_value_codes(A);
     if (A->nnz) hipLaunchKernelGGL(scale_values_kernel, dim3(grid_for(A->nnz)), dim3(BLK), 0, 0, A->nnz, alpha, (double *)A->d_Ax);

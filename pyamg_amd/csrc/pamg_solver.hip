@@ -472,6 +472,13 @@ int run_cycle(pamg_solver_s *S, int type, int cpl, hipStream_t s, bool check = t
 
 int ensure_amli(pamg_solver_s *S, int cycle);
 
+// SOR's relaxation parameter takes effect on this operator (gs_apply): the CSR flavour, a one-directional sweep, omega != 1 -- the
+// reference's quirks make every other "SOR" a plain Gauss-Seidel sweep
+static bool sor_takes_omega(const pamg_matrix_s *A, const Smoother &sm)
+{
+    return sm.kind == PAMG_SMOOTH_SOR && A->R == 1 && A->flavour != PAMG_BSR && sm.sweep != PAMG_SYMMETRIC && sm.omega != 1.0;
+}
+
 int prebuild_schedules(Level &L, const Smoother &sm)
 {
     if (sm.kind == PAMG_SMOOTH_GS_NE || sm.kind == PAMG_SMOOTH_GS_NR) {
@@ -487,7 +494,7 @@ int prebuild_schedules(Level &L, const Smoother &sm)
     if (!gs || L.A->nrows == 0) return PAMG_OK;
     // the merged lane form (pamg_lanem_plan.h) eliminates dependency levels with coefficients that would depend on SOR's relaxation
     // parameter: an operator swept by SOR keeps the unmerged layout (one layout per schedule)
-    if (sm.kind == PAMG_SMOOTH_SOR && L.A->lane_merge == 0) L.A->lane_merge = 1;
+    if (sor_takes_omega(L.A, sm) && L.A->lane_merge == 0) L.A->lane_merge = 1;
     int r0, r1, rs;
     if (sm.sweep == PAMG_FORWARD || sm.sweep == PAMG_SYMMETRIC) {
         PAMG_TRY(sweep_bounds(L.A, PAMG_FORWARD, r0, r1, rs));
@@ -1346,6 +1353,12 @@ int pamg_solver_finalize(pamg_solver_t S)
         }
     }
     const int nsm = S->coarse_relax ? nlev : nlev - 1;      // levels that carry a relaxation method
+    for (int l = 0; l < nsm; ++l) {
+        // an operator swept by SOR in either slot keeps the unmerged lane layout (prebuild_schedules): decided from both smoothers
+        // BEFORE the jobs build anything -- a merged layout built first would leave SOR to a lazy build at its first sweep
+        Level &L = S->levels[l];
+        if ((sor_takes_omega(L.A, L.pre) || sor_takes_omega(L.A, L.post)) && L.A->lane_merge == 0) L.A->lane_merge = 1;
+    }
     {
         std::vector<SchedJob> jobs;
         for (int l = 0; l < nsm; ++l) { sched_jobs_of(S->levels[l], S->levels[l].pre, jobs); sched_jobs_of(S->levels[l], S->levels[l].post, jobs); }
