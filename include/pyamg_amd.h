@@ -676,6 +676,23 @@ int pamg_solver_fgmres(pamg_solver_t S, void *x, const void *b, double tol, int 
 int pamg_solver_gmres(pamg_solver_t S, void *x, const void *b, double tol, int maxiter, int restart,
                       int cycle, int cycles_per_level, double *residuals, int residuals_cap, int *n_res,
                       int *n_iter, int *info, pamg_stream_t s);
+/* BiCGStab, conjugate residual, steepest descent and minimal residual with the resident cycle as
+ * preconditioner, all vectors on the DEVICE (reference: pyamg/krylov/_bicgstab.py, _cr.py,
+ * _steepest_descent.py, _minimal_residual.py with criteria 'rr', as driven by
+ * MultilevelSolver.solve(accel=...)).  M is one cycle from a zero guess.  x: in = initial guess, out =
+ * solution.  maxiter <= 0: the method's own default (n + 5, 1.3 n + 2, n, 1.3 n + 2).  residuals: HOST
+ * array of residuals_cap doubles (may be NULL); *n_res = entries the reference's list would hold
+ * (minimal residual: preconditioned norms ||M r||).  *info: 0 converged, -1 breakdown detected as the
+ * reference detects it (CR, steepest descent, minimal residual), else the iteration count.  One host
+ * read-back per iteration.  Needs up to 5 device vectors of work (allocated on first use, kept with the
+ * solver); n must be >= 2 (PAMG_E_UNSUPPORTED otherwise). */
+#define PAMG_ACCEL_BICGSTAB 0
+#define PAMG_ACCEL_CR 1
+#define PAMG_ACCEL_STEEPEST_DESCENT 2
+#define PAMG_ACCEL_MINIMAL_RESIDUAL 3
+int pamg_solver_krylov(pamg_solver_t S, int method, void *x, const void *b, double tol, int maxiter,
+                       int cycle, int cycles_per_level, double *residuals, int residuals_cap,
+                       int *n_res, int *n_iter, int *info, pamg_stream_t s);
 /* Same iteration split in three so that callers (benchmarks, device-side Krylov drivers)
  * can run exactly k cycles on the resident state with no staging copies in between:
  * load copies DEVICE x, b into the solver's level-0 buffers; iterate runs k x (cycle +

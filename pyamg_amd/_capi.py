@@ -24,6 +24,7 @@ FORWARD, BACKWARD, SYMMETRIC = 0, 1, 2
 SMOOTH = {"schwarz": 14, "cf_block_jacobi": 12, "fc_block_jacobi": 13, "gauss_seidel_ne": 9, "gauss_seidel_nr": 10, "jacobi_ne": 11, "cf_jacobi": 7, "fc_jacobi": 8, "none": 0, "jacobi": 1, "gauss_seidel": 2, "sor": 3, "polynomial": 4,
           "block_jacobi": 5, "block_gauss_seidel": 6}
 KRYLOV = {"cg": 0, "gmres": 1, "cgne": 2, "cgnr": 3}
+ACCEL = {"bicgstab": 0, "cr": 1, "steepest_descent": 2, "minimal_residual": 3}     # pamg_solver_krylov methods (PAMG_ACCEL_*)
 SWEEP = {"forward": FORWARD, "backward": BACKWARD, "symmetric": SYMMETRIC}
 CYCLE = {"V": 0, "W": 1, "F": 2, "AMLI": 3}
 
@@ -181,6 +182,7 @@ def _declare(lib):
     f("pamg_solver_pcg", _vp, _vp, _vp, _d, _i, _i, _i, _vp, P(_i), P(_i), _vp)
     f("pamg_solver_fgmres", _vp, _vp, _vp, _d, _i, _i, _i, _i, _vp, _i, P(_i), P(_i), P(_i), _vp)
     f("pamg_solver_gmres", _vp, _vp, _vp, _d, _i, _i, _i, _i, _vp, _i, P(_i), P(_i), P(_i), _vp)
+    f("pamg_solver_krylov", _vp, _i, _vp, _vp, _d, _i, _i, _i, _vp, _i, P(_i), P(_i), P(_i), _vp)
     f("pamg_solver_load", _vp, _vp, _vp, _vp)
     f("pamg_solver_iterate", _vp, _i, _i, _i, _vp, _vp)
     f("pamg_solver_store", _vp, _vp, _vp)

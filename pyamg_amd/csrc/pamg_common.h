@@ -285,6 +285,28 @@ int block_jacobi_step(pamg_matrix_s *A, int kind, const void *Dinv, const void *
 int ensure_schedule(pamg_matrix_s *A, int row_start, int row_stop, int row_step, bool block_gs = false);
 struct CsrArrays { int64_t m, n, nnz; const int *p, *j; const double *x; };
 int csr_device_arrays(struct ::pamg_csr_s *A, CsrArrays *out);                                  // pamg_setup.hip: the device arrays behind a pamg_csr_t
+// pamg_krylov.hip: fused vector steps of the BiCGStab / CR / steepest-descent / minimal-residual accelerators.  Scalars are read from
+// (and step sizes written to) device slots; `part` holds the per-workgroup partials of up to 3 inner products (KR_PARTIALS doubles),
+// kr_reduce sums the first k of them into *o0, *o1, *o2 (n: the vector length the partials were taken over)
+constexpr int KR_PARTIALS = 3 * 2048;
+int kr_reduce(int64_t n, const double *part, int k, double *o0, double *o1, double *o2, hipStream_t s);
+int kr_dots(int dtype, int64_t n, int k, const void *a0, const void *b0, const void *a1, const void *b1, const void *a2, const void *b2,
+            double *part, hipStream_t s);
+int bicg_alpha(int dtype, int64_t n, const double *rr, const double *d, double *alpha, void *x, void *xc, const void *r, const void *AMp,
+               void *bc, hipStream_t s);
+int bicg_omega(int dtype, int64_t n, const double *num, const double *den, double *omega, void *x, const void *xc, const void *bc,
+               const void *AMs, void *r, const void *rstar, double *part, hipStream_t s);
+int bicg_dir(int dtype, int64_t n, const double *rr_new, const double *rr_old, const double *alpha, const double *omega, const void *r,
+             void *p, const void *AMp, void *bc, void *xc, hipStream_t s);
+int cr_update(int dtype, int64_t n, const double *rAz, const double *ApAp, void *x, const void *p, void *r, const void *Ap, bool update_r,
+              void *xc, hipStream_t s);
+int cr_dir(int dtype, int64_t n, const double *rAz_new, const double *rAz_old, void *p, const void *z, void *Ap, const void *Az,
+           double *part, hipStream_t s);
+int sd_update(int dtype, int64_t n, const double *rz, const double *zAz, void *x, void *xc, void *r, const void *q, bool update_r,
+              hipStream_t s);
+int mr_update(int dtype, int64_t n, const double *pz, const double *pp, void *x, void *z, void *xc, bool update_z, double *part,
+              hipStream_t s);
+int kr_take(int dtype, int64_t n, void *xc, void *dst, double *part, hipStream_t s);
 int solver_cycle_inline(pamg_solver_s *S, void *x, const void *b, int cycle, int cpl, hipStream_t s, bool allow_graph);   // pamg_solver.hip
 bool solver_needs_host_sync(const pamg_solver_s *S);                                                                   // pamg_solver.hip
 // pamg_line.hip: the line-scan fast-order sweep (banded operators in their natural order)

@@ -187,6 +187,8 @@ struct pamg_solver_s {
     double *d_slot = nullptr;     // 4 doubles: [0] current ||r||^2, [1] ||b||^2
     double *d_scratch = nullptr;  // 1032 doubles for vector reductions
     void *cg_r = nullptr, *cg_z = nullptr, *cg_p = nullptr, *cg_q = nullptr;   // device PCG work vectors
+    void *kr_v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // BiCGStab / CR / SD / MR work vectors (allocated on first use)
+    double *kr_red = nullptr;     // KR_PARTIALS inner-product partials + 16 scalar slots of those accelerators
     std::map<int, hipGraphExec_t> graphs;   // key = cycle*1024 + cycles_per_level
     bool host_sync = false;       // a Krylov smoother / coarse solver reads scalars back inside the cycle: no graph capture
     int fallbacks = 0;            // times a persistent sweep timed out and the solver switched to per-level launches
@@ -937,6 +939,226 @@ int krylov_householder(pamg_solver_s *S, pamg_matrix_s *Aop, int64_t n, bool fle
 }
 
 
+// BiCGStab, CR, steepest descent and minimal residual with the resident cycle as preconditioner M (one cycle from x = 0), faithful
+// restatements of the reference's krylov/_bicgstab.py, _cr.py, _steepest_descent.py and _minimal_residual.py under criteria 'rr' as
+// MultilevelSolver.solve(accel=...) drives them (multilevel.py:479-535).  The operand of M is the fine level's right-hand side
+// L0.b and its result the fine level's iterate L0.x: each method keeps the vector it preconditions there (r for CR and SD, s and
+// then the new direction for BiCGStab, A z for MR), and the fused steps of pamg_krylov.hip clear L0.x behind the last reader of a
+// cycle's result.  Per iteration the host reads back ONE group of scalars -- the residual norm and whatever breakdown test the
+// reference makes -- everything else (step sizes, inner products) stays in device slots.
+struct KrylovRun {
+    pamg_solver_s *S;
+    Level &L0;
+    int dt;
+    int64_t n;
+    size_t vb;
+    int cycle, cpl;
+    hipStream_t s;
+    double *part, *sl;              // partials, scalar slots (S->kr_red)
+    double *residuals;
+    int cap, nres = 0;
+    double h[8];
+
+    void push(double v) { if (residuals && nres < cap) residuals[nres] = v; ++nres; }
+    int fetch(int first, int k)     // h[0..k) = sl[first .. first+k): the iteration's one read-back
+    {
+        PAMG_HIP(hipMemcpyAsync(h, sl + first, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, s));
+        return (int)hipStreamSynchronize(s);
+    }
+    int precond() { return run_cycle(S, cycle, cpl, s, false, true); }   // L0.x = M L0.b (L0.x is zero on entry)
+    int dots(int k, const void *a0, const void *b0, const void *a1, const void *b1, const void *a2, const void *b2, double *o0,
+             double *o1 = nullptr, double *o2 = nullptr)
+    {
+        PAMG_TRY(kr_dots(dt, n, k, a0, b0, a1, b1, a2, b2, part, s));
+        return kr_reduce(n, part, k, o0, o1, o2, s);
+    }
+    int reduce(int k, double *o0, double *o1 = nullptr) { return kr_reduce(n, part, k, o0, o1, nullptr, s); }
+    int matvec(const void *v, void *out) { return stream_launch(L0.A, EPI_SET, v, nullptr, out, 0.0, 0.0, nullptr, s); }
+    int residual(const void *x, const void *b, void *out) { return stream_launch(L0.A, EPI_RESID, x, b, out, 0.0, 0.0, nullptr, s); }
+    int copy(void *dst, const void *src) { return (int)hipMemcpyAsync(dst, src, vb, hipMemcpyDeviceToDevice, s); }
+};
+
+// krylov/_bicgstab.py:84-188.  No breakdown test (the reference has none): a zero denominator gives inf / nan as NumPy's does.
+// Work: r, r*, p, A M p, A M s.  Slots: [0,1] (r*, r) of this / the next iteration, [2] (r*, AMp), [3] alpha, [4] omega,
+// [5] (AMs, s), [6] (AMs, AMs), [7] ||r||^2, [8] ||b||^2.
+int bicgstab_core(KrylovRun &K, void *x, const void *b, double tol, int maxiter, int &it, int &inf)
+{
+    void **v = K.S->kr_v;
+    void *r = v[0], *rstar = v[1], *p = v[2], *AMp = v[3], *AMs = v[4];
+    void *bc = K.L0.b, *xc = K.L0.x;
+    double *sl = K.sl;
+    PAMG_TRY(K.residual(x, b, r));                                                        // r = b - A x
+    PAMG_TRY(K.dots(3, r, r, b, b, r, r, sl + 7, sl + 8, sl + 0));                        // ||r||^2, ||b||^2, (r*, r) with r* = r
+    PAMG_TRY(K.fetch(7, 2));
+    const double normr0 = std::sqrt(K.h[0]);
+    double normb = std::sqrt(K.h[1]);
+    K.push(normr0);
+    if (normb == 0.0) normb = 1.0;
+    const double rtol = tol * normb;
+    if (normr0 < rtol) { inf = 0; return PAMG_OK; }
+    PAMG_TRY(K.copy(rstar, r));
+    PAMG_TRY(K.copy(p, r));
+    PAMG_TRY(K.copy(bc, r));                                                              // the first cycle's operand: p
+    PAMG_HIP(hipMemsetAsync(xc, 0, K.vb, K.s));
+    while (true) {
+        double *rr_old = sl + (it & 1), *rr_new = sl + ((it + 1) & 1);
+        PAMG_TRY(K.precond());                                                            // xc = M p
+        PAMG_TRY(K.matvec(xc, AMp));
+        PAMG_TRY(K.dots(1, rstar, AMp, nullptr, nullptr, nullptr, nullptr, sl + 2));
+        PAMG_TRY(bicg_alpha(K.dt, K.n, rr_old, sl + 2, sl + 3, x, xc, r, AMp, bc, K.s));  // x += alpha Mp; bc = s; xc = 0
+        PAMG_TRY(K.precond());                                                            // xc = M s
+        PAMG_TRY(K.matvec(xc, AMs));
+        PAMG_TRY(K.dots(2, AMs, bc, AMs, AMs, nullptr, nullptr, sl + 5, sl + 6));
+        PAMG_TRY(bicg_omega(K.dt, K.n, sl + 5, sl + 6, sl + 4, x, xc, bc, AMs, r, rstar, K.part, K.s));   // x += omega Ms; r = s - omega AMs
+        PAMG_TRY(K.reduce(2, rr_new, sl + 7));
+        PAMG_TRY(bicg_dir(K.dt, K.n, rr_new, rr_old, sl + 3, sl + 4, r, p, AMp, bc, xc, K.s));          // p = r + beta (p - omega AMp); bc = p
+        PAMG_TRY(K.fetch(7, 1));
+        ++it;
+        const double normr = std::sqrt(K.h[0]);
+        K.push(normr);
+        if (normr < rtol) { inf = 0; break; }
+        if (it == maxiter) { inf = it; break; }
+    }
+    return PAMG_OK;
+}
+
+// krylov/_cr.py:87-199.  r lives in bc, z = M r in xc.  Work: p, Ap, Az.  Slots: [0,1] (r, Az) of this / the next iteration,
+// [2] (Ap, Ap), [3] (z, z), [4] ||r||^2, [5] ||b||^2.
+int cr_core(KrylovRun &K, void *x, const void *b, double tol, int maxiter, int &it, int &inf)
+{
+    void **v = K.S->kr_v;
+    void *p = v[0], *Ap = v[1], *Az = v[2];
+    void *r = K.L0.b, *xc = K.L0.x;
+    double *sl = K.sl;
+    PAMG_TRY(K.residual(x, b, r));                                                        // r = b - A x
+    PAMG_HIP(hipMemsetAsync(xc, 0, K.vb, K.s));
+    PAMG_TRY(K.precond());                                                                // z = M r
+    PAMG_TRY(K.dots(2, r, r, b, b, nullptr, nullptr, sl + 4, sl + 5));
+    PAMG_TRY(K.fetch(4, 2));
+    const double normr0 = std::sqrt(K.h[0]);
+    double normb = std::sqrt(K.h[1]);
+    K.push(normr0);
+    if (normb == 0.0) normb = 1.0;
+    const double rtol = tol * normb;
+    if (normr0 < rtol) { inf = 0; return PAMG_OK; }
+    PAMG_TRY(K.matvec(xc, Az));                                                           // Az = A z
+    PAMG_TRY(K.copy(p, xc));                                                              // p = z
+    PAMG_TRY(K.copy(Ap, Az));                                                             // Ap = A p: the same product, the same bits
+    PAMG_TRY(K.dots(2, r, Az, Ap, Ap, nullptr, nullptr, sl + 0, sl + 2));
+    while (true) {
+        double *rAz_old = sl + (it & 1), *rAz_new = sl + ((it + 1) & 1);
+        const bool recompute = !((it % 8) != 0 && it > 0);                                // _cr.py:151-154
+        PAMG_TRY(cr_update(K.dt, K.n, rAz_old, sl + 2, x, p, r, Ap, !recompute, xc, K.s));   // x += alpha p; [r -= alpha Ap]; xc = 0
+        if (recompute) PAMG_TRY(K.residual(x, b, r));
+        PAMG_TRY(K.precond());                                                            // z = M r
+        PAMG_TRY(K.matvec(xc, Az));
+        PAMG_TRY(K.dots(3, r, Az, xc, xc, r, r, rAz_new, sl + 3, sl + 4));
+        PAMG_TRY(cr_dir(K.dt, K.n, rAz_new, rAz_old, p, xc, Ap, Az, K.part, K.s));        // p = beta p + z; Ap = beta Ap + Az
+        PAMG_TRY(K.reduce(1, sl + 2));
+        PAMG_TRY(K.fetch(3, 2));
+        ++it;
+        const double zz = K.h[0], normr = std::sqrt(K.h[1]);
+        K.push(normr);
+        if (normr < rtol) { inf = 0; break; }
+        if (zz == 0.0) { inf = -1; break; }                                               // singular preconditioner
+        if (it == maxiter) { inf = it; break; }
+    }
+    return PAMG_OK;
+}
+
+// krylov/_steepest_descent.py:92-197.  r lives in bc, z = M r in xc.  Work: q = A z.  Slots: [0] (r, z), [1] (z, A z),
+// [2] ||r||^2, [3] ||b||^2.  The curvature test of A comes before the update of x in the reference: sd_update skips that write
+// when (z, A z) < 0, and the host reports -1 from the same read-back as the residual.
+int sd_core(KrylovRun &K, void *x, const void *b, double tol, int maxiter, int &it, int &inf)
+{
+    void *q = K.S->kr_v[0];
+    void *r = K.L0.b, *xc = K.L0.x;
+    double *sl = K.sl;
+    PAMG_TRY(K.residual(x, b, r));
+    PAMG_HIP(hipMemsetAsync(xc, 0, K.vb, K.s));
+    PAMG_TRY(K.precond());                                                                // z = M r
+    PAMG_TRY(K.dots(3, r, xc, r, r, b, b, sl + 0, sl + 2, sl + 3));
+    PAMG_TRY(K.fetch(2, 2));
+    double normb = std::sqrt(K.h[1]);
+    K.push(std::sqrt(K.h[0]));
+    if (normb == 0.0) normb = 1.0;
+    const double rtol = tol * normb;                                                      // (the reference does not test the initial guess)
+    while (true) {
+        PAMG_TRY(K.matvec(xc, q));                                                        // q = A z
+        PAMG_TRY(K.dots(1, xc, q, nullptr, nullptr, nullptr, nullptr, sl + 1));
+        // The reference's recompute test is inverted (`if np.mod(it, recompute_r) and it > 0: r = b - A x`, it already
+        // incremented): r is recomputed on every iteration EXCEPT multiples of 50, where it is updated.  Kept as it is.
+        const bool recompute = ((it + 1) % 50) != 0;
+        PAMG_TRY(sd_update(K.dt, K.n, sl + 0, sl + 1, x, xc, r, q, !recompute, K.s));     // x = x + alpha z; [r = r - alpha q]; xc = 0
+        if (recompute) PAMG_TRY(K.residual(x, b, r));
+        PAMG_TRY(K.precond());                                                            // z = M r
+        PAMG_TRY(K.dots(2, r, xc, r, r, nullptr, nullptr, sl + 0, sl + 2));
+        PAMG_TRY(K.fetch(0, 3));
+        const double rz = K.h[0], zAz = K.h[1], normr = std::sqrt(K.h[2]);
+        if (zAz < 0.0) { inf = -1; break; }                                               // indefinite A: x was not touched
+        ++it;
+        if (rz < 0.0) { inf = -1; break; }                                                // indefinite M (before the history entry)
+        K.push(normr);
+        if (normr < rtol) { inf = 0; break; }
+        if (rz == 0.0) { inf = -1; break; }                                               // singular M
+        if (it == maxiter) { inf = it; break; }
+    }
+    return PAMG_OK;
+}
+
+// krylov/_minimal_residual.py:95-163: residuals and the stopping test are preconditioned norms ||z|| = ||M r||, relative to
+// ||M b|| (one more cycle at setup; 1 when b = 0).  Work: z.  A z is written straight into bc (the operand of M), p = M A z
+// arrives in xc.  Slots: [0] (p, z), [1] (p, p), [2] ||z||^2, [3] ||b||^2, [4] ||M b||^2.
+int mr_core(KrylovRun &K, void *x, const void *b, double tol, int maxiter, int &it, int &inf)
+{
+    void *z = K.S->kr_v[0];
+    void *bc = K.L0.b, *xc = K.L0.x;
+    double *sl = K.sl;
+    PAMG_TRY(K.residual(x, b, bc));                                                       // r = b - A x
+    PAMG_HIP(hipMemsetAsync(xc, 0, K.vb, K.s));
+    PAMG_TRY(K.precond());
+    PAMG_TRY(kr_take(K.dt, K.n, xc, z, K.part, K.s));                                     // z = M r; xc = 0
+    PAMG_TRY(K.reduce(1, sl + 2));
+    PAMG_TRY(K.dots(1, b, b, nullptr, nullptr, nullptr, nullptr, sl + 3));
+    PAMG_TRY(K.fetch(2, 2));
+    const double normr0 = std::sqrt(K.h[0]);
+    K.push(normr0);
+    double normMb = 1.0;
+    if (K.h[1] != 0.0) {                                                                  // ||M b||
+        PAMG_TRY(K.copy(bc, b));
+        PAMG_TRY(K.precond());
+        PAMG_TRY(K.dots(1, xc, xc, nullptr, nullptr, nullptr, nullptr, sl + 4));
+        PAMG_HIP(hipMemsetAsync(xc, 0, K.vb, K.s));
+        PAMG_TRY(K.fetch(4, 1));
+        normMb = std::sqrt(K.h[0]);
+    }
+    const double rtol = tol * normMb;
+    if (normr0 < rtol) { inf = 0; return PAMG_OK; }
+    while (true) {
+        PAMG_TRY(K.matvec(z, bc));                                                        // bc = A z
+        PAMG_TRY(K.precond());                                                            // p = M A z
+        PAMG_TRY(K.dots(2, xc, z, xc, xc, nullptr, nullptr, sl + 0, sl + 1));
+        // the same inverted recompute test as steepest descent (_minimal_residual.py:145-149): on every iteration but multiples of
+        // 50, r = b - A x and z = M r -- two cycles per iteration
+        const bool recompute = ((it + 1) % 50) != 0;
+        PAMG_TRY(mr_update(K.dt, K.n, sl + 0, sl + 1, x, z, xc, !recompute, K.part, K.s));    // x = x + alpha z; [z = z - alpha p]; xc = 0
+        if (recompute) {
+            PAMG_TRY(K.residual(x, b, bc));
+            PAMG_TRY(K.precond());
+            PAMG_TRY(kr_take(K.dt, K.n, xc, z, K.part, K.s));                             // z = M r; xc = 0
+        }
+        PAMG_TRY(K.reduce(1, sl + 2));
+        PAMG_TRY(K.fetch(0, 3));
+        if (K.h[0] < 0.0) { inf = -1; break; }                                            // indefinite M A: x was not touched
+        ++it;
+        const double normr = std::sqrt(K.h[2]);
+        K.push(normr);
+        if (normr < rtol) { inf = 0; break; }
+        if (it == maxiter) { inf = it; break; }
+    }
+    return PAMG_OK;
+}
+
 // A Krylov method as smoother / coarse solver (smoothing.py:794-830, multilevel.py:752-762): x[:] = method(A, b, x0 = x, ...)[0].
 // The iteration reads scalars back to the host (the reference's stopping rules are data dependent): such a cycle is not captured.
 int krylov_smooth(pamg_solver_s *S, Level &L, const Smoother &sm, hipStream_t s)
@@ -1074,6 +1296,8 @@ int pamg_solver_destroy(pamg_solver_t S)
     }
     hipFree(S->d_coarse); hipFree(S->d_norms); hipFree(S->d_slot); hipFree(S->d_scratch);
     hipFree(S->cg_r); hipFree(S->cg_z); hipFree(S->cg_p); hipFree(S->cg_q);
+    for (void *v : S->kr_v) hipFree(v);
+    hipFree(S->kr_red);
     if (S->own_stream) hipStreamDestroy(S->own_stream);
     delete S;
     return PAMG_OK;
@@ -1613,6 +1837,44 @@ int pamg_solver_gmres(pamg_solver_t S, void *x, const void *b, double tol, int m
 {
     return krylov_accel(S, false, x, b, tol, maxiter, restart, cycle, cycles_per_level, residuals, residuals_cap,
                         n_res, n_iter, info, s);
+}
+
+int pamg_solver_krylov(pamg_solver_t S, int method, void *x, const void *b, double tol, int maxiter, int cycle, int cycles_per_level,
+                       double *residuals, int residuals_cap, int *n_res, int *n_iter, int *info, pamg_stream_t s_)
+{
+    if (!S || !x || !b) return PAMG_E_ARG;
+    if (!S->finalized) return PAMG_E_STATE;
+    if (cycle < PAMG_CYCLE_V || cycle > PAMG_CYCLE_AMLI || cycles_per_level < 1 || cycles_per_level > 1023) return PAMG_E_ARG;
+    if (method < PAMG_ACCEL_BICGSTAB || method > PAMG_ACCEL_MINIMAL_RESIDUAL) return PAMG_E_ARG;
+    Level &L0 = S->levels[0];
+    const int64_t n = L0.n;
+    if (n < 2) return PAMG_E_UNSUPPORTED;              // the reference special-cases n == 1 (bicgstab) on the host
+    static const int nvec[4] = {5, 3, 1, 1};           // work vectors per method
+    if (maxiter <= 0) {                                // the methods' own defaults
+        const int64_t d = method == PAMG_ACCEL_BICGSTAB ? n + 5 : method == PAMG_ACCEL_STEEPEST_DESCENT ? n : (int64_t)(1.3 * (double)n) + 2;
+        maxiter = (int)std::min<int64_t>(d, INT32_MAX);
+    }
+    hipStream_t s = s_ ? (hipStream_t)s_ : S->own_stream;
+    PAMG_TRY(ensure_amli(S, cycle));
+    if (!s_) PAMG_HIP(hipStreamSynchronize(nullptr));
+    const size_t vb = (size_t)n * tsize(S->dtype);
+    for (int k = 0; k < nvec[method]; ++k)
+        if (!S->kr_v[k]) PAMG_TRY(dalloc(S, &S->kr_v[k], vb));
+    if (!S->kr_red) PAMG_TRY(dalloc(S, (void **)&S->kr_red, sizeof(double) * (KR_PARTIALS + 16)));
+    KrylovRun K{S, L0, S->dtype, n, vb, cycle, cycles_per_level, s, S->kr_red, S->kr_red + KR_PARTIALS, residuals, residuals_cap};
+    int it = 0, inf = 0, st = PAMG_OK;
+    switch (method) {
+        case PAMG_ACCEL_BICGSTAB: st = bicgstab_core(K, x, b, tol, maxiter, it, inf); break;
+        case PAMG_ACCEL_CR: st = cr_core(K, x, b, tol, maxiter, it, inf); break;
+        case PAMG_ACCEL_STEEPEST_DESCENT: st = sd_core(K, x, b, tol, maxiter, it, inf); break;
+        default: st = mr_core(K, x, b, tol, maxiter, it, inf); break;
+    }
+    PAMG_HIP(hipStreamSynchronize(s));
+    PAMG_TRY(st);
+    if (n_res) *n_res = K.nres;
+    if (n_iter) *n_iter = it;
+    if (info) *info = inf;
+    return check_sweeps(S);
 }
 
 int pamg_solver_stats(pamg_solver_t S, int64_t stats[8])

@@ -13,8 +13,10 @@ and error behaviour follow the reference:
   ``residuals[:] = [r0, r1, ...]`` (:546-569), ``callback(x)`` after every cycle (:571-572).
 * ``aspreconditioner(cycle)`` -- SciPy ``LinearOperator`` whose matvec is exactly one cycle
   from a zero initial guess (:390-396).
-* ``accel=`` -- the Krylov method runs on the host exactly as in the reference (:479-535)
-  with the device cycle as preconditioner ``M``.
+* ``accel=`` -- 'cg', 'gmres' / 'gmres_householder', 'fgmres', 'bicgstab', 'cr', 'steepest_descent' and
+  'minimal_residual' run on the device (vectors resident, one host read-back per iteration); any other
+  accelerator, and any call with ``callback=``, runs on the host exactly as in the reference (:479-535) with
+  the device cycle as preconditioner ``M``.
 
 There is no CPU fallback: unsupported configurations raise ``NotImplementedError``.
 """
@@ -676,10 +678,36 @@ class DeviceMultilevelSolver:
                                                C.byref(nit), C.byref(info), stream), _entry)
         return res[: min(nres.value, cap)], nit.value, info.value
 
+    def krylov_device(self, method, xd, bd, tol=1e-5, maxiter=None, cycle="V", cycles_per_level=1, stream=None):
+        """Device-resident BiCGStab / CR / steepest descent / minimal residual (krylov/_bicgstab.py, _cr.py,
+        _steepest_descent.py, _minimal_residual.py, criteria 'rr') on DEVICE vectors; returns (residuals, n_iter, info).
+        minimal_residual reports preconditioned norms ||M r||, as the reference does."""
+        self._need_device("krylov_device")
+        if method not in capi.ACCEL:
+            raise ValueError(f"krylov_device: unknown method {method!r} (one of {sorted(capi.ACCEL)})")
+        n = self.shape[0]
+        if maxiter is None:                                  # the methods' own defaults
+            maxiter = {"bicgstab": n + 5, "steepest_descent": n}.get(method, int(1.3 * n) + 2)
+        elif maxiter < 1:
+            raise ValueError("Number of iterations must be positive")
+        cap = int(maxiter) + 1
+        res = np.zeros(cap, dtype=np.float64)
+        nres, nit, info = C.c_int(0), C.c_int(0), C.c_int(0)
+        capi.check(capi.lib().pamg_solver_krylov(self.handle, capi.ACCEL[method], xd.ptr, bd.ptr, float(tol), int(maxiter),
+                                                 capi.CYCLE[cycle], int(cycles_per_level), capi.ptr(res), cap, C.byref(nres),
+                                                 C.byref(nit), C.byref(info), stream), "pamg_solver_krylov")
+        return res[: min(nres.value, cap)], nit.value, info.value
+
+    # the reference's warnings on info == -1 (krylov/_cr.py:195, _minimal_residual.py:137, _steepest_descent.py:148/164/193)
+    _BREAKDOWN = {"cr": "\nSingular preconditioner detected in CR, ceasing iterations\n",
+                  "minimal_residual": "\nIndefinite matrix detected in minimal residual, stopping.\n"}
+
     def _solve_accel(self, b, x0, tol, maxiter, cycle, accel, callback, residuals, return_info):
-        """multilevel.py:479-535.  accel='cg', 'fgmres' and 'gmres' without a callback run entirely on
-        the device (``pamg_solver_pcg`` / ``pamg_solver_fgmres`` / ``pamg_solver_gmres``); every other accelerator is the host
-        Krylov method of the reference / SciPy around the device preconditioner."""
+        """multilevel.py:479-535.  Without a callback, on a fine level of more than one unknown and in the hierarchy's dtype,
+        these accelerators run entirely on the device: 'cg' (``pamg_solver_pcg``), 'fgmres' (``pamg_solver_fgmres``), 'gmres' and
+        'gmres_householder' (``pamg_solver_gmres``), 'bicgstab', 'cr', 'steepest_descent' and 'minimal_residual'
+        (``pamg_solver_krylov``).  Everything else -- callables, ``callback=``, 'cgne' / 'cgnr' / 'gmres_mgs', SciPy's
+        names -- is the host Krylov method of the reference / SciPy around the device preconditioner."""
         if accel == "cg" and not self.symmetric_smoothing and self.ml is not None:
             from warnings import warn
             warn("Incompatible non-symmetric multigrid preconditioner detected, due to presmoother/postsmoother "
@@ -696,12 +724,26 @@ class DeviceMultilevelSolver:
                 residuals[:] = list(res)
             out = self._xd.download()
             return (out, info) if return_info else out
-        if accel in ("fgmres", "gmres") and callback is None and self.shape[0] > 1 and np.result_type(b.dtype, self.dtype) == self.dtype:
+        device_ok = callback is None and self.shape[0] > 1 and np.result_type(b.dtype, self.dtype) == self.dtype
+        if device_ok and isinstance(accel, str) and (accel in ("fgmres", "gmres", "gmres_householder") or accel in capi.ACCEL):
             x = np.zeros(self.shape[0], dtype=self.dtype) if x0 is None else np.ravel(np.array(x0)).astype(self.dtype)
             self._bd.upload(np.ravel(b).astype(self.dtype, copy=False))
             self._xd.upload(x)
-            run = self.fgmres_device if accel == "fgmres" else self.gmres_device
-            res, nit, info = run(self._xd, self._bd, tol, maxiter, None, cycle)
+            if accel in capi.ACCEL:
+                res, nit, info = self.krylov_device(accel, self._xd, self._bd, tol, maxiter, cycle)
+                if info == -1 and accel in self._BREAKDOWN:
+                    from warnings import warn
+                    warn(self._BREAKDOWN[accel])
+                elif info == -1 and accel == "steepest_descent":
+                    from warnings import warn
+                    # an indefinite preconditioner stops the reference before the iteration's history entry, an indefinite matrix
+                    # after the previous one; a singular preconditioner ((r, M r) == 0 exactly, also -1 through the C ABI) gets
+                    # the second text
+                    warn("\nIndefinite preconditioner detected in steepest descent, stopping.\n" if len(res) == nit else
+                         "\nIndefinite matrix detected in steepest descent, aborting\n")
+            else:
+                run = self.fgmres_device if accel == "fgmres" else self.gmres_device
+                res, nit, info = run(self._xd, self._bd, tol, maxiter, None, cycle)
             if residuals is not None:
                 residuals[:] = list(res)
             out = self._xd.download()
