@@ -367,6 +367,8 @@ int pamg_matrix_info(pamg_matrix_t A, int64_t info[8]);
  * operators the instantiation choice of key 8 bit 5 already sits at the best occupancy, profiles/r06_microbench_sa_ops_lds_pad.json).
  * Key 8, bit 5 (round 6): an operator WITHOUT 8-bit value codes through the kernel instantiation that carries their paths (same arithmetic, another
  * instruction schedule; pamg_matrix_autotune times both).
+ * 37 = fused symmetric sweep (default 1): a symmetric Gauss-Seidel sweep in fast order is ONE persistent launch (forward schedule, completion
+ * barrier, backward schedule) where both schedules take the merged lane form or both the line form (f64); 0 = two directional launches.  Same bits.
  * Returns PAMG_E_STATE while a solver holds the operator (captured graphs point into the plans). */
 int pamg_matrix_tune(pamg_matrix_t A, int key, int value);
 /* n_values = size of the operator's value dictionary when the whole-operator kernels stream 8-bit value codes
@@ -494,6 +496,14 @@ int pamg_matrix_block_jacobi_indexed(pamg_matrix_t A, const void *Dinv, void *x,
  * 100-154, quirks included: 'symmetric' ignores omega, BSR flavour ignores omega). */
 int pamg_matrix_gauss_seidel(pamg_matrix_t A, void *x, const void *b, int sweep, double omega,
                              int iterations, pamg_stream_t s);
+/* The same with the caller's word that x is all zeros on entry (x_is_zero != 0; a cycle's pre-smoothing below the finest level): the first
+ * forward half of a fused symmetric sweep then skips the operands that would multiply zero -- the same bits for finite data. */
+int pamg_matrix_gauss_seidel_x0(pamg_matrix_t A, void *x, const void *b, int sweep, double omega,
+                                int iterations, int x_is_zero, pamg_stream_t s);
+/* The fused symmetric sweep (tune key 37): {fused launches enqueued or captured so far, those with x known to be zero, form of the last one
+ * (1 merged lanes across the chip, 2 lines, 3 merged lanes inside one XCD, 0 none yet), its workgroups, tune key 37, entries of the forward hand-off buffer that are NOT sentinels (0 between
+ * launches; -1: no buffers), counters that are not zero (0 between launches), 0}.  Synchronises the device. */
+int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[8]);
 /* relaxation.polynomial (relaxation.py:585-659); coeffs is a HOST array; x_is_zero != 0
  * asserts x == 0 on entry (the reference tests norm(x) == 0, relaxation.py:649). */
 int pamg_matrix_polynomial(pamg_matrix_t A, void *x, const void *b, void *work,

@@ -235,6 +235,15 @@ struct pamg_matrix_s {
     size_t point_twin_bytes = 0;     // what the twin added to `bytes` when it was made
     bool point_twin_unfit = false;   // no fast-order form fits the flattened rows (or the twin could not be built): the exact block kernels sweep
     pamg::LineSchedule *ls[4] = {nullptr, nullptr, nullptr, nullptr};  // Kaczmarz sweeps over this operator's rows
+    // fused symmetric sweep (forward and backward schedule in ONE launch; pamg_lane.hip / pamg_line.hip): the operator's own pair of
+    // hand-off buffers and counters.  Between launches d_sym_hf[parity] is all sentinels, the other two hold anything, the counters are zero.
+    int sym_fused = 1;               // tune key 37: 1 = a symmetric Gauss-Seidel sweep is one launch where both schedules take the merged or the line form, 0 = two launches
+    void *d_sym_hf[2] = {nullptr, nullptr}, *d_sym_hb = nullptr;
+    unsigned *d_sym_sync = nullptr;  // [0] finished groups of phase 1, [1] workgroups that left, [2] / [3] tickets of phase 1 / 2, [4] home XCD + 1, [5] parity: the forward buffer of the next launch
+    int sym_cap = 0;                 // co-resident workgroups per CU of the fused kernel (queried once per kernel)
+    const void *sym_cap_kernel = nullptr;
+    int sym_form = 0, sym_grid = 0;  // the last fused launch: 1 = merged lanes, 2 = lines, 3 = merged lanes inside one XCD / its workgroups (diagnostics)
+    long long sym_launches = 0, sym_zero_launches = 0;   // fused launches enqueued or captured / those with x known to be zero
     size_t bytes = 0;
 };
 
@@ -259,6 +268,11 @@ void matrix_drop_point_twin(pamg_matrix_s *A);
 void matrix_drop_schedules(pamg_matrix_s *A);
 int gs_sweep(pamg_matrix_s *A, int epi, void *x, const void *b, double omega, int row_start,
              int row_stop, int row_step, hipStream_t s);
+// one launch for a symmetric Gauss-Seidel sweep (f64, fast order, both schedules in the merged lane form or both in the line form).
+// *ran = false: not applicable (the caller runs the two directional sweeps); x_zero: x is known to be all zeros
+int gs_sweep_symmetric(pamg_matrix_s *A, void *x, const void *b, bool x_zero, hipStream_t s, bool *ran);
+int ensure_sym_parts(pamg_matrix_s *A);          // the buffers of the fused sweep, where it applies (allocates: never inside a capture)
+int sym_reset(pamg_matrix_s *A);                 // after a time-out: sentinels and counters back to the state between launches
 int reduce_partials(const double *partial, int n, double *out, hipStream_t s);
 int vec_sumsq(int dtype, int64_t n, const void *x, double *scratch, double *out, hipStream_t s);
 int vec_axpy(int dtype, int64_t n, double a, const void *x, void *y, hipStream_t s);
@@ -316,6 +330,7 @@ void free_line_part(LineSched *t);
 size_t line_part_bytes(const GsSchedule *g);
 int line_launch(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, const void *b, double omega, hipStream_t s);
 int line_info(const GsSchedule *g, int64_t *info);
+int line_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, hipStream_t s);
 // pamg_kz.hip: the lane-parallel fast-order Kaczmarz sweeps (gauss_seidel_ne / gauss_seidel_nr)
 int build_kz_lane_part(pamg_matrix_s *Lm, LineSchedule *g);
 void free_kz_lane_part(KzLaneSched *t);
@@ -351,6 +366,8 @@ void free_lanem_part(struct LaneMSched *t);
 size_t lanem_part_bytes(const GsSchedule *g);
 int lanem_info(const GsSchedule *g, int64_t *info, double *growth);
 int lanem_levels(const GsSchedule *g, int64_t *out, int64_t cap, int64_t *n);
+int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, bool x_zero, hipStream_t s);
+int sym_fill_sentinels(void *p, int64_t n);      // n f64 sentinels on the null stream, synchronised
 int sweep_error(pamg_matrix_s *A, bool *error);      // spin bound hit since the last call? (caller has synchronised; clears the flag)
 inline size_t tsize(int dtype) { return dtype == PAMG_F64 ? 8 : 4; }
 

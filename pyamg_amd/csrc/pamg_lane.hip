@@ -453,15 +453,23 @@ __device__ __forceinline__ void m_slots(const LaneMArgs &a, MCtx<NREG> &C, const
     }
 }
 
+// xz: the old iterate is known to be all zeros -- every OLD operand (neither an early one nor an entry of b) becomes an idle slot, its product + 0
+// as the padding's is: the same bits for finite data without the gathers.  coh: a.xold was written by other workgroups of THIS launch (the second
+// phase of the fused symmetric sweep), so the row's own old value is read past the L1 as the operands are
 template <int NREG>
-__device__ __forceinline__ void m_gather(const LaneMArgs &a, MCtx<NREG> &C, int idle)
+__device__ __forceinline__ void m_gather(const LaneMArgs &a, MCtx<NREG> &C, int idle, const bool xz = false, const bool coh = false)
 {
 #pragma unroll
     for (int k = 1; k < NREG; ++k)
         if (k >= C.K) C.c[k] = LANE_NONE;
+    if (xz) {
+#pragma unroll
+        for (int k = 0; k < NREG; ++k)
+            if (!(C.c[k] & (LANE_EARLY | LANEM_BSRC))) C.c[k] |= LANE_NONE;
+    }
     const int row = C.rid < 0 ? 0 : (C.rid & LANE_MASK);
     C.bv = a.b[row];
-    C.xo = a.xold[row];                                        // used by rows without a diagonal only
+    C.xo = coh ? __hip_atomic_load(a.xold + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.xold[row];      // used by rows without a diagonal only
     // every operand by an L1-bypassing load: early ones poll the hand-off buffer, static ones read the snapshot of x and b (ordinary loads for
     // the static operands were measured 3 - 5 % slower, profiles/r06_microbench_lanem_plain_loads_for_static_operands_not_kept.json)
 #pragma unroll
@@ -477,7 +485,7 @@ __device__ __forceinline__ void m_gather(const LaneMArgs &a, MCtx<NREG> &C, int 
 
 // wait for the group's operands and form x_i of its rows; returns the value a row's head lane publishes
 template <int RPW, int NREG>
-__device__ __forceinline__ double m_finish(const LaneMArgs &a, MCtx<NREG> &C, int idle, long long *t_ready = nullptr, unsigned *n_spins = nullptr)
+__device__ __forceinline__ double m_finish(const LaneMArgs &a, MCtx<NREG> &C, int idle, long long *t_ready = nullptr, unsigned *n_spins = nullptr, const bool xz = false)
 {
     using T = double;
     const int lane = threadIdx.x & 63;
@@ -525,7 +533,8 @@ __device__ __forceinline__ double m_finish(const LaneMArgs &a, MCtx<NREG> &C, in
         // the units beyond the registers: fetched now, one after the other (groups this long are a few per cent)
         for (int k = NREG; k < C.K; ++k) {
             const size_t e = (size_t)(C.unit + k) * 64 + (size_t)lane;
-            const int c = a.cols[e];
+            int c = a.cols[e];
+            if (xz && !(c & (LANE_EARLY | LANEM_BSRC))) c |= LANE_NONE;
             const T v = a.vals[e];
             const int col = c & LANEM_MASK;
             const bool early = (c & LANE_EARLY) && !(c & LANE_NONE);
@@ -552,14 +561,18 @@ __device__ __forceinline__ double m_finish(const LaneMArgs &a, MCtx<NREG> &C, in
     return val;
 }
 
-template <int RPW, int MODE, int NREG>
+// PH = 1: the first phase of the fused symmetric sweep -- the hand-off buffer is also where the second phase reads its OLD operands (every row
+// publishes, a row without a diagonal its old value), x is not written
+template <int RPW, int MODE, int NREG, int PH = 0>
 __device__ __forceinline__ void m_publish(const LaneMArgs &a, const MCtx<NREG> &C, double val)
 {
     if (((threadIdx.x & 63) & (64 / RPW - 1)) == 0 && C.rid >= 0) {
         const int row = C.rid & LANE_MASK;
         if constexpr (MODE == 1) __hip_atomic_store(a.xs + row, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         else __hip_atomic_store(a.xs + row, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!(C.rid & LANE_NODIAG)) a.y[row] = val;
+        if constexpr (PH != 1) {
+            if (!(C.rid & LANE_NODIAG)) a.y[row] = val;
+        }
     }
 }
 
@@ -640,6 +653,171 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
             g2 = (int)__builtin_amdgcn_readfirstlane(tk3);
         }
     }
+}
+
+// =================================================================== the FUSED SYMMETRIC sweep of the merged form: forward + backward in ONE launch
+// Phase 1 walks the forward schedule's groups exactly as gs_lanem_kernel does, a completion barrier follows, phase 2 walks the backward schedule's.
+// What the two directional launches paid around the sweeps is gone: no sentinel fill and no snapshot of x (lanem_prepare_kernel), one kernel
+// drain / ramp-up instead of two, and phase 1 stores every value ONCE.
+//   vectors : phase 1 reads its OLD operands from x, which it never writes, and publishes every row's value in its hand-off buffer H_f (a row
+//             without a diagonal its old value): H_f then IS the iterate after the forward sweep.  Phase 2 reads its OLD operands from H_f, polls
+//             H_b and writes x.  No vector is read and written in the same phase, so no snapshot is needed.
+//   buffers : the operator owns H_f[0], H_f[1] and H_b; a parity word says which H_f this launch publishes in and is flipped by the last workgroup
+//             to leave.  Between launches H_f[parity] is all sentinels, the other two hold anything.  Wipes ride on the sweep: phase 1 wipes H_b
+//             (the previous sweep's backward values, read by nobody in phase 1), phase 2 wipes H_f[parity ^ 1] (the previous launch's forward
+//             values, dead since that launch ended) -- the buffer the NEXT launch publishes in.  The wipe is partitioned by GROUP, not by wave, so
+//             that it holds for the static and the ticket assignment alike: with n = q G + r entries and G groups, group g owns
+//             [g q + min(g, r), + q + (g < r)); the first group of every block of B consecutive groups (B = wipe_blk, chosen so that a block owns
+//             >= 64 entries) wipes its block's entries in one coalesced wave store (tests/test_symsweep_plan.py replays the partition).  Wipes are
+//             stores of the flavour of the publishing store and complete with the wave's vmcnt(0) wait in front of the barrier / at its exit.
+//   barrier : counts FINISHED GROUPS (in the ticket form nobody knows how many workgroups stayed).  Every wave waits for its stores
+//             (s_waitcnt vmcnt(0)) and adds its groups to a word in LDS; behind a workgroup barrier ONE lane adds the workgroup's total to the counter
+//             (agent-scope atomic) and polls it past the L1 with the bounded spin of the hand-offs (same error word, same time-out); the other
+//             waves wait for that lane at a second workgroup barrier.  No phase-2 group starts before the counter is full; phase 1 is the forward
+//             sweep, which completes on its own, and phase 2 is the backward sweep: deadlock-free where the two sweeps are.
+//   counters: the last workgroup to leave (a second counter, one add per workgroup after its waves have met) zeroes barrier, tickets and the home
+//             XCD word and flips the parity: no helper launch, no memset node.
+struct LaneMSymArgs {
+    LaneMArgs ph[2];       // [0] forward: xold = x, xs = H_f[parity] (set by the kernel); [1] backward: xold = H_f[parity] (likewise), y = x, xs = H_b
+    double *hf[2];
+    unsigned *sync;        // [0] finished groups of phase 1, [1] workgroups that left, [2] / [3] tickets of phase 1 / 2, [4] home XCD + 1, [5] parity
+    int wq[2], wr[2], wblk[2];   // wipe parts of phase p (over the buffer it wipes): n = wq * ngroups + wr, groups per wipe block
+    int xzero;             // x is all zeros on entry: phase 1 skips its OLD operands
+};
+
+// group g's duty in the wipe of `w`: nothing unless it is the first group of its block
+template <int MODE>
+__device__ __forceinline__ void m_wipe(double *w, int g, int G, int q, int r, int blk, int lane)
+{
+    if (g & (blk - 1)) return;                                  // blk: a power of two
+    const int g1 = g + blk < G ? g + blk : G;
+    const int lo = g * q + (g < r ? g : r), hi = g1 * q + (g1 < r ? g1 : r);
+    unsigned long long *p = reinterpret_cast<unsigned long long *>(w);
+    for (int i = lo + lane; i < hi; i += 64) {
+        if constexpr (MODE == 1) __hip_atomic_store(p + i, Sentinel<double>::value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else __hip_atomic_store(p + i, Sentinel<double>::value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// one phase of the fused sweep by one wave; returns the groups it finished
+template <int MODE, int RPW, int NREG, int PH>
+__device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, int wq, int wr, int wblk, unsigned *ticket, const bool xz, int lane, int wib, int idle)
+{
+    const int4 *rp = reinterpret_cast<const int4 *>(a.rec);
+    const int gend = a.ngroups;
+    MCtx<NREG> X;
+    unsigned done = 0;
+    if constexpr (MODE != 1) {
+        const int W = (int)gridDim.x * LANE_WPB;
+        int g = __builtin_amdgcn_readfirstlane((int)blockIdx.x * LANE_WPB + wib);
+        if (g >= gend) return 0;
+        int4 q0, q1;
+        m_rec(rp, g, gend, q0, q1);
+        for (; g < gend; g += W) {
+            int4 n0, n1;
+            m_rec(rp, g + W, gend, n0, n1);
+            m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
+            m_gather<NREG>(a, X, idle, xz, PH == 2);
+            const double val = m_finish<RPW, NREG>(a, X, idle, nullptr, nullptr, xz);
+            m_publish<RPW, MODE, NREG, PH>(a, X, val);
+            m_wipe<MODE>(wipe, g, gend, wq, wr, wblk, lane);      // behind the publishing stores: nobody waits for these
+            ++done;
+            q0 = n0; q1 = n1;
+        }
+    } else {
+        unsigned tk = 0;
+        if (lane == 0) tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int g = (int)__builtin_amdgcn_readfirstlane(tk);
+        if (g >= gend) return 0;
+        if (lane == 0) tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int g2 = (int)__builtin_amdgcn_readfirstlane(tk);
+        int4 q0, q1;
+        m_rec(rp, g, gend, q0, q1);
+        while (true) {
+            int4 n0, n1;
+            m_rec(rp, g2, gend, n0, n1);
+            unsigned tk3 = 0;
+            if (g2 < gend && lane == 0) tk3 = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
+            m_gather<NREG>(a, X, idle, xz, PH == 2);
+            const double val = m_finish<RPW, NREG>(a, X, idle, nullptr, nullptr, xz);
+            m_publish<RPW, MODE, NREG, PH>(a, X, val);
+            m_wipe<MODE>(wipe, g, gend, wq, wr, wblk, lane);
+            ++done;
+            if (g2 >= gend) break;
+            g = g2; q0 = n0; q1 = n1;
+            g2 = (int)__builtin_amdgcn_readfirstlane(tk3);
+        }
+    }
+    return done;
+}
+
+// the completion barrier between the phases (see above); `done` = groups this wave finished, `total` = groups of the phase.  Every wave of the
+// workgroup calls it.
+__device__ __forceinline__ void sym_phase_barrier(unsigned *counter, unsigned *err, unsigned *sh_done, unsigned done, unsigned total)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's phase-1 stores (values and wipes) have left
+    if ((threadIdx.x & 63) == 0 && done) atomicAdd(sh_done, done);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned mine = *sh_done;
+        if (mine) __hip_atomic_fetch_add(counter, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned spins = 0;
+        while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < total) {
+            __builtin_amdgcn_s_sleep(2);
+            if ((++spins & 1023u) == 0 && (spins > (1u << 21) || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+                __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                break;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// the last workgroup to leave puts the counters back to zero and flips the parity (every workgroup of the grid passes here once, after its waves
+// have met: nobody polls, draws a ticket or reads the parity any more when the last add arrives)
+__device__ __forceinline__ void sym_leave(unsigned *sync, unsigned parity)
+{
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned left = __hip_atomic_fetch_add(sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (left == gridDim.x - 1) {
+            for (int k = 0; k < 5; ++k) __hip_atomic_store(sync + k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(sync + 5, parity ^ 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+template <int MODE, int RPW, int NREG>
+__global__ __launch_bounds__(BLK) void gs_lanem_sym_kernel(const LaneMSymArgs a)
+{
+    __shared__ unsigned sh_done;
+    __shared__ int sh_home;
+    const int lane = threadIdx.x & 63;
+    const int wib = threadIdx.x >> 6;
+    const int idle = (int)((((unsigned)blockIdx.x * LANE_WPB + (unsigned)wib) * 16u) % (unsigned)a.ph[0].nidle);
+    const unsigned parity = __builtin_amdgcn_readfirstlane(__hip_atomic_load(a.sync + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & 1u;
+    if (threadIdx.x == 0) {
+        sh_done = 0u;
+        sh_home = 1;
+        if constexpr (MODE == 1) {
+            const unsigned me = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) + 1u;
+            unsigned home = 0u;
+            __hip_atomic_compare_exchange_strong(a.sync + 4, &home, me, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            sh_home = (home == 0u || home == me) ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    if (sh_home) {                                               // (uniform per workgroup: the barriers below are met by all of its waves or by none)
+        double *hf = a.hf[parity], *hf_next = a.hf[parity ^ 1u];
+        LaneMArgs p1 = a.ph[0], p2 = a.ph[1];
+        p1.xs = hf; p1.y = nullptr;
+        p2.xold = hf;
+        const unsigned done = m_phase<MODE, RPW, NREG, 1>(p1, p2.xs, a.wq[0], a.wr[0], a.wblk[0], a.sync + 2, a.xzero != 0, lane, wib, idle);
+        sym_phase_barrier(a.sync, p1.err, &sh_done, done, (unsigned)p1.ngroups);
+        (void)m_phase<MODE, RPW, NREG, 2>(p2, hf_next, a.wq[1], a.wr[1], a.wblk[1], a.sync + 3, false, lane, wib, idle);
+    }
+    sym_leave(a.sync, parity);
 }
 
 // ------------------------------------------------------------------ host side
@@ -980,6 +1158,80 @@ int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStr
     }
     t->last_grid = G;
     PAMG_HIP(hipLaunchKernel(k, dim3(G), dim3(BLK), args, 0, s));
+    return PAMG_OK;
+}
+
+int sym_fill_sentinels(void *p, int64_t n)
+{
+    if (n <= 0) return PAMG_OK;
+    const int fgrid = (int)std::min<int64_t>(4096, (n + BLK - 1) / BLK);
+    hipLaunchKernelGGL((lane_fill_sentinel_kernel<double>), dim3(fgrid), dim3(BLK), 0, 0, (double *)p, n);
+    PAMG_HIP(hipGetLastError());
+    PAMG_HIP(hipDeviceSynchronize());
+    return PAMG_OK;
+}
+
+// The fused symmetric sweep (gs_lanem_sym_kernel).  PAMG_E_UNSUPPORTED: the two schedules would not run the same kernel -- the caller sweeps
+// them one after the other.  The grid is the larger of the two directional wishes (lanem_launch) under the fused kernel's own co-residency cap.
+int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, bool x_zero, hipStream_t s)
+{
+    LaneMSched *tf = gf->lanem, *tb = gb->lanem;
+    if (!tf || !tb || !A->d_sym_hf[0] || !A->d_sym_hf[1] || !A->d_sym_hb || !A->d_sym_sync) return PAMG_E_STATE;
+    const int64_t n = A->nrows;
+    auto one_xcd = [&](const GsSchedule *g) { return A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= 8192); };
+    const bool xcd = one_xcd(gf);
+    if (xcd != one_xcd(gb) || tf->rpw != tb->rpw || tf->ngroups < 1 || tb->ngroups < 1) return PAMG_E_UNSUPPORTED;
+    LaneMSymArgs a;
+    GsSchedule *gs2[2] = {gf, gb};
+    for (int p = 0; p < 2; ++p) {
+        LaneMSched *t = gs2[p]->lanem;
+        LaneMArgs &q = a.ph[p];
+        q.cols = t->d_cols; q.vals = t->d_vals; q.rec = t->d_rec;
+        q.use_gate = (A->lane_flags & 1) ? 1 : 0;
+        q.b = (const double *)b;
+        q.err = gf->d_sync + 1; q.ticket = nullptr;
+        q.ngroups = (int)t->ngroups;
+        q.nidle = (int)std::max<int64_t>(1, std::min<int64_t>(n, 1 << 20));
+        q.prof = nullptr;
+        a.wq[p] = (int)(n / t->ngroups); a.wr[p] = (int)(n % t->ngroups);
+        a.wblk[p] = 1;                                          // groups per wipe block: the power of two whose groups own >= 64 entries together
+        while ((int64_t)a.wblk[p] * n < 64 * t->ngroups && a.wblk[p] < (1 << 20)) a.wblk[p] *= 2;
+    }
+    a.ph[0].xold = (const double *)x; a.ph[0].y = nullptr;     a.ph[0].xs = nullptr;                     // (xs / xold of the parity's H_f: set by the kernel)
+    a.ph[1].xold = nullptr;           a.ph[1].y = (double *)x; a.ph[1].xs = (double *)A->d_sym_hb;
+    a.hf[0] = (double *)A->d_sym_hf[0]; a.hf[1] = (double *)A->d_sym_hf[1];
+    a.sync = A->d_sym_sync;
+    a.xzero = x_zero ? 1 : 0;
+    static const int nreg_env = [] { const char *e = getenv("PAMG_LANEM_NREG"); return e ? atoi(e) : 0; }();
+    const bool all_regs = tf->rpw == 1 && (nreg_env ? nreg_env == 8 : A->nrows <= 131072);
+    const void *k = tf->rpw == 2 ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4> : (const void *)gs_lanem_sym_kernel<0, 2, 4>)
+                  : all_regs     ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 8> : (const void *)gs_lanem_sym_kernel<0, 1, 8>)
+                                 : (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 2> : (const void *)gs_lanem_sym_kernel<0, 1, 2>);
+    static thread_local int cus = 0;
+    if (!cus) cus = device_cus_lane();
+    if (!(A->sym_cap > 0 && A->sym_cap_kernel == k)) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess) nb = 2;
+        A->sym_cap = std::max(1, std::min(nb - 1, 8));          // every workgroup must be resident (the query can over-report by one)
+        A->sym_cap_kernel = k;
+    }
+    const int cap = A->sym_cap;
+    int G = 1;
+    for (int p = 0; p < 2; ++p) {                               // the directional rule (lanem_launch), the larger wish of the two
+        const LaneMSched *t = gs2[p]->lanem;
+        const int per_level = (int)((t->ngroups + t->nsuper - 1) / std::max(1, t->nsuper));
+        const int64_t want_waves = std::max<int64_t>(128, ((int64_t)A->lanem_ahead10 * per_level + 9) / 10);
+        int Gp = (int)std::min<int64_t>((want_waves + LANE_WPB - 1) / LANE_WPB, (int64_t)std::min(cap, t->rpw == 2 ? 2 : 3) * cus);
+        if (A->lane_G > 0) Gp = std::min(A->lane_G, cap * cus);
+        Gp = (int)std::max<int64_t>(1, std::min<int64_t>(Gp, (t->ngroups + LANE_WPB - 1) / LANE_WPB));
+        G = std::max(G, Gp);
+    }
+    if (xcd) G = 8 * std::max(1, std::min(G, (cus / 8) * cap));   // 8x the wanted grid; the workgroups off the home XCD leave at once
+    void *args[] = {(void *)&a};
+    PAMG_HIP(hipLaunchKernel(k, dim3(G), dim3(BLK), args, 0, s));
+    A->sym_form = xcd ? 3 : 1; A->sym_grid = G;
+    A->sym_launches++;
+    if (x_zero) A->sym_zero_launches++;
     return PAMG_OK;
 }
 

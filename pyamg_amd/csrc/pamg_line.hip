@@ -136,13 +136,18 @@ __device__ __forceinline__ void line_scan(T &Av, T &Bv, int lane)
     }
 }
 
-template <typename T, int EPI, int K>
-__global__ __launch_bounds__(BLK) void gs_line_kernel(const LineArgs<T> a)
+// the lines of one sweep direction that fall to this wave.  PH = 0: a directional launch.  PH = 1 / 2: the phases of the fused symmetric sweep
+// (gs_line_sym_kernel): the wave that walks line l also wipes the l-th of nlines parts of the buffer `wipe` (n = wq nlines + wr entries, part
+// l = [l wq + min(l, wr), + wq + (l < wr))); phase 1 publishes in its hand-off buffer only (x is not written: the buffer is where phase 2 reads
+// its old operands, a.x of phase 2, past the L1 like everything another workgroup of the launch has written).  Returns the lines walked.
+template <typename T, int EPI, int K, int PH>
+__device__ __forceinline__ unsigned line_walk(const LineArgs<T> &a, T *wipe, int wq, int wr)
 {
     const int lane = threadIdx.x & 63;
     const int wib = threadIdx.x >> 6;
     const int W = (int)gridDim.x * LINE_WPB;
     const int idle = (int)((((unsigned)blockIdx.x * LINE_WPB + (unsigned)wib) * 16u) % (unsigned)a.nidle);
+    unsigned walked = 0;
     for (int line = (int)blockIdx.x * LINE_WPB + wib; line < a.nlines; line += W) {
         const int g0 = a.line_chunk[line], g1 = a.line_chunk[line + 1];
         T carry = T(0);
@@ -156,7 +161,7 @@ __global__ __launch_bounds__(BLK) void gs_line_kernel(const LineArgs<T> a)
             const T bv = a.b[row];
             T xo = T(0);
             if constexpr (EPI == EPI_SOR) xo = a.x[row];
-            else if (S.nod) xo = a.x[row];
+            else if (S.nod) xo = PH == 2 ? __hip_atomic_load(a.x + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.x[row];
             T xv[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) {
@@ -215,7 +220,7 @@ __global__ __launch_bounds__(BLK) void gs_line_kernel(const LineArgs<T> a)
             const T v = Bv + Av * carry;
             if (active) {
                 __hip_atomic_store(a.xs + row, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (!S.nod) a.y[row] = v;
+                if constexpr (PH != 1) { if (!S.nod) a.y[row] = v; }
             }
             carry = line_readlane(v, S.cnt - 1);
         };
@@ -225,6 +230,72 @@ __global__ __launch_bounds__(BLK) void gs_line_kernel(const LineArgs<T> a)
             if (++g >= g1) break;
             chunk(Q, P, g);
             if (++g >= g1) break;
+        }
+        if constexpr (PH != 0) {
+            using B = typename LSentinel<T>::bits_t;
+            const int lo = line * wq + (line < wr ? line : wr), cnt = wq + (line < wr ? 1 : 0);
+            B *p = reinterpret_cast<B *>(wipe) + lo;
+            for (int i = lane; i < cnt; i += 64) __hip_atomic_store(p + i, LSentinel<T>::value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        ++walked;
+    }
+    return walked;
+}
+
+template <typename T, int EPI, int K>
+__global__ __launch_bounds__(BLK) void gs_line_kernel(const LineArgs<T> a)
+{
+    (void)line_walk<T, EPI, K, 0>(a, nullptr, 0, 0);
+}
+
+// The FUSED SYMMETRIC sweep of the line form: the forward schedule's lines, a completion barrier, the backward schedule's, in one launch -- no
+// sentinel fill in front of either direction, and the forward half stores every value once.  Vectors, buffer discipline (two forward buffers
+// alternating by a parity word, one backward buffer, wipes riding on the sweep), barrier and counters are those of gs_lanem_sym_kernel
+// (pamg_lane.hip), the barrier counting finished LINES: phase 1 reads old operands from x and publishes in H_f[parity], phase 2 reads old
+// operands from H_f[parity], polls H_b and writes x.
+template <typename T>
+struct LineSymArgs {
+    LineArgs<T> ph[2];     // [0] forward: x = the live x, xs = H_f[parity] (set by the kernel); [1] backward: x = H_f[parity] (likewise), y = the live x, xs = H_b
+    T *hf[2];
+    unsigned *sync;        // [0] finished lines of phase 1, [1] workgroups that left, [5] parity
+    int wq[2], wr[2];
+};
+
+template <typename T, int K>
+__global__ __launch_bounds__(BLK) void gs_line_sym_kernel(const LineSymArgs<T> a)
+{
+    __shared__ unsigned sh_done;
+    const unsigned parity = __builtin_amdgcn_readfirstlane(__hip_atomic_load(a.sync + 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & 1u;
+    if (threadIdx.x == 0) sh_done = 0u;
+    __syncthreads();
+    LineArgs<T> p1 = a.ph[0], p2 = a.ph[1];
+    p1.xs = a.hf[parity]; p1.y = nullptr;
+    p2.x = a.hf[parity];
+    const unsigned done = line_walk<T, EPI_GS, K, 1>(p1, p2.xs, a.wq[0], a.wr[0]);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's phase-1 stores (hand-off values, wipes) have left
+    if ((threadIdx.x & 63) == 0 && done) atomicAdd(&sh_done, done);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned mine = sh_done;
+        if (mine) __hip_atomic_fetch_add(a.sync, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned spins = 0;
+        while (__hip_atomic_load(a.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)p1.nlines) {
+            __builtin_amdgcn_s_sleep(2);
+            if ((++spins & 1023u) == 0 && (spins > (1u << 21) || __hip_atomic_load(p1.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+                __hip_atomic_store(p1.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                break;
+            }
+        }
+    }
+    __syncthreads();
+    (void)line_walk<T, EPI_GS, K, 2>(p2, a.hf[parity ^ 1u], a.wq[1], a.wr[1]);
+    __syncthreads();
+    if (threadIdx.x == 0) {                                     // the last workgroup to leave zeroes the counters and flips the parity: no memset node
+        const unsigned left = __hip_atomic_fetch_add(a.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (left == gridDim.x - 1) {
+            __hip_atomic_store(a.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.sync + 5, parity ^ 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -470,6 +541,70 @@ static int line_launch_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, cons
     t->last_grid = G;
     void *args[] = {(void *)&a};
     PAMG_HIP(hipLaunchKernel(k, dim3(G), dim3(BLK), args, 0, s));
+    return PAMG_OK;
+}
+
+// The fused symmetric sweep (f64 Gauss-Seidel).  No vector is read and written in the same phase, so it would order a structurally
+// non-symmetric pattern too; those keep the two launches with their snapshots all the same, because no test sweeps one through the line form.  PAMG_E_UNSUPPORTED: not applicable.  Grid: the larger of the two directional wishes under the fused kernel's co-residency cap.
+int line_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, hipStream_t s)
+{
+    LineSched *tf = gf->line, *tb = gb->line;
+    if (!tf || !tb || !A->d_sym_hf[0] || !A->d_sym_hf[1] || !A->d_sym_hb || !A->d_sym_sync) return PAMG_E_STATE;
+    if (A->dtype != PAMG_F64 || !gf->symmetric || !gb->symmetric || tf->K != tb->K || tf->nlines < 1 || tb->nlines < 1) return PAMG_E_UNSUPPORTED;
+    using T = double;
+    const int64_t n = A->nrows;
+    LineSymArgs<T> a;
+    GsSchedule *gs2[2] = {gf, gb};
+    for (int p = 0; p < 2; ++p) {
+        const LineSched *t = gs2[p]->line;
+        LineArgs<T> &q = a.ph[p];
+        q.cols = t->d_cols; q.vals = (const T *)t->d_vals; q.rdiag = (const T *)t->d_rdiag; q.acoef = (const T *)t->d_acoef;
+        q.nodiag = t->d_nodiag; q.row0 = t->d_row0; q.cnt = t->d_cnt; q.gate = t->d_gate; q.line_chunk = t->d_line_chunk;
+        q.x = (const T *)x; q.y = (T *)x; q.xs = nullptr; q.b = (const T *)b;      // (the kernel points phase 1's xs and phase 2's x at H_f[parity])
+        q.err = gf->d_sync + 1;
+        q.nlines = (int)t->nlines; q.step = t->step;
+        q.nidle = (int)std::max<int64_t>(1, std::min<int64_t>(n, 1 << 20));
+        q.use_gate = (A->lane_flags & 8) ? 1 : 0;
+        q.omega = T(1);
+        a.wq[p] = (int)(n / t->nlines); a.wr[p] = (int)(n % t->nlines);
+    }
+    a.ph[1].xs = (T *)A->d_sym_hb;
+    a.hf[0] = (T *)A->d_sym_hf[0]; a.hf[1] = (T *)A->d_sym_hf[1];
+    a.sync = A->d_sym_sync;
+    const void *k = nullptr;
+    switch (tf->K) {
+        case 1: k = (const void *)gs_line_sym_kernel<T, 1>; break;
+        case 2: k = (const void *)gs_line_sym_kernel<T, 2>; break;
+        case 3: k = (const void *)gs_line_sym_kernel<T, 3>; break;
+        case 4: k = (const void *)gs_line_sym_kernel<T, 4>; break;
+        case 5: k = (const void *)gs_line_sym_kernel<T, 5>; break;
+        case 6: k = (const void *)gs_line_sym_kernel<T, 6>; break;
+        case 7: k = (const void *)gs_line_sym_kernel<T, 7>; break;
+        case 8: k = (const void *)gs_line_sym_kernel<T, 8>; break;
+    }
+    if (!k) return PAMG_E_UNSUPPORTED;
+    static thread_local int cus = 0;
+    if (!cus) cus = line_cus();
+    if (A->sym_cap <= 0 || A->sym_cap_kernel != k) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess) nb = 2;
+        A->sym_cap = std::max(1, std::min(nb - 1, 8));          // every workgroup must be resident (the query can over-report by one)
+        A->sym_cap_kernel = k;
+    }
+    const int cap = A->sym_cap;
+    int G = 1;
+    for (int p = 0; p < 2; ++p) {
+        const LineSched *t = gs2[p]->line;
+        const int64_t want_waves = std::max<int64_t>(256, 4 * t->max_level_lines);
+        int Gp = (int)std::min<int64_t>((want_waves + LINE_WPB - 1) / LINE_WPB, (int64_t)cap * cus);
+        if (A->lane_G > 0) Gp = std::min(A->lane_G, cap * cus);
+        Gp = (int)std::max<int64_t>(1, std::min<int64_t>(Gp, (t->nlines + LINE_WPB - 1) / LINE_WPB));
+        G = std::max(G, Gp);
+    }
+    void *args[] = {(void *)&a};
+    PAMG_HIP(hipLaunchKernel(k, dim3(G), dim3(BLK), args, 0, s));
+    A->sym_form = 2; A->sym_grid = G;
+    A->sym_launches++;
     return PAMG_OK;
 }
 

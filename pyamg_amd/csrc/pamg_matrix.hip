@@ -1390,6 +1390,76 @@ int gs_sweep(pamg_matrix_s *A, int epi, void *x, const void *b, double omega, in
     return block_point_sweep(A, g, x, b, row_step < 0 ? -1 : 1, s);      // pamg_block.hip
 }
 
+// ---- the fused symmetric sweep: one launch for forward + backward where both schedules take the same fast form (merged lanes or lines).
+// Everything else keeps the two directional sweeps: SOR (the caller), f32, block operators, unmerged lanes, tiles, the exact schedulers, level
+// launches after a time-out (gs_mode 1), profiling.  0 = not applicable, 1 = merged lanes, 2 = lines.
+static int sym_form_of(pamg_matrix_s *A, GsSchedule **pf, GsSchedule **pb)
+{
+    if (!A->sym_fused || A->R != 1 || A->dtype != PAMG_F64 || A->gs_order != 1 || A->gs_mode != 0 || A->gs_prof || A->nrows < 2) return 0;
+    const int n = (int)A->nrows;
+    GsSchedule *gf = nullptr, *gb = nullptr;
+    if (get_schedule(A, 0, n, 1, &gf) != PAMG_OK || get_schedule(A, n - 1, -1, -1, &gb) != PAMG_OK) return 0;
+    if (ensure_parts(A, gf) != PAMG_OK || ensure_parts(A, gb) != PAMG_OK) return 0;
+    if (gf->nrows != A->nrows || gb->nrows != A->nrows) return 0;
+    *pf = gf; *pb = gb;
+    const bool lf = want_lines(A, gf), lb = want_lines(A, gb);
+    if (lf != lb) return 0;
+    // lines: structurally symmetric patterns only (line_sym_launch says why); the others keep the two launches and their snapshots
+    if (lf) return (gf->line && gb->line && gf->symmetric && gb->symmetric) ? 2 : 0;
+    if (want_lanes(A, gf) && want_lanes(A, gb) && gf->lanem && gb->lanem) return 1;
+    return 0;
+}
+
+int ensure_sym_parts(pamg_matrix_s *A)
+{
+    GsSchedule *gf = nullptr, *gb = nullptr;
+    if (!A || A->d_sym_hf[0] || !sym_form_of(A, &gf, &gb)) return PAMG_OK;
+    const size_t vb = ((size_t)A->nrows + 8) * sizeof(double);
+    void *hf0 = nullptr, *hf1 = nullptr, *hb = nullptr;
+    unsigned *sy = nullptr;
+    int st = (int)hipMalloc(&hf0, vb);
+    if (!st) st = (int)hipMalloc(&hf1, vb);
+    if (!st) st = (int)hipMalloc(&hb, vb);
+    if (!st) st = (int)hipMalloc((void **)&sy, 16 * sizeof(unsigned));
+    if (!st) st = (int)hipMemset(sy, 0, 16 * sizeof(unsigned));
+    if (!st) st = sym_fill_sentinels(hf0, A->nrows + 8);
+    if (!st) st = sym_fill_sentinels(hf1, A->nrows + 8);
+    if (!st) st = sym_fill_sentinels(hb, A->nrows + 8);
+    if (st) { hipFree(hf0); hipFree(hf1); hipFree(hb); hipFree(sy); return st; }
+    A->d_sym_hf[0] = hf0; A->d_sym_hf[1] = hf1; A->d_sym_hb = hb; A->d_sym_sync = sy;
+    { std::lock_guard<std::mutex> lk(g_sched_mu); A->bytes += 3 * vb + 16 * sizeof(unsigned); }
+    return PAMG_OK;
+}
+
+int sym_reset(pamg_matrix_s *A)
+{
+    if (!A || !A->d_sym_hf[0]) return PAMG_OK;
+    PAMG_HIP(hipDeviceSynchronize());
+    PAMG_HIP(hipMemset(A->d_sym_sync, 0, 16 * sizeof(unsigned)));                          // parity 0 again
+    PAMG_TRY(sym_fill_sentinels(A->d_sym_hf[0], A->nrows + 8));
+    return sym_fill_sentinels(A->d_sym_hf[1], A->nrows + 8);
+}
+
+int gs_sweep_symmetric(pamg_matrix_s *A, void *x, const void *b, bool x_zero, hipStream_t s, bool *ran)
+{
+    *ran = false;
+    GsSchedule *gf = nullptr, *gb = nullptr;
+    const int form = sym_form_of(A, &gf, &gb);
+    if (!form) return PAMG_OK;
+    if (!A->d_sym_hf[0]) {
+        // a bare operator's first symmetric sweep (a solver allocates with its schedules): never inside a graph capture
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        PAMG_HIP(hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone) return PAMG_OK;
+        PAMG_TRY(ensure_sym_parts(A));
+        if (!A->d_sym_hf[0]) return PAMG_OK;
+    }
+    const int st = form == 2 ? line_sym_launch(A, gf, gb, x, b, s) : lanem_sym_launch(A, gf, gb, x, b, x_zero, s);
+    if (st == PAMG_E_UNSUPPORTED) return PAMG_OK;
+    if (st == PAMG_OK) *ran = true;
+    return st;
+}
+
 int ensure_schedule(pamg_matrix_s *A, int row_start, int row_stop, int row_step, bool block_gs)
 {
     GsSchedule *g = nullptr;
@@ -1746,6 +1816,7 @@ int sweep_error(pamg_matrix_s *A, bool *error)
             PAMG_HIP(hipMemset(g->d_sync + 1, 0, sizeof(unsigned)));
         }
     }
+    if (*error) PAMG_TRY(sym_reset(A));                        // a fused sweep that gave up leaves its buffers and counters anywhere
     for (int k = 0; k < 4; ++k) if (A->ls[k] && kz_lane_error(A->ls[k])) *error = true;
     if (A->point_twin) {
         bool e2 = false;
@@ -1897,6 +1968,7 @@ int pamg_matrix_destroy(pamg_matrix_t A)
     hipFree(A->d_part[0]); hipFree(A->d_part[1]);
     for (int k = 0; k < 4; ++k) free_schedule(A->gs[k]);
     for (int k = 0; k < 4; ++k) pamg::free_line_schedule(A->ls[k]);
+    hipFree(A->d_sym_hf[0]); hipFree(A->d_sym_hf[1]); hipFree(A->d_sym_hb); hipFree(A->d_sym_sync);
     if (A->point_twin) pamg_matrix_destroy(A->point_twin);
     delete A;
     return PAMG_OK;
@@ -1991,6 +2063,7 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
         case 35: if (value < 0 || value > 2) return PAMG_E_ARG; A->lanem_rpw = value; break;
         case 36: if (value < 0 || value > 98304) return PAMG_E_ARG; A->lds_pad = value & ~15; return PAMG_OK;
         case 34: if (value < 1 || value > 400) return PAMG_E_ARG; A->lanem_ahead10 = value; matrix_drop_point_twin(A); return PAMG_OK;
+        case 37: if (value < 0 || value > 1) return PAMG_E_ARG; A->sym_fused = value; return PAMG_OK;      // read at launch time; refused above while a solver's graphs hold the choice
         case 30:                                               // 2: also where the estimate favours the lane form
             if (value < 0 || value > 2) return PAMG_E_ARG;
             A->line_scan = value;
@@ -2198,6 +2271,27 @@ int pamg_matrix_lanem_info(pamg_matrix_t A, int which, int64_t info[12], double 
 {
     if (!A || !info || which < 0 || which > 3) return PAMG_E_ARG;
     return pamg::lanem_info(A->gs[which], info, growth);
+}
+
+int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[8])
+{
+    if (!A || !info) return PAMG_E_ARG;
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    info[0] = A->sym_launches; info[1] = A->sym_zero_launches; info[2] = A->sym_form; info[3] = A->sym_grid; info[4] = A->sym_fused;
+    info[5] = -1; info[6] = -1;
+    if (!A->d_sym_hf[0]) return PAMG_OK;
+    PAMG_HIP(hipDeviceSynchronize());
+    // the invariant between launches: every entry of the forward hand-off buffer the NEXT launch publishes in a sentinel, the counters zero
+    unsigned w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    PAMG_HIP(hipMemcpy(w, A->d_sym_sync, sizeof(w), hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> h((size_t)A->nrows);
+    if (A->nrows) PAMG_HIP(hipMemcpy(h.data(), A->d_sym_hf[w[5] & 1u], (size_t)A->nrows * 8, hipMemcpyDeviceToHost));
+    int64_t bad = 0;
+    for (unsigned long long v : h) bad += (v != 0x7FF8DEADBEEF5A5Aull);
+    info[5] = bad;
+    info[6] = 0;
+    for (int k = 0; k < 5; ++k) info[6] += w[k] != 0u;
+    return PAMG_OK;
 }
 
 int pamg_matrix_lanem_levels(pamg_matrix_t A, int which, int64_t *out, int64_t capacity, int64_t *count)

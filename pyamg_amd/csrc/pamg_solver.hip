@@ -95,7 +95,7 @@ int block_jacobi_pp(pamg_matrix_s *A, void **px, void **palt, const void *b, con
 // relaxation.gauss_seidel / relaxation.sor as the reference runs them (relaxation.py:265-346,
 // :100-154).  Quirks mirrored on purpose: sweep='symmetric' drops omega (:326-330), the BSR
 // flavour ignores omega (:343-346).
-int gs_apply(pamg_matrix_s *A, void *x, const void *b, int sweep, double omega, int its, hipStream_t s)
+int gs_apply(pamg_matrix_s *A, void *x, const void *b, int sweep, double omega, int its, hipStream_t s, bool x_zero = false)
 {
     if (!square_ok(A)) return PAMG_E_ARG;
     if (A->nrows == 0) return PAMG_OK;
@@ -109,6 +109,10 @@ int gs_apply(pamg_matrix_s *A, void *x, const void *b, int sweep, double omega, 
     };
     if (sweep == PAMG_SYMMETRIC) {
         for (int it = 0; it < its; ++it) {
+            // one launch where both directions take the same fast form (x_zero holds for the first iteration only)
+            bool ran = false;
+            PAMG_TRY(gs_sweep_symmetric(A, x, b, x_zero && it == 0, s, &ran));
+            if (ran) continue;
             PAMG_TRY(one(PAMG_FORWARD, 1.0));
             PAMG_TRY(one(PAMG_BACKWARD, 1.0));
         }
@@ -204,8 +208,8 @@ int apply_smoother(pamg_solver_s *S, Level &L, const Smoother &sm, bool x_zero, 
     switch (sm.kind) {
         case PAMG_SMOOTH_NONE: return PAMG_OK;
         case PAMG_SMOOTH_JACOBI: return jacobi_pp(L.A, &L.x, &L.xalt, L.b, sm.omega, sm.iterations, s);
-        case PAMG_SMOOTH_GS: return gs_apply(L.A, L.x, L.b, sm.sweep, 1.0, sm.iterations, s);
-        case PAMG_SMOOTH_SOR: return gs_apply(L.A, L.x, L.b, sm.sweep, sm.omega, sm.iterations, s);
+        case PAMG_SMOOTH_GS: return gs_apply(L.A, L.x, L.b, sm.sweep, 1.0, sm.iterations, s, x_zero);
+        case PAMG_SMOOTH_SOR: return gs_apply(L.A, L.x, L.b, sm.sweep, sm.omega, sm.iterations, s, x_zero);
         case PAMG_SMOOTH_POLY:
             return poly_apply(L.A, L.x, L.b, L.work, sm.coeffs.data(), (int)sm.coeffs.size(),
                               sm.iterations, x_zero ? 1 : 0, s);
@@ -336,6 +340,7 @@ int fall_back_to_level_launches(pamg_solver_s *S)
         if (!L.A) continue;
         L.A->gs_mode = 1;
         L.A->tile_default = false;
+        PAMG_TRY(sym_reset(L.A));                             // (the fused symmetric sweep declines from here on: gs_mode 1)
         for (Smoother *sm : {&L.pre, &L.post}) {
             // kz_lane_launch is gated on gs_mode == 0 of the operator the sweep runs on (pamg_matrix.hip: kaczmarz_sweep)
             if (sm->At) sm->At->gs_mode = 1;
@@ -506,6 +511,8 @@ int prebuild_schedules(Level &L, const Smoother &sm)
         PAMG_TRY(sweep_bounds(L.A, PAMG_BACKWARD, r0, r1, rs));
         PAMG_TRY(ensure_schedule(L.A, r0, r1, rs, sm.kind == PAMG_SMOOTH_BLOCK_GS));
     }
+    // the fused symmetric sweep's hand-off buffers (allocated here: the first cycle may be a graph capture)
+    if (sm.sweep == PAMG_SYMMETRIC && sm.kind != PAMG_SMOOTH_BLOCK_GS) PAMG_TRY(ensure_sym_parts(L.A));
     return PAMG_OK;
 }
 
@@ -1236,6 +1243,14 @@ int pamg_matrix_gauss_seidel(pamg_matrix_t A, void *x, const void *b, int sweep,
     if (!A || !x || !b || iterations < 0) return PAMG_E_ARG;
     if (sweep < PAMG_FORWARD || sweep > PAMG_SYMMETRIC) return PAMG_E_ARG;
     return gs_apply(A, x, b, sweep, omega, iterations, (hipStream_t)s);
+}
+
+int pamg_matrix_gauss_seidel_x0(pamg_matrix_t A, void *x, const void *b, int sweep, double omega,
+                                int iterations, int x_is_zero, pamg_stream_t s)
+{
+    if (!A || !x || !b || iterations < 0) return PAMG_E_ARG;
+    if (sweep < PAMG_FORWARD || sweep > PAMG_SYMMETRIC) return PAMG_E_ARG;
+    return gs_apply(A, x, b, sweep, omega, iterations, (hipStream_t)s, x_is_zero != 0);
 }
 
 int pamg_matrix_polynomial(pamg_matrix_t A, void *x, const void *b, void *work, const double *coeffs,

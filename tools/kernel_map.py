@@ -55,7 +55,26 @@ def kernel_map(dml, smoother_kind):
             n, nnz, vb = inf["rows"], inf["nnz"], A.dtype.itemsize
             if smoother_kind == "gauss_seidel":
                 alg = (vb + 4) * nnz + 4 * (n + 1) + 3 * vb * n
-                for which, dirn in ((0, "forward"), (1, "backward")):
+                sym = A.sym_info()
+                directions = ((0, "forward"), (1, "backward"))
+                if sym["launches"] and sym["form"] != "none":
+                    # the fused symmetric sweep: ONE launch walks both schedules (bytes: the two directions' together)
+                    directions = ()
+                    lm, ln = [A.lanem_info(w) for w in (0, 1)], [A.line_info(w) for w in (0, 1)]
+                    if sym["form"] == "line":
+                        out.append({"family": "gs_line", "grid": int(sym["launch_grid"]), "level": i, "op": "A",
+                                    "what": f"symmetric Gauss-Seidel sweep, one launch (fast order, line scan: {ln[0]['lines']} lines, {ln[0]['line_levels']} + {ln[1]['line_levels']} line levels)",
+                                    "rows": int(n), "nnz": int(nnz), "bytes_alg": int(2 * alg),
+                                    "bytes_streamed": int(sum(l_["chunks"] * 64 * (l_["slots_per_row"] * (vb + 4) + 2 * vb + 1) + n * 4 * vb for l_ in ln)),
+                                    "format": f"chunks of 64 rows x {ln[0]['slots_per_row']} slots", "dependency_levels": int(ln[0]["line_levels"] + ln[1]["line_levels"])})
+                    else:
+                        out.append({"family": "gs_lanem", "grid": int(sym["launch_grid"]), "level": i, "op": "A",
+                                    "what": f"symmetric Gauss-Seidel sweep, one launch (fast order, merged: {lm[0]['super_levels']} + {lm[1]['super_levels']} super-levels of <= {lm[0]['s_max']} dependency levels)",
+                                    "rows": int(n), "nnz": int(nnz), "bytes_alg": int(2 * alg),
+                                    "bytes_streamed": int(sum(l_["units"] * 64 * (vb + 4) + n * (32 + 4 * vb) for l_ in lm)),
+                                    "format": f"one row per wave, {lm[0]['units'] / max(1, lm[0]['rows']):.2f} x 64 operand slots per row, padded",
+                                    "dependency_levels": int(lm[0]["super_levels"] + lm[1]["super_levels"])})
+                for which, dirn in directions:
                     lane, tile, line, lanem = A.lane_info(which), A.tile_info(which), A.line_info(which), A.lanem_info(which)
                     if lanem["rows"] and lanem["launch_grid"]:
                         out.append({"family": "gs_lanem", "grid": int(lanem["launch_grid"]), "level": i, "op": "A",

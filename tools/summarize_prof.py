@@ -41,6 +41,12 @@ def short(name):
     m = re.search(r"gs_lane_kernel<(\w+), *(\d+), *(\d+), *(\d+), *(\w+)>", name)
     if m:
         return f"gs_lane<{m.group(1)},{EPI[int(m.group(2))]},L{m.group(3)},K{m.group(4)},{'oneXCD' if m.group(5) in ('true', '1') else 'chip'}>"
+    m = re.search(r"gs_lanem_sym_kernel<(\w+), *(\d+), *(\d+)>", name)      # the fused symmetric sweeps: forward + backward in one launch
+    if m:
+        return f"gs_lanem_sym<double,GS,{'oneXCD' if m.group(1) in ('true', '1') else 'chip'},rpw{m.group(2)},regs{m.group(3)}>"
+    m = re.search(r"gs_line_sym_kernel<(\w+), *(\d+)>", name)
+    if m:
+        return f"gs_line_sym<{m.group(1)},GS,K{m.group(2)}>"
     m = re.search(r"gs_lanem\w*_kernel<(\w+)(?:, *(\d+))?(?:, *(\d+))?>", name)
     if m:
         return (f"gs_lanem<double,GS,{'oneXCD' if m.group(1) in ('true', '1') else 'chip'}" + (f",rpw{m.group(2)}" if m.group(2) else "")
