@@ -362,7 +362,9 @@ int pamg_matrix_info(pamg_matrix_t A, int64_t info[8]);
  * hand-off per super-level; same iterates in exact arithmetic, another association in floating point; groups are closed early where a merged row would
  * exceed 512 operands (256 with two rows per wave) or its growth factor 1e3 (csrc/pamg_lanem_plan.h; pamg_matrix_lanem_info); 34 = its persistent waves
  * as tenths of the rows of an average super-level (default 40); 35 = its rows per wave: 1 (64 lanes per row), 2 (32 lanes per row, rows of a
- * super-level paired by length), 0 (default) = 2 on levels above 131 072 rows.
+ * super-level paired by length), 0 (default) = 2 on levels above 131 072 rows; 38 = its CLUSTER layout: 4 / 8 = up to that many rows of a
+ * super-level, consecutive in row-index order, share a wave, which loads the union of their operands once and forms the row sums from LDS (static
+ * chip-wide form only); 1 = off; 0 (default) = automatic: 8 on levels above 131 072 rows, where key 33's automatic choice is then 4.
  * 36 = unused dynamic LDS (bytes) added to the launches of the staged whole-operator kernel: caps its workgroups per CU (a measurement knob: on the SA-level
  * operators the instantiation choice of key 8 bit 5 already sits at the best occupancy, profiles/r06_microbench_sa_ops_lds_pad.json).
  * Key 8, bit 5 (round 6): an operator WITHOUT 8-bit value codes through the kernel instantiation that carries their paths (same arithmetic, another
@@ -410,8 +412,13 @@ int pamg_matrix_lane_info(pamg_matrix_t A, int which, int64_t info[8]);
  * of x, operands read from b, longest merged row, levels merged at most, groups closed early by row length, closed early by the growth bound,
  * workgroups of the last launch}; *growth (may be NULL) = the largest accepted growth factor sum_r |T_ir| |a_ii|.  All zero when the schedule
  * runs unmerged.  The merged sweep computes the reference's Gauss-Seidel iterates (amg_core::gauss_seidel, relaxation.h:48-76) in another
- * association: equal in exact arithmetic, to rounding in floating point. */
-int pamg_matrix_lanem_info(pamg_matrix_t A, int which, int64_t info[12], double *growth);
+ * association: equal in exact arithmetic, to rounding in floating point.
+ * info[12..19] (round 8): rows per wave of the CLUSTER layout (tune key 38; 0 = the row / pair layout), groups (one wave's work item: a row, a pair
+ * or a cluster), padded slots (64 x info[3]; over info[4] + info[5] + info[6] it is the layout's padding factor), 64-code units of unique operands,
+ * unique operands polled / read from the snapshot / read from b and distinct 64-byte lines of the unique polled operands, each counted per group and
+ * summed (what a wave really loads where the rows of a group share operands; the row / pair layouts share nothing: their counts repeat
+ * info[4..6] and no lines are counted). */
+int pamg_matrix_lanem_info(pamg_matrix_t A, int which, int64_t info[20], double *growth);
 /* Fast order (tune key 24 = 1) of the BSR POINT sweep (amg_core::bsr_gauss_seidel, relaxation.h:185-266: what relaxation.gauss_seidel runs on a
  * block operator): the same rows in the same order are the scalar Gauss-Seidel sweep of the flattened operator, so the block operator builds a
  * scalar CSR twin of itself with its schedules and sweeps it in the lane-parallel / merged / line-scan form (same iterates to rounding, like every

@@ -367,6 +367,13 @@ struct LaneMSched {
     double *d_vals = nullptr;
     LaneMRec *d_rec = nullptr;
     long long *d_prof = nullptr;
+    // cluster layout (cluster > 0: d_cols = unique operands, d_vals = slot values, d_rec stays empty)
+    int cluster = 0;
+    int4 *d_crec = nullptr;           // [ngroups] {gate, first unique unit, first slot unit, KU | KS << 8 | rows << 16}
+    unsigned short *d_sidx = nullptr; // [n_units * 64] slot codes
+    int *d_crid = nullptr;            // [ngroups * cluster] row | NODIAG, -1 = none
+    double *d_crd = nullptr;          // [ngroups * cluster] 1 / a_ii
+    int64_t n_uunits = 0, n_uearly = 0, n_uold = 0, n_ub = 0, n_early_lines = 0;
     std::vector<int64_t> super_grp;   // [nsuper + 1] first row (group) of every super-level
     int last_grid = 0;
     int cap = 0;
@@ -386,6 +393,10 @@ struct LaneMArgs {
     unsigned *ticket;
     int ngroups, nidle, use_gate;
     long long *prof;       // nullptr or [ngroups][4] time stamps (tune key 11; the unpipelined kernel, static form)
+    const unsigned short *sidx;   // cluster layout only: slot codes, rows of the groups, 1 / a_ii, rows per group at most (rec: one int4 per group)
+    const int *crid;
+    const double *crd;
+    int crows;
 };
 
 // x -> snapshot, sentinels -> hand-off buffer: the two passes every merged sweep starts with, in one launch
@@ -410,7 +421,9 @@ __global__ __launch_bounds__(BLK) void lanem_prepare_kernel(const double *__rest
 // waits for the prefetches, the first poll round is stale); the same with a PUBLISHER wave per workgroup taking the stores out of the compute waves'
 // in-order memory queue through an LDS mailbox (2.2 - 2.5 ms); ordinary loads for the static operands (+ 3 - 5 %); the next row's slots requested behind
 // the current row's operands (1.86 - 1.99 ms).  An ablation of the first kernel (wrong results by construction): 1.21 ms without waiting for early
-// operands, 0.94 without the publishing store as well, 0.73 for slots + early operands alone.
+// operands, 0.94 without the publishing store as well, 0.73 for slots + early operands alone.  What that ablation priced -- the loads past the L1 and the
+// publishing stores per row -- is what the CLUSTER layout (round 8, c_group below; RPW = 0 in the kernels' template arguments) shares between
+// neighbouring rows.
 // RPW rows of one super-level per wave (64 / RPW lanes each), NREG units of 64 slots in registers (the rest of a long group is fetched in the tail)
 template <int NREG>
 struct MCtx {
@@ -474,10 +487,7 @@ __device__ __forceinline__ void m_gather(const LaneMArgs &a, MCtx<NREG> &C, int 
     // the static operands were measured 3 - 5 % slower, profiles/r06_microbench_lanem_plain_loads_for_static_operands_not_kept.json)
 #pragma unroll
     for (int k = 0; k < NREG; ++k) {
-        int col = C.c[k] & LANEM_MASK;
-#ifdef PAMG_LANEM_FAKE_LOCALITY      /* experiment only (wrong results): every static operand next to the row -- what perfect locality of the gathers would buy */
-        if (!(C.c[k] & LANE_EARLY)) col = (row & ~63) + (int)(threadIdx.x & 63);
-#endif
+        const int col = C.c[k] & LANEM_MASK;
         const double *p = (C.c[k] & LANE_NONE) ? a.xold + idle : ((C.c[k] & LANE_EARLY) ? a.xs + col : ((C.c[k] & LANEM_BSRC) ? a.b + col : a.xold + col));
         C.xv[k] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -576,6 +586,133 @@ __device__ __forceinline__ void m_publish(const LaneMArgs &a, const MCtx<NREG> &
     }
 }
 
+// ---- the CLUSTER layout (pamg_lanem_plan.h): one wave takes up to R rows of one super-level that are consecutive in row-index order, loads the
+// UNION of their operands ONCE -- one lane per unique operand, the same L1-bypassing loads, sentinel polling, gate wait, bounded spin and error
+// word as m_gather / m_finish -- puts the values in its own 4 KB of LDS (wave-synchronous: the waves of a workgroup never meet), forms the products
+// of its slots from there, sums them per row (a lane serves one row, a row owns consecutive lanes: segmented inclusive scan, the row's LAST lane
+// holds the sum) and publishes every row of the group in one store instruction.  Static chip-wide assignment only.
+constexpr int LANEC_K = 8;                    // units of unique operands / of slots per group at most (LANEC_UMAX = 64 * this)
+
+__device__ __forceinline__ int4 c_rec(const int4 *rp, int g, int gend) { return rp[(size_t)(g < gend ? g : gend - 1)]; }
+
+// one group.  PH as in m_publish; xz / coh as in m_gather
+template <int PH>
+__device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const int4 &q, int g, int lane, int idle, const bool xz, const bool coh)
+{
+    using T = double;
+    const int gate = a.use_gate ? __builtin_amdgcn_readfirstlane(q.x) : -1;
+    const int uunit = __builtin_amdgcn_readfirstlane(q.y), sunit = __builtin_amdgcn_readfirstlane(q.z), kk = __builtin_amdgcn_readfirstlane(q.w);
+    const int KU = kk & 15, KS = (kk >> 8) & 15;
+    int c[LANEC_K];
+    unsigned si[LANEC_K];
+    T sv[LANEC_K], xv[LANEC_K];
+    const size_t u0 = (size_t)uunit * 64 + (size_t)lane, s0 = (size_t)sunit * 64 + (size_t)lane;
+#pragma unroll
+    for (int k = 0; k < LANEC_K; ++k) {
+        c[k] = LANE_NONE;
+        if (k < KU) c[k] = a.cols[u0 + (size_t)64 * k];
+    }
+#pragma unroll
+    for (int k = 0; k < LANEC_K; ++k) {
+        si[k] = LANEC_PAD | LANEC_UNUSED; sv[k] = T(0);
+        if (k < KS) { si[k] = a.sidx[s0 + (size_t)64 * k]; sv[k] = a.vals[s0 + (size_t)64 * k]; }
+    }
+    if (xz) {
+#pragma unroll
+        for (int k = 0; k < LANEC_K; ++k)
+            if (!(c[k] & (LANE_EARLY | LANEM_BSRC))) c[k] |= LANE_NONE;
+    }
+    // the unique operands: early ones poll the hand-off buffer, static ones read the snapshot of x and b
+#pragma unroll
+    for (int k = 0; k < LANEC_K; ++k) {
+        xv[k] = T(0);
+        if (k < KU) {
+            const int col = c[k] & LANEM_MASK;
+            const T *p = (c[k] & LANE_NONE) ? a.xold + idle : ((c[k] & LANE_EARLY) ? a.xs + col : ((c[k] & LANEM_BSRC) ? a.b + col : a.xold + col));
+            xv[k] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    // the lane's row (every slot of a lane carries it)
+    const bool unused = (si[0] & LANEC_UNUSED) != 0;
+    const int tag = (int)((si[0] >> LANEC_ROWSHIFT) & 7u);
+    const size_t ri = (size_t)g * (size_t)a.crows + (size_t)(tag < a.crows ? tag : 0);
+    const int rid = unused ? -1 : a.crid[ri];
+    const T rd = a.crd[ri];
+    const int row = rid < 0 ? 0 : (rid & LANE_MASK);
+    const T bv = a.b[row];
+    const T xo = coh ? __hip_atomic_load(a.xold + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.xold[row];      // used by rows without a diagonal only
+    unsigned pend = 0;
+#pragma unroll
+    for (int k = 0; k < LANEC_K; ++k)
+        if ((c[k] & LANE_EARLY) && !(c[k] & LANE_NONE) && Sentinel<T>::bits(xv[k]) == Sentinel<T>::value) pend |= 1u << k;
+    unsigned spins = 0;
+    if (gate >= 0 && __builtin_amdgcn_ballot_w64(pend != 0)) {
+        const T *gp = a.xs + gate;
+        while (true) {
+            const T gv = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (Sentinel<T>::bits(gv) != Sentinel<T>::value) break;
+            __builtin_amdgcn_s_sleep(2);
+            if ((++spins & 1023u) == 0 && (spins > (1u << 21) || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) break;
+        }
+    }
+    while (pend) {
+        if (spins) __builtin_amdgcn_s_sleep(1);
+        T t[LANEC_K];
+#pragma unroll
+        for (int k = 0; k < LANEC_K; ++k) {
+            t[k] = T(0);
+            if (k < KU) t[k] = __hip_atomic_load(((pend >> k) & 1u) ? a.xs + (c[k] & LANEM_MASK) : a.xs + idle, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int k = 0; k < LANEC_K; ++k)
+            if ((pend >> k) & 1u) {
+                xv[k] = t[k];
+                if (Sentinel<T>::bits(t[k]) != Sentinel<T>::value) pend &= ~(1u << k);
+            }
+        if ((++spins & 1023u) == 0) {
+            if (spins > (1u << 21) || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                break;
+            }
+        }
+    }
+    // values -> LDS (an idle operand is a zero: padding, and every OLD operand where x is known to be zero), slots <- LDS
+#pragma unroll
+    for (int k = 0; k < LANEC_K; ++k)
+        if (k < KU) lds[k * 64 + lane] = (c[k] & LANE_NONE) ? T(0) : xv[k];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    T s = T(0);
+#pragma unroll
+    for (int k = 0; k < LANEC_K; ++k) {
+        const T pr = sv[k] * lds[si[k] & LANEC_IDX];
+        s = s + ((si[k] & LANEC_PAD) ? T(0) : pr);
+    }
+    // segmented inclusive scan over the lanes of a row
+    const unsigned key = si[0] & ((7u << LANEC_ROWSHIFT) | LANEC_UNUSED);
+    const unsigned left = (unsigned)__shfl_up((int)key, 1);
+    const unsigned long long heads = __builtin_amdgcn_ballot_w64(lane == 0 || left != key);
+    const int seglo = 63 - __builtin_clzll(heads & (~0ull >> (63 - lane)));
+#pragma unroll
+    for (int d = 1; d < 64; d *= 2) {
+        const T o = __shfl_up(s, d);
+        s = s + ((lane - d >= seglo) ? o : T(0));
+    }
+    const bool tail = ((((heads >> 1) | (1ull << 63)) >> lane) & 1ull) != 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // the next group's values overwrite what was read here
+    __builtin_amdgcn_wave_barrier();
+    const bool upd = rid >= 0 && !(rid & LANE_NODIAG);
+    T val = (bv - s) * rd;
+    if (!upd) val = xo;
+    if (tail && rid >= 0) {
+        __hip_atomic_store(a.xs + row, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (PH != 1) {
+            if (upd) a.y[row] = val;
+        }
+    }
+}
+
 // NREG = units of a group held in registers: 2 (one row per wave) / 4 (two rows per wave) on the large levels, where eight waves per SIMD matter;
 // 8 on the small levels, whose sweeps are bound by their hand-offs -- there the sequential tail of a long row sits on the critical path (level 2 of the
 // 256^3 hierarchy at s = 6: 56 % of the rows hold three and more units)
@@ -587,6 +724,19 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
     const int idle = (int)((((unsigned)blockIdx.x * LANE_WPB + (unsigned)wib) * 16u) % (unsigned)a.nidle);
     const int4 *rp = reinterpret_cast<const int4 *>(a.rec);
     const int gend = a.ngroups;
+    __shared__ double c_lds[RPW == 0 ? LANE_WPB * LANEC_UMAX : 1];
+    if constexpr (RPW == 0) {                                    // the cluster layout (static assignment)
+        static_assert(RPW != 0 || MODE != 1, "the cluster layout has no ticket form");
+        const int W = (int)gridDim.x * LANE_WPB;
+        int g = __builtin_amdgcn_readfirstlane((int)blockIdx.x * LANE_WPB + wib);
+        if (g >= gend) return;
+        int4 q = c_rec(rp, g, gend);
+        for (; g < gend; g += W) {
+            const int4 nq = c_rec(rp, g + W, gend);
+            c_group<0>(a, c_lds + wib * LANEC_UMAX, q, g, lane, idle, false, false);
+            q = nq;
+        }
+    } else {
     MCtx<NREG> X;
     if constexpr (MODE != 1) {
         const int W = (int)gridDim.x * LANE_WPB;
@@ -653,6 +803,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
             g2 = (int)__builtin_amdgcn_readfirstlane(tk3);
         }
     }
+    }
 }
 
 // =================================================================== the FUSED SYMMETRIC sweep of the merged form: forward + backward in ONE launch
@@ -701,12 +852,26 @@ __device__ __forceinline__ void m_wipe(double *w, int g, int G, int q, int r, in
 
 // one phase of the fused sweep by one wave; returns the groups it finished
 template <int MODE, int RPW, int NREG, int PH>
-__device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, int wq, int wr, int wblk, unsigned *ticket, const bool xz, int lane, int wib, int idle)
+__device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, int wq, int wr, int wblk, unsigned *ticket, const bool xz, int lane, int wib, int idle, double *c_lds)
 {
     const int4 *rp = reinterpret_cast<const int4 *>(a.rec);
     const int gend = a.ngroups;
-    MCtx<NREG> X;
     unsigned done = 0;
+    if constexpr (RPW == 0) {                                    // the cluster layout (static assignment)
+        static_assert(RPW != 0 || MODE != 1, "the cluster layout has no ticket form");
+        const int W = (int)gridDim.x * LANE_WPB;
+        int g = __builtin_amdgcn_readfirstlane((int)blockIdx.x * LANE_WPB + wib);
+        if (g >= gend) return 0;
+        int4 q = c_rec(rp, g, gend);
+        for (; g < gend; g += W) {
+            const int4 nq = c_rec(rp, g + W, gend);
+            c_group<PH>(a, c_lds + wib * LANEC_UMAX, q, g, lane, idle, xz, PH == 2);
+            m_wipe<MODE>(wipe, g, gend, wq, wr, wblk, lane);
+            ++done;
+            q = nq;
+        }
+    } else {
+    MCtx<NREG> X;
     if constexpr (MODE != 1) {
         const int W = (int)gridDim.x * LANE_WPB;
         int g = __builtin_amdgcn_readfirstlane((int)blockIdx.x * LANE_WPB + wib);
@@ -748,6 +913,7 @@ __device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, in
             g = g2; q0 = n0; q1 = n1;
             g2 = (int)__builtin_amdgcn_readfirstlane(tk3);
         }
+    }
     }
     return done;
 }
@@ -793,6 +959,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_sym_kernel(const LaneMSymArgs a)
 {
     __shared__ unsigned sh_done;
     __shared__ int sh_home;
+    __shared__ double c_lds[RPW == 0 ? LANE_WPB * LANEC_UMAX : 1];
     const int lane = threadIdx.x & 63;
     const int wib = threadIdx.x >> 6;
     const int idle = (int)((((unsigned)blockIdx.x * LANE_WPB + (unsigned)wib) * 16u) % (unsigned)a.ph[0].nidle);
@@ -813,9 +980,9 @@ __global__ __launch_bounds__(BLK) void gs_lanem_sym_kernel(const LaneMSymArgs a)
         LaneMArgs p1 = a.ph[0], p2 = a.ph[1];
         p1.xs = hf; p1.y = nullptr;
         p2.xold = hf;
-        const unsigned done = m_phase<MODE, RPW, NREG, 1>(p1, p2.xs, a.wq[0], a.wr[0], a.wblk[0], a.sync + 2, a.xzero != 0, lane, wib, idle);
+        const unsigned done = m_phase<MODE, RPW, NREG, 1>(p1, p2.xs, a.wq[0], a.wr[0], a.wblk[0], a.sync + 2, a.xzero != 0, lane, wib, idle, c_lds);
         sym_phase_barrier(a.sync, p1.err, &sh_done, done, (unsigned)p1.ngroups);
-        (void)m_phase<MODE, RPW, NREG, 2>(p2, hf_next, a.wq[1], a.wr[1], a.wblk[1], a.sync + 3, false, lane, wib, idle);
+        (void)m_phase<MODE, RPW, NREG, 2>(p2, hf_next, a.wq[1], a.wr[1], a.wblk[1], a.sync + 3, false, lane, wib, idle, c_lds);
     }
     sym_leave(a.sync, parity);
 }
@@ -1025,10 +1192,24 @@ void free_lanem_part(LaneMSched *t)
 {
     if (!t) return;
     hipFree(t->d_cols); hipFree(t->d_vals); hipFree(t->d_rec); hipFree(t->d_prof);
+    hipFree(t->d_crec); hipFree(t->d_sidx); hipFree(t->d_crid); hipFree(t->d_crd);
     delete t;
 }
 
 size_t lanem_part_bytes(const GsSchedule *g) { return (g && g->lanem) ? g->lanem->bytes : 0; }
+
+// rows per wave of the cluster layout: tune key 38 (4 / 8; 1 = off), 0 = automatic -- 8 on the large levels.  Level 1 of the 256^3 hierarchy, fused
+// symmetric launch, 512 workgroups (profiles/r08_lanem_cluster_ab.txt): 3.61 ms in the pair layout at s = 3 (4.31 at s = 4); clusters of 4 / 8 rows
+// 3.40 / 3.36 ms at s = 3, 3.15 / 2.95 at s = 4, 3.35 / 3.14 at s = 5 -- a wave that loads 46 unique operands per row instead of 60 affords the longer
+// rows of a deeper merge.  The small levels are bound by their hand-offs and keep one row per wave (and the one-XCD ticket form).
+int lanem_cluster_rows(const pamg_matrix_s *A)
+{
+    if (A->lanem_cluster >= 4) return A->lanem_cluster;
+    if (A->lanem_cluster == 1) return 0;
+    static const int env = [] { const char *e = getenv("PAMG_LANEM_CLUSTER"); return e ? atoi(e) : 0; }();     // A/B: 1 = off, 4 / 8
+    if (A->nrows <= 131072 || env == 1) return 0;
+    return env == 4 ? 4 : 8;
+}
 
 // levels merged per super-level: tune key 33 (1 = unmerged form, >= 2 = that many), 0 = automatic -- rows long enough to fill a wave
 // (the SA coarse levels: >= 12 entries per row on average), f64
@@ -1040,10 +1221,11 @@ int lanem_smax(const pamg_matrix_s *A, const GsSchedule *g)
     const char *e = getenv("PAMG_LANE_MERGE");
     if (e && atoi(e) >= 1) return atoi(e);
     if (A->nnz < 12 * std::max<int64_t>(1, A->nrows)) return 1;
-    // large levels: 3 (level 1 of the 256^3 hierarchy: 1.80 ms at 2, 1.76 at 3, 2.14 at 4 -- the sweep is bound by rows per second, longer rows cost);
+    // large levels: 3 in the pair layout (level 1 of the 256^3 hierarchy: 1.80 ms at 2, 1.76 at 3, 2.14 at 4 -- the sweep is bound by rows per second, longer
+    // rows cost), 4 in the cluster layout (above);
     // small levels are bound by their hand-offs: 8 (every unit in registers there; level 2, 44.6 K rows: 0.484 ms at 4, 0.447 at 6, 0.440 at 8; level 3,
     // 463 rows: 0.052 / 0.042 / 0.034)
-    return A->nrows > 131072 ? 3 : 8;
+    return A->nrows > 131072 ? (lanem_cluster_rows(A) ? 4 : 3) : 8;
 }
 
 int build_lanem_part(pamg_matrix_s *A, GsSchedule *g)
@@ -1061,8 +1243,9 @@ int build_lanem_part(pamg_matrix_s *A, GsSchedule *g)
     // row, not by waves or hand-offs (profiles/r06_microbench_lanem_rows_per_wave.json); small levels are bound by their hand-offs: a wave that waits
     // for ITS row only (tune key 35: 1 / 2, 0 = this rule)
     const int rpw = A->lanem_rpw ? A->lanem_rpw : (A->nrows > 131072 ? 2 : 1);
+    const int cluster = lanem_cluster_rows(A);
     if (build_lanem_plan((int)A->nrows, A->h_Ap.data(), A->h_Aj.data(), hAx.data(), g->row_start, g->row_step, (int)g->nrows, g->nlevels, g->h_vis, g->h_lvl,
-                         s_max, 1e3, P, LANEM_KMAX * 64, rpw))
+                         s_max, 1e3, P, LANEM_KMAX * 64, rpw, cluster))
         return PAMG_E_ARG;
     hAx = PlanVec<double>();
     // nothing gained (every group closed at once: an operator the growth bound rejects): the unmerged form is the cheaper layout
@@ -1073,6 +1256,31 @@ int build_lanem_part(pamg_matrix_s *A, GsSchedule *g)
     t->closed_by_length = P.closed_by_length; t->closed_by_growth = P.closed_by_growth; t->max_growth = P.max_growth;
     t->n_early = P.n_early; t->n_old = P.n_old; t->n_b = P.n_b; t->max_super_groups = P.max_super_groups;
     t->super_grp = P.super_grp;
+    t->cluster = P.cluster; t->n_uunits = P.n_uunits; t->n_uearly = P.n_uearly; t->n_uold = P.n_uold; t->n_ub = P.n_ub; t->n_early_lines = P.n_early_lines;
+    if (P.cluster) {
+        std::vector<int4> crec((size_t)P.ngroups);
+        lane_parallel(P.ngroups, [&](int64_t g0, int64_t g1) {
+            for (int64_t q = g0; q < g1; ++q)
+                crec[(size_t)q] = make_int4(P.gate[(size_t)q], P.c_uunit[(size_t)q], P.c_sunit[(size_t)q],
+                                            (int)P.c_KU[(size_t)q] | ((int)P.c_KS[(size_t)q] << 8) | ((int)P.c_rows[(size_t)q] << 16));
+        });
+        int st = lane_upload(&t->d_crec, crec.data(), crec.size() * sizeof(int4), &t->bytes);
+        if (!st) st = lane_upload(&t->d_cols, P.ucodes.data(), P.ucodes.size() * sizeof(int), &t->bytes);
+        if (!st) st = lane_upload(&t->d_vals, P.svals.data(), P.svals.size() * sizeof(double), &t->bytes);
+        if (!st) st = lane_upload(&t->d_sidx, P.sidx.data(), P.sidx.size() * sizeof(unsigned short), &t->bytes);
+        if (!st) st = lane_upload(&t->d_crid, P.rid.data(), P.rid.size() * sizeof(int), &t->bytes);
+        if (!st) st = lane_upload(&t->d_crd, P.rdiag.data(), P.rdiag.size() * sizeof(double), &t->bytes);
+        if (!st && !g->d_xold) {
+            const size_t xb = ((size_t)A->nrows + 8) * sizeof(double);
+            st = (int)hipMalloc(&g->d_xold, xb);
+            if (!st) t->bytes += xb;
+        }
+        if (st) { free_lanem_part(t); return st; }
+        if (getenv("PAMG_TIMING")) fprintf(stderr, "[pamg timing]     lanem plan: cluster layout, %d rows per wave: %zu bytes uploaded\n", P.cluster, t->bytes);
+        g->lanem = t;
+        g->bytes += t->bytes;
+        return PAMG_OK;
+    }
     std::vector<LaneMRec> rec((size_t)P.ngroups);
     lane_parallel(P.ngroups, [&](int64_t g0, int64_t g1) {
         for (int64_t q = g0; q < g1; ++q) {
@@ -1095,9 +1303,18 @@ int build_lanem_part(pamg_matrix_s *A, GsSchedule *g)
         if (!st) t->bytes += xb;
     }
     if (st) { free_lanem_part(t); return st; }
+    if (getenv("PAMG_TIMING")) fprintf(stderr, "[pamg timing]     lanem plan: %d row(s) per wave: %zu bytes uploaded\n", P.rpw, t->bytes);
     g->lanem = t;
     g->bytes += t->bytes;
     return PAMG_OK;
+}
+
+// the layout-dependent operands of a launch
+static void lanem_layout_args(const LaneMSched *t, LaneMArgs &a)
+{
+    a.cols = t->d_cols; a.vals = t->d_vals;
+    a.rec = t->cluster ? reinterpret_cast<const LaneMRec *>(t->d_crec) : t->d_rec;
+    a.sidx = t->d_sidx; a.crid = t->d_crid; a.crd = t->d_crd; a.crows = t->cluster;
 }
 
 int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStream_t s)
@@ -1106,26 +1323,27 @@ int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStr
     if (!t || !g->d_xold) return PAMG_E_STATE;
     const int64_t n = A->nrows;
     LaneMArgs a;
-    a.cols = t->d_cols; a.vals = t->d_vals; a.rec = t->d_rec;
+    lanem_layout_args(t, a);
     a.use_gate = (A->lane_flags & 1) ? 1 : 0;
     a.xold = (const double *)g->d_xold; a.y = (double *)x; a.xs = (double *)g->d_xs; a.b = (const double *)b;
     a.err = g->d_sync + 1; a.ticket = g->d_sync + 20;
     a.ngroups = (int)t->ngroups;
     a.nidle = (int)std::max<int64_t>(1, std::min<int64_t>(n, 1 << 20));
-    if (A->gs_prof && !t->d_prof) {
+    if (A->gs_prof && !t->d_prof && !t->cluster) {
         PAMG_HIP(hipMalloc((void **)&t->d_prof, (size_t)t->ngroups * 4 * sizeof(long long)));
         PAMG_HIP(hipMemset(t->d_prof, 0, (size_t)t->ngroups * 4 * sizeof(long long)));
     }
-    a.prof = A->gs_prof ? t->d_prof : nullptr;
+    a.prof = (A->gs_prof && !t->cluster) ? t->d_prof : nullptr;
     const int fgrid = (int)std::min<int64_t>(4096, (n + BLK - 1) / BLK);
     hipLaunchKernelGGL(lanem_prepare_kernel, dim3(fgrid), dim3(BLK), 0, s, (const double *)x, (double *)g->d_xold, (double *)g->d_xs, n);
     PAMG_HIP(hipGetLastError());
     // the ticket form inside one XCD only for tiny levels: one row per group means one ticket per ROW, and the ticket counter is one address whose
     // atomics serialise (11.4 ns each) -- level 2 of the 256^3 hierarchy (44.6 K rows): 0.58 ms inside one XCD, 0.48 across the chip
-    const bool xcd = A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= 8192);
+    const bool xcd = !t->cluster && (A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= 8192));      // (the cluster layout: static form only)
     static const int nreg_env = [] { const char *e = getenv("PAMG_LANEM_NREG"); return e ? atoi(e) : 0; }();     // A/B: 2 / 8 units in registers on one-row-per-wave levels
     const bool all_regs = t->rpw == 1 && (nreg_env ? nreg_env == 8 : A->nrows <= 131072);
-    const void *k = t->rpw == 2 ? (xcd ? (const void *)gs_lanem_kernel<1, 2, 4> : (const void *)gs_lanem_kernel<0, 2, 4>)
+    const void *k = t->cluster  ? (const void *)gs_lanem_kernel<0, 0, 8>
+                  : t->rpw == 2 ? (xcd ? (const void *)gs_lanem_kernel<1, 2, 4> : (const void *)gs_lanem_kernel<0, 2, 4>)
                   : all_regs    ? (xcd ? (const void *)gs_lanem_kernel<1, 1, 8> : (const void *)gs_lanem_kernel<0, 1, 8>)
                                 : (xcd ? (const void *)gs_lanem_kernel<1, 1, 2> : (const void *)gs_lanem_kernel<0, 1, 2>);
     static thread_local int cus = 0;
@@ -1145,7 +1363,7 @@ int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStr
     // three workgroups per CU at most: from 768 workgroups on the sweep delivers what it delivers, more waves only slow each other down
     // (level 1 of the 256^3 hierarchy, s = 3: 1.76 ms with 768 workgroups, 1.88 with 1 024, 2.17 with 1 536, 2.33 with 1 792)
     // (two rows per wave, s = 3: 1.74 ms with 512 workgroups, 1.89 with 768, 2.08 with 1 024: two per CU)
-    int G = (int)std::min<int64_t>((want_waves + cwpb - 1) / cwpb, (int64_t)std::min(cap, t->rpw == 2 ? 2 : 3) * cus);
+    int G = (int)std::min<int64_t>((want_waves + cwpb - 1) / cwpb, (int64_t)std::min(cap, (t->rpw == 2 || t->cluster) ? 2 : 3) * cus);
     if (A->lane_G > 0) G = std::min(A->lane_G, cap * cus);
     G = (int)std::max<int64_t>(1, std::min<int64_t>(G, (t->ngroups + cwpb - 1) / cwpb));
     void *args[] = {(void *)&a};
@@ -1178,15 +1396,15 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
     LaneMSched *tf = gf->lanem, *tb = gb->lanem;
     if (!tf || !tb || !A->d_sym_hf[0] || !A->d_sym_hf[1] || !A->d_sym_hb || !A->d_sym_sync) return PAMG_E_STATE;
     const int64_t n = A->nrows;
-    auto one_xcd = [&](const GsSchedule *g) { return A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= 8192); };
+    auto one_xcd = [&](const GsSchedule *g) { return !g->lanem->cluster && (A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= 8192)); };
     const bool xcd = one_xcd(gf);
-    if (xcd != one_xcd(gb) || tf->rpw != tb->rpw || tf->ngroups < 1 || tb->ngroups < 1) return PAMG_E_UNSUPPORTED;
+    if (xcd != one_xcd(gb) || tf->rpw != tb->rpw || tf->cluster != tb->cluster || tf->ngroups < 1 || tb->ngroups < 1) return PAMG_E_UNSUPPORTED;
     LaneMSymArgs a;
     GsSchedule *gs2[2] = {gf, gb};
     for (int p = 0; p < 2; ++p) {
         LaneMSched *t = gs2[p]->lanem;
         LaneMArgs &q = a.ph[p];
-        q.cols = t->d_cols; q.vals = t->d_vals; q.rec = t->d_rec;
+        lanem_layout_args(t, q);
         q.use_gate = (A->lane_flags & 1) ? 1 : 0;
         q.b = (const double *)b;
         q.err = gf->d_sync + 1; q.ticket = nullptr;
@@ -1204,7 +1422,8 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
     a.xzero = x_zero ? 1 : 0;
     static const int nreg_env = [] { const char *e = getenv("PAMG_LANEM_NREG"); return e ? atoi(e) : 0; }();
     const bool all_regs = tf->rpw == 1 && (nreg_env ? nreg_env == 8 : A->nrows <= 131072);
-    const void *k = tf->rpw == 2 ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4> : (const void *)gs_lanem_sym_kernel<0, 2, 4>)
+    const void *k = tf->cluster  ? (const void *)gs_lanem_sym_kernel<0, 0, 8>
+                  : tf->rpw == 2 ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4> : (const void *)gs_lanem_sym_kernel<0, 2, 4>)
                   : all_regs     ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 8> : (const void *)gs_lanem_sym_kernel<0, 1, 8>)
                                  : (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 2> : (const void *)gs_lanem_sym_kernel<0, 1, 2>);
     static thread_local int cus = 0;
@@ -1221,7 +1440,7 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
         const LaneMSched *t = gs2[p]->lanem;
         const int per_level = (int)((t->ngroups + t->nsuper - 1) / std::max(1, t->nsuper));
         const int64_t want_waves = std::max<int64_t>(128, ((int64_t)A->lanem_ahead10 * per_level + 9) / 10);
-        int Gp = (int)std::min<int64_t>((want_waves + LANE_WPB - 1) / LANE_WPB, (int64_t)std::min(cap, t->rpw == 2 ? 2 : 3) * cus);
+        int Gp = (int)std::min<int64_t>((want_waves + LANE_WPB - 1) / LANE_WPB, (int64_t)std::min(cap, (t->rpw == 2 || t->cluster) ? 2 : 3) * cus);
         if (A->lane_G > 0) Gp = std::min(A->lane_G, cap * cus);
         Gp = (int)std::max<int64_t>(1, std::min<int64_t>(Gp, (t->ngroups + LANE_WPB - 1) / LANE_WPB));
         G = std::max(G, Gp);
@@ -1237,14 +1456,19 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
 
 // info[0..11] = super-levels, dependency levels, groups (rows), 64-slot units, early / old / b operands, longest merged row, levels merged at most,
 //               groups closed early by length / by growth, workgroups of the last launch;  growth = largest accepted growth factor
+// info[12..19] = rows per wave of the cluster layout (0: the row / pair layout), groups (waves' work items), padded slots (64 x units), units of unique
+//               operands, unique early / old / b operands and distinct 64-byte lines of the unique early operands, each summed over the groups (the
+//               row / pair layouts share nothing: their unique operands ARE info[4..6], lines are not counted)
 int lanem_info(const GsSchedule *g, int64_t *info, double *growth)
 {
-    for (int i = 0; i < 12; ++i) info[i] = 0;
+    for (int i = 0; i < 20; ++i) info[i] = 0;
     if (growth) *growth = 0.0;
     if (!g || !g->lanem) return PAMG_OK;
     const LaneMSched *t = g->lanem;
     info[0] = t->nsuper; info[1] = t->nlevels; info[2] = t->nrows; info[3] = t->n_units; info[4] = t->n_early; info[5] = t->n_old; info[6] = t->n_b;
     info[7] = t->max_len; info[8] = t->s_max; info[9] = t->closed_by_length; info[10] = t->closed_by_growth; info[11] = t->last_grid;
+    info[12] = t->cluster; info[13] = t->ngroups; info[14] = t->n_units * 64; info[15] = t->n_uunits;
+    info[16] = t->cluster ? t->n_uearly : t->n_early; info[17] = t->cluster ? t->n_uold : t->n_old; info[18] = t->cluster ? t->n_ub : t->n_b; info[19] = t->n_early_lines;
     if (growth) *growth = t->max_growth;
     return PAMG_OK;
 }

@@ -32,10 +32,25 @@
 //     vals[(unit + k) * 64 + lane]   v
 // A group only waits for groups of EARLIER super-levels (smaller numbers): the static wave assignment g = w, w + W, ...
 // stays deadlock-free.  SOR is not merged (its coefficients depend on the relaxation parameter of the call).
+//
+// Cluster layout (cluster = 4 / 8; same merged rows, same super-levels).  Neighbouring rows of a super-level share most of their operands, and
+// every operand is a load past the L1 on the device; one wave therefore takes up to R rows of ONE super-level that are consecutive in row-index
+// order, loads the UNION of their operands once and forms the row sums from its own LDS:
+//     ucodes[(uunit + k) * 64 + lane]   the group's unique operands in the encoding of `cols`, sorted by (kind, column); KU units, NONE = padding
+//     svals / sidx[(sunit + k) * 64 + lane]   KS units of slots {v, 16-bit code}: bits 0-8 index into the unique list, bits 9-11 the row of the
+//                                       group (0 .. R-1), LANEC_PAD = no product, LANEC_UNUSED = a lane without a row
+//     rid / rdiag[g * R + r]            the rows of the group (-1: none), loaded per lane
+// A lane serves ONE row: row r owns n_r = max(1, ceil(len_r / KS)) consecutive lanes (KS = the smallest count of slots per lane with which the
+// group's rows fit 64 lanes), its operand e sits in lane lo_r + e % n_r, slot e / n_r; the row sum is a segmented sum over the row's lanes.
+// A group is closed in front of the row with which its union would pass LANEC_UMAX operands or its rows would no longer fit 64 lanes x
+// LANEM_KMAX slots, and where the super-level ends.
 #pragma once
 #include "pamg_host_threads.h"
 #include <chrono>
+#include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <iterator>
 #include <cstdio>
 #include <cstdlib>
 
@@ -46,6 +61,11 @@ namespace pamg {
 constexpr int LANEM_BSRC = 0x20000000;        // operand read from b
 constexpr int LANEM_MASK = 0x1FFFFFFF;        // column of a slot
 constexpr int LANEM_KMAX = 8;                 // slots per lane: merged rows of up to 512 operands
+constexpr int LANEC_UMAX = 512;               // cluster layout: unique operands of a group (8 units; 4 KB of LDS per wave)
+constexpr int LANEC_IDX = 0x1FF;              // slot code: index into the unique list
+constexpr int LANEC_ROWSHIFT = 9;             //            row of the group (3 bits)
+constexpr int LANEC_PAD = 0x1000;             //            padding (no product)
+constexpr int LANEC_UNUSED = 0x2000;          //            the lane serves no row
 
 struct LaneMPlan {
     int s_max = 0;
@@ -70,6 +90,16 @@ struct LaneMPlan {
     int closed_by_length = 0, closed_by_growth = 0;   // groups closed before s_max levels were in
     double max_growth = 0.0;                  // largest accepted growth factor
     int64_t max_super_groups = 0;             // rows of the widest super-level
+    // ---- cluster layout (cluster > 0; unit / K / cols / vals stay empty, rid / rdiag hold `cluster` entries per group)
+    int cluster = 0;                          // rows per wave at most (4 / 8)
+    std::vector<int> c_uunit, c_sunit;        // [ngroups] first unit of the unique list / of the slots
+    std::vector<unsigned char> c_KU, c_KS, c_rows;   // [ngroups] units of either, rows of the group
+    PlanVec<int> ucodes;                      // [n_uunits * 64]
+    PlanVec<double> svals;                    // [n_sunits * 64]
+    PlanVec<unsigned short> sidx;             // [n_sunits * 64]
+    int64_t n_uunits = 0, n_sunits = 0;
+    int64_t n_uearly = 0, n_uold = 0, n_ub = 0;      // unique operands by kind, summed over the groups
+    int64_t n_early_lines = 0;                // distinct 64-byte lines among a group's unique early operands, summed over the groups
 };
 
 namespace lanem_detail {
@@ -114,7 +144,7 @@ struct RowRef { int64_t off = 0; int len = 0; int arena = -1; };
 // longer than LANEM_KMAX * 64 operands even unmerged, index range) -- the caller keeps the unmerged lane form.
 inline int build_lanem_plan(int n, const int *Ap, const int *Aj, const double *Ax, int row_start, int row_step, int m, int nl,
                             const std::vector<int> &vis, const std::vector<int> &lvl, int s_max, double growth_cap, LaneMPlan &P,
-                            int len_cap = LANEM_KMAX * 64, int rpw = 1)
+                            int len_cap = LANEM_KMAX * 64, int rpw = 1, int cluster = 0)
 {
     using namespace lanem_detail;
     const bool timing_ = getenv("PAMG_TIMING") != nullptr;
@@ -128,8 +158,10 @@ inline int build_lanem_plan(int n, const int *Ap, const int *Aj, const double *A
     P = LaneMPlan();
     P.s_max = s_max; P.nlevels = nl;
     if (m <= 0 || nl <= 0 || s_max < 1 || (rpw != 1 && rpw != 2)) return 1;
+    if (cluster != 0 && cluster != 4 && cluster != 8) return 1;
     if (n > LANEM_MASK) return 1;
-    P.rpw = rpw; P.nrows = m;
+    if (cluster) rpw = 1;                                       // (rows of up to 512 operands; the pair layout is not built)
+    P.rpw = rpw; P.nrows = m; P.cluster = cluster;
     len_cap = std::max(1, std::min(len_cap, LANEM_KMAX * (64 / rpw)));
     // rows in level order, visit order inside a level
     std::vector<int64_t> lptr((size_t)nl + 1, 0);
@@ -281,6 +313,181 @@ inline int build_lanem_plan(int n, const int *Ap, const int *Aj, const double *A
         int s = -1;
         for (int l = 0; l < nl; ++l) { if (starts[(size_t)l]) ++s; sup_of_level[(size_t)l] = s; }
         P.nsuper = s + 1;
+    }
+    if (cluster) {
+        // ---- cluster layout: up to R rows of a super-level, consecutive in row-index order, per group
+        const int R = cluster;
+        std::vector<int64_t> super_first_c((size_t)P.nsuper + 1, 0);
+        for (int l = 0; l < nl; ++l) super_first_c[(size_t)sup_of_level[(size_t)l] + 1] = lptr[l + 1];
+        std::vector<int> corder(order);
+        lane_parallel(P.nsuper, [&](int64_t s0, int64_t s1) {
+            for (int64_t s = s0; s < s1; ++s) std::sort(corder.begin() + super_first_c[(size_t)s], corder.begin() + super_first_c[(size_t)s + 1]);
+        }, 1);
+        auto ucmp = [](int x, int y) { return (unsigned)x < (unsigned)y; };
+        auto rlen = [&](int i) { return (diag[(size_t)i] != 0.0) ? ref[(size_t)i].len : 0; };
+        auto rcodes = [&](int i) { const RowRef &rr = ref[(size_t)i]; return acode[(size_t)rr.arena].data() + rr.off; };
+        auto rvals = [&](int i) { const RowRef &rr = ref[(size_t)i]; return aval[(size_t)rr.arena].data() + rr.off; };
+        // slots per lane with which rows of these lengths fit 64 lanes (0: they do not)
+        auto slots_per_lane = [&](const int *len, int nr) {
+            for (int ks = 1; ks <= LANEM_KMAX; ++ks) {
+                int lanes = 0;
+                for (int r = 0; r < nr; ++r) lanes += std::max(1, (len[r] + ks - 1) / ks);
+                if (lanes <= 64) return ks;
+            }
+            return 0;
+        };
+        // pass 1: the groups of every super-level (rows per group)
+        std::vector<std::vector<unsigned char>> cut((size_t)P.nsuper);
+        std::atomic<int> bad(0);
+        lane_parallel(P.nsuper, [&](int64_t s0, int64_t s1) {
+            std::vector<int> uni, tmp;
+            int len[8];
+            for (int64_t s = s0; s < s1; ++s) {
+                int nr = 0;
+                uni.clear();
+                for (int64_t q = super_first_c[(size_t)s]; q < super_first_c[(size_t)s + 1]; ++q) {
+                    const int i = corder[(size_t)q], li = rlen(i);
+                    const int *rc = rcodes(i);
+                    bool fits = nr < R;
+                    if (fits) {
+                        tmp.clear();
+                        std::set_union(uni.begin(), uni.end(), rc, rc + li, std::back_inserter(tmp), ucmp);
+                        len[nr] = li;
+                        fits = (int)tmp.size() <= LANEC_UMAX && slots_per_lane(len, nr + 1) > 0;
+                    }
+                    if (!fits) {
+                        if (nr == 0) { bad.store(1); return; }            // a single row that does not fit (cannot happen below len_cap)
+                        cut[(size_t)s].push_back((unsigned char)nr);
+                        nr = 0;
+                        uni.assign(rc, rc + li);
+                        len[0] = li;
+                        if (li > LANEC_UMAX || !slots_per_lane(len, 1)) { bad.store(1); return; }
+                    } else uni.swap(tmp);
+                    ++nr;
+                }
+                if (nr) cut[(size_t)s].push_back((unsigned char)nr);
+            }
+        }, 1);
+        if (bad.load()) return 1;
+        P.super_grp.assign((size_t)P.nsuper + 1, 0);
+        for (int s = 0; s < P.nsuper; ++s) {
+            P.super_grp[(size_t)s + 1] = P.super_grp[(size_t)s] + (int64_t)cut[(size_t)s].size();
+            P.max_super_groups = std::max<int64_t>(P.max_super_groups, (int64_t)cut[(size_t)s].size());
+        }
+        const int64_t G = P.super_grp[(size_t)P.nsuper];
+        if (G >= ((int64_t)1 << 30)) return 1;
+        P.ngroups = G;
+        P.c_rows.assign((size_t)G, 0); P.c_KU.assign((size_t)G, 1); P.c_KS.assign((size_t)G, 1); P.c_uunit.assign((size_t)G, 0); P.c_sunit.assign((size_t)G, 0);
+        P.rid.assign((size_t)G * R, -1); P.rdiag.assign((size_t)G * R, 0.0); P.gate.assign((size_t)G, -1); P.super_of.assign((size_t)G, 0);
+        std::vector<int64_t> gfirst((size_t)G, 0);                 // position of the group's first row in corder
+        lane_parallel(P.nsuper, [&](int64_t s0, int64_t s1) {
+            for (int64_t s = s0; s < s1; ++s) {
+                int64_t q = super_first_c[(size_t)s], g = P.super_grp[(size_t)s];
+                for (unsigned char nr : cut[(size_t)s]) { P.c_rows[(size_t)g] = nr; P.super_of[(size_t)g] = (int)s; gfirst[(size_t)g] = q; q += nr; ++g; }
+            }
+        }, 1);
+        // pass 2: units of every group
+        lane_parallel(G, [&](int64_t g0, int64_t g1) {
+            std::vector<int> uni;
+            int len[8];
+            for (int64_t g = g0; g < g1; ++g) {
+                uni.clear();
+                const int nr = P.c_rows[(size_t)g];
+                for (int r = 0; r < nr; ++r) {
+                    const int i = corder[(size_t)(gfirst[(size_t)g] + r)];
+                    len[r] = rlen(i);
+                    uni.insert(uni.end(), rcodes(i), rcodes(i) + len[r]);
+                }
+                std::sort(uni.begin(), uni.end(), ucmp);
+                uni.erase(std::unique(uni.begin(), uni.end()), uni.end());
+                P.c_KU[(size_t)g] = (unsigned char)std::max<size_t>(1, (uni.size() + 63) / 64);
+                P.c_KS[(size_t)g] = (unsigned char)slots_per_lane(len, nr);
+            }
+        });
+        int64_t uu = 0, su = 0;
+        for (int64_t g = 0; g < G; ++g) {
+            P.c_uunit[(size_t)g] = (int)uu; P.c_sunit[(size_t)g] = (int)su;
+            uu += P.c_KU[(size_t)g]; su += P.c_KS[(size_t)g];
+            if (uu >= ((int64_t)1 << 25) || su >= ((int64_t)1 << 25)) return 1;     // unit * 64 stays below 2^31
+        }
+        P.n_uunits = uu; P.n_sunits = su; P.n_units = su;
+        std::vector<int> sup_row((size_t)n, -1), best_dep((size_t)n, -1);
+        lane_parallel(m, [&](int64_t q0, int64_t q1) { for (int64_t q = q0; q < q1; ++q) { const int i = order[(size_t)q]; sup_row[(size_t)i] = sup_of_level[(size_t)lvl[i]]; } });
+        lane_parallel(m, [&](int64_t q0, int64_t q1) {
+            for (int64_t q = q0; q < q1; ++q) {
+                const int i = order[(size_t)q];
+                if (!(diag[(size_t)i] != 0.0)) continue;
+                const int *rc = rcodes(i);
+                int bl = -1;
+                for (int e = 0; e < ref[(size_t)i].len; ++e)
+                    if (rc[e] & LANE_EARLY) {
+                        const int j = rc[e] & LANEM_MASK;
+                        if (sup_row[(size_t)j] > bl) { bl = sup_row[(size_t)j]; best_dep[(size_t)i] = j; }
+                    }
+            }
+        });
+        lap_("clusters, units, gates' inputs");
+        plan_fill(P.ucodes, (size_t)uu * 64, (int)LANE_NONE);
+        plan_fill(P.svals, (size_t)su * 64, 0.0);
+        plan_fill(P.sidx, (size_t)su * 64, (unsigned short)(LANEC_UNUSED | LANEC_PAD));
+        std::atomic<int64_t> ne(0), no(0), nb(0), nd(0), ue(0), uo(0), ub(0), el(0);
+        lane_parallel(G, [&](int64_t g0, int64_t g1) {
+            int64_t e_ = 0, o_ = 0, b_ = 0, d_ = 0, ue_ = 0, uo_ = 0, ub_ = 0, el_ = 0;
+            std::vector<int> uni;
+            for (int64_t g = g0; g < g1; ++g) {
+                const int mysup = P.super_of[(size_t)g], nr = P.c_rows[(size_t)g], KS = P.c_KS[(size_t)g];
+                uni.clear();
+                for (int r = 0; r < nr; ++r) {
+                    const int i = corder[(size_t)(gfirst[(size_t)g] + r)];
+                    uni.insert(uni.end(), rcodes(i), rcodes(i) + rlen(i));
+                }
+                std::sort(uni.begin(), uni.end(), ucmp);
+                uni.erase(std::unique(uni.begin(), uni.end()), uni.end());
+                int *uc = P.ucodes.data() + (size_t)P.c_uunit[(size_t)g] * 64;
+                int last_line = -1;
+                for (size_t u = 0; u < uni.size(); ++u) {
+                    uc[u] = uni[u];
+                    if (uni[u] & LANE_EARLY) { ++ue_; const int ln = (uni[u] & LANEM_MASK) >> 3; if (ln != last_line) { ++el_; last_line = ln; } }
+                    else if (uni[u] & LANEM_BSRC) ++ub_;
+                    else ++uo_;
+                }
+                double *sv = P.svals.data() + (size_t)P.c_sunit[(size_t)g] * 64;
+                unsigned short *si = P.sidx.data() + (size_t)P.c_sunit[(size_t)g] * 64;
+                int lo = 0, gl = -1;
+                for (int r = 0; r < nr; ++r) {
+                    const int i = corder[(size_t)(gfirst[(size_t)g] + r)];
+                    const bool nodiag = !(diag[(size_t)i] != 0.0);
+                    const int len = rlen(i), nlanes = std::max(1, (len + KS - 1) / KS);
+                    P.rid[(size_t)(g * R + r)] = i | (nodiag ? LANE_NODIAG : 0);
+                    P.rdiag[(size_t)(g * R + r)] = nodiag ? 0.0 : 1.0 / diag[(size_t)i];
+                    for (int p = Ap[i]; p < Ap[i + 1]; ++p) d_ += (Aj[p] != i && Aj[p] >= 0 && Aj[p] < n);
+                    for (int k = 0; k < KS; ++k)
+                        for (int l = lo; l < lo + nlanes; ++l) si[(size_t)k * 64 + (size_t)l] = (unsigned short)(LANEC_PAD | (r << LANEC_ROWSHIFT));
+                    const int *rc = rcodes(i);
+                    const double *rv = rvals(i);
+                    for (int e = 0; e < len; ++e) {
+                        const size_t sl = (size_t)(e / nlanes) * 64 + (size_t)(lo + e % nlanes);
+                        const int u = (int)(std::lower_bound(uni.begin(), uni.end(), rc[e], ucmp) - uni.begin());
+                        si[sl] = (unsigned short)(u | (r << LANEC_ROWSHIFT));
+                        sv[sl] = rv[e];
+                        if (rc[e] & LANE_EARLY) {
+                            ++e_;
+                            int cand = rc[e] & LANEM_MASK;
+                            if (sup_row[(size_t)cand] > mysup - 2) cand = best_dep[(size_t)cand];
+                            if (cand >= 0 && sup_row[(size_t)cand] <= mysup - 2 && sup_row[(size_t)cand] > gl) { gl = sup_row[(size_t)cand]; P.gate[(size_t)g] = cand; }
+                        } else if (rc[e] & LANEM_BSRC) ++b_;
+                        else ++o_;
+                    }
+                    lo += nlanes;
+                }
+            }
+            ne += e_; no += o_; nb += b_; nd += d_; ue += ue_; uo += uo_; ub += ub_; el += el_;
+        });
+        P.n_early = ne.load(); P.n_old = no.load(); P.n_b = nb.load(); P.n_direct = nd.load();
+        for (int64_t q = 0; q < m; ++q) P.max_len = std::max(P.max_len, rlen(order[(size_t)q]));
+        P.n_uearly = ue.load(); P.n_uold = uo.load(); P.n_ub = ub.load(); P.n_early_lines = el.load();
+        lap_("cluster slots filled");
+        return 0;
     }
     // ---- groups: RPW rows of one super-level share a wave (64 / RPW lanes each).  With two rows per wave the rows of a super-level are paired by length
     //      (a pair is padded to the longer row's units; the order of rows INSIDE a super-level is free: they do not depend on each other)

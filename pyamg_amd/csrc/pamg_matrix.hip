@@ -1210,7 +1210,7 @@ int ensure_point_twin(pamg_matrix_s *A, GsSchedule *g)
             if (st != PAMG_OK) { A->point_twin_unfit = true; return st == PAMG_E_UNSUPPORTED || st == PAMG_E_ARG ? PAMG_OK : st; }
             T->gs_order = 1;
             T->lane_L = A->lane_L; T->lane_G = A->lane_G; T->lane_flags = A->lane_flags; T->lane_merge = A->lane_merge; T->line_scan = A->line_scan;
-            T->lane_wide = A->lane_wide; T->lanem_rpw = A->lanem_rpw; T->lanem_ahead10 = A->lanem_ahead10; T->gran_xcd = A->gran_xcd;
+            T->lane_wide = A->lane_wide; T->lanem_rpw = A->lanem_rpw; T->lanem_cluster = A->lanem_cluster; T->lanem_ahead10 = A->lanem_ahead10; T->gran_xcd = A->gran_xcd;
             A->point_twin = T;
             { std::lock_guard<std::mutex> lk2(g_sched_mu); A->bytes += T->bytes; A->point_twin_bytes = T->bytes; }
         }
@@ -2061,6 +2061,7 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
         case 27: if (value < 0 || value > 1) return PAMG_E_ARG; A->lane_wide = value; matrix_drop_point_twin(A); return PAMG_OK;
         case 33: if (value < 0 || value > 8) return PAMG_E_ARG; A->lane_merge = value; break;
         case 35: if (value < 0 || value > 2) return PAMG_E_ARG; A->lanem_rpw = value; break;
+        case 38: if (value != 0 && value != 1 && value != 4 && value != 8) return PAMG_E_ARG; A->lanem_cluster = value; break;
         case 36: if (value < 0 || value > 98304) return PAMG_E_ARG; A->lds_pad = value & ~15; return PAMG_OK;
         case 34: if (value < 1 || value > 400) return PAMG_E_ARG; A->lanem_ahead10 = value; matrix_drop_point_twin(A); return PAMG_OK;
         case 37: if (value < 0 || value > 1) return PAMG_E_ARG; A->sym_fused = value; return PAMG_OK;      // read at launch time; refused above while a solver's graphs hold the choice
@@ -2075,7 +2076,7 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
         case 28: if (value < 0 || value > 15 || (value & 6)) return PAMG_E_ARG; A->lane_flags = value; matrix_drop_point_twin(A); return PAMG_OK;      // bits 1, 2: retired (slab form, old values through the L1)
         default: return PAMG_E_ARG;
     }
-    if (key == 25 || key == 33 || key == 35) {         // lane geometry / merging: drop the lane parts only (and the point twin, which copied the keys)
+    if (key == 25 || key == 33 || key == 35 || key == 38) {         // lane geometry / merging: drop the lane parts only (and the point twin, which copied the keys)
         matrix_drop_point_twin(A);
         for (int k = 0; k < 4; ++k) {
             GsSchedule *g = A->gs[k];
@@ -2267,7 +2268,7 @@ int pamg_matrix_kz_info(pamg_matrix_t A, int which, int64_t info[8])
     return pamg::kz_lane_info(A->ls[which], info);
 }
 
-int pamg_matrix_lanem_info(pamg_matrix_t A, int which, int64_t info[12], double *growth)
+int pamg_matrix_lanem_info(pamg_matrix_t A, int which, int64_t info[20], double *growth)
 {
     if (!A || !info || which < 0 || which > 3) return PAMG_E_ARG;
     return pamg::lanem_info(A->gs[which], info, growth);

@@ -6,6 +6,21 @@ code."""
 import numpy as np
 
 
+
+def _lanem_bytes(l_, n, vb):
+    """bytes one merged sweep streams: the cluster layout (16-byte record per group, 4-byte unique codes, 8 + 2 bytes per slot, 12 bytes of row data)
+    or the row / pair layout (12 bytes per slot, 32-byte record per row); plus b, x, hand-off buffer and snapshot"""
+    if l_.get("cluster_rows"):
+        return l_["units"] * 64 * (vb + 2) + l_["unique_units"] * 64 * 4 + l_["groups"] * 16 + n * (12 + 4 * vb)
+    return l_["units"] * 64 * (vb + 4) + n * (32 + 4 * vb)
+
+
+def _lanem_format(l_):
+    if l_.get("cluster_rows"):
+        return (f"clusters of <= {l_['cluster_rows']} rows per wave ({l_['rows'] / max(1, l_['groups']):.1f} on average), {l_['units'] / max(1, l_['groups']):.2f} x 64 slots and "
+                f"{l_['unique_units'] / max(1, l_['groups']):.2f} x 64 unique operands per cluster, padded")
+    return f"one row per wave, {l_['units'] / max(1, l_['rows']):.2f} x 64 operand slots per row, padded"
+
 def _vec_bytes(epi, nr, nc, vb=8):
     return {"SET": vb * (nc + nr), "ACC": vb * (nc + 2 * nr), "RESID": vb * (nc + 2 * nr), "SUMSQ": vb * (nc + nr),
             "AXPBY": vb * (nc + 2 * nr), "ACC_AXPBY": vb * (nc + 3 * nr), "JACOBI": vb * (nc + 2 * nr), "JACOBI_B": vb * (nc + 2 * nr)}[epi]
@@ -71,16 +86,16 @@ def kernel_map(dml, smoother_kind):
                         out.append({"family": "gs_lanem", "grid": int(sym["launch_grid"]), "level": i, "op": "A",
                                     "what": f"symmetric Gauss-Seidel sweep, one launch (fast order, merged: {lm[0]['super_levels']} + {lm[1]['super_levels']} super-levels of <= {lm[0]['s_max']} dependency levels)",
                                     "rows": int(n), "nnz": int(nnz), "bytes_alg": int(2 * alg),
-                                    "bytes_streamed": int(sum(l_["units"] * 64 * (vb + 4) + n * (32 + 4 * vb) for l_ in lm)),
-                                    "format": f"one row per wave, {lm[0]['units'] / max(1, lm[0]['rows']):.2f} x 64 operand slots per row, padded",
+                                    "bytes_streamed": int(sum(_lanem_bytes(l_, n, vb) for l_ in lm)),
+                                    "format": _lanem_format(lm[0]),
                                     "dependency_levels": int(lm[0]["super_levels"] + lm[1]["super_levels"])})
                 for which, dirn in directions:
                     lane, tile, line, lanem = A.lane_info(which), A.tile_info(which), A.line_info(which), A.lanem_info(which)
                     if lanem["rows"] and lanem["launch_grid"]:
                         out.append({"family": "gs_lanem", "grid": int(lanem["launch_grid"]), "level": i, "op": "A",
                                     "what": f"{dirn} Gauss-Seidel sweep (fast order, merged: {lanem['super_levels']} super-levels of <= {lanem['s_max']} dependency levels)",
-                                    "rows": int(n), "nnz": int(nnz), "bytes_alg": int(alg), "bytes_streamed": int(lanem["units"] * 64 * (vb + 4) + n * (32 + 4 * vb)),
-                                    "format": f"one row per wave, {lanem['units'] / max(1, lanem['rows']):.2f} x 64 operand slots per row, padded", "dependency_levels": int(lanem["super_levels"])})
+                                    "rows": int(n), "nnz": int(nnz), "bytes_alg": int(alg), "bytes_streamed": int(_lanem_bytes(lanem, n, vb)),
+                                    "format": _lanem_format(lanem), "dependency_levels": int(lanem["super_levels"])})
                     elif line["lines"] and line["launch_grid"]:
                         out.append({"family": "gs_line", "grid": int(line["launch_grid"]), "level": i, "op": "A", "what": f"{dirn} Gauss-Seidel sweep (fast order, line scan: {line['lines']} lines, {line['line_levels']} line levels)",
                                     "rows": int(n), "nnz": int(nnz), "bytes_alg": int(alg), "bytes_streamed": int(line["chunks"] * 64 * (line["slots_per_row"] * (vb + 4) + 2 * vb + 1) + n * 4 * vb),
