@@ -371,6 +371,12 @@ int pamg_matrix_info(pamg_matrix_t A, int64_t info[8]);
  * instruction schedule; pamg_matrix_autotune times both).
  * 37 = fused symmetric sweep (default 1): a symmetric Gauss-Seidel sweep in fast order is ONE persistent launch (forward schedule, completion
  * barrier, backward schedule) where both schedules take the merged lane form or both the line form (f64); 0 = two directional launches.  Same bits.
+ * 39 = ZERO-ITERATE plans (round 9): a symmetric sweep announced to start from x = 0 (pamg_matrix_gauss_seidel_x0, a cycle's pre-smoothing below the
+ * finest level) runs the merged forward plan of tril(A), which also stores the numerators w_r = b_r - s_r, then the merged backward plan of triu(A)
+ * with w as right-hand side -- half the operands per row, fused or as two launches alike; equal to the general plans in exact arithmetic, to rounding
+ * in floating point.  0 (default) = automatic: pamg_solver_finalize builds them on every level below the finest whose pre-smoother takes the merged
+ * form in both directions, a bare operator has none; 1 = off; 2 = on (a solver: the finest level too; a bare operator builds them at its first such
+ * sweep outside a graph capture).  40 = their merge depth (2..16; 0 = automatic).
  * Returns PAMG_E_STATE while a solver holds the operator (captured graphs point into the plans). */
 int pamg_matrix_tune(pamg_matrix_t A, int key, int value);
 /* n_values = size of the operator's value dictionary when the whole-operator kernels stream 8-bit value codes
@@ -417,7 +423,8 @@ int pamg_matrix_lane_info(pamg_matrix_t A, int which, int64_t info[8]);
  * or a cluster), padded slots (64 x info[3]; over info[4] + info[5] + info[6] it is the layout's padding factor), 64-code units of unique operands,
  * unique operands polled / read from the snapshot / read from b and distinct 64-byte lines of the unique polled operands, each counted per group and
  * summed (what a wave really loads where the rows of a group share operands; the row / pair layouts share nothing: their counts repeat
- * info[4..6] and no lines are counted). */
+ * info[4..6] and no lines are counted).
+ * which = 4 / 5 (round 9): the operator's zero-iterate plans (tune key 39), the forward plan of tril(A) / the backward plan of triu(A). */
 int pamg_matrix_lanem_info(pamg_matrix_t A, int which, int64_t info[20], double *growth);
 /* Fast order (tune key 24 = 1) of the BSR POINT sweep (amg_core::bsr_gauss_seidel, relaxation.h:185-266: what relaxation.gauss_seidel runs on a
  * block operator): the same rows in the same order are the scalar Gauss-Seidel sweep of the flattened operator, so the block operator builds a
@@ -508,8 +515,10 @@ int pamg_matrix_gauss_seidel(pamg_matrix_t A, void *x, const void *b, int sweep,
 int pamg_matrix_gauss_seidel_x0(pamg_matrix_t A, void *x, const void *b, int sweep, double omega,
                                 int iterations, int x_is_zero, pamg_stream_t s);
 /* The fused symmetric sweep (tune key 37): {fused launches enqueued or captured so far, those with x known to be zero, form of the last one
- * (1 merged lanes across the chip, 2 lines, 3 merged lanes inside one XCD, 0 none yet), its workgroups, tune key 37, entries of the forward hand-off buffer that are NOT sentinels (0 between
- * launches; -1: no buffers), counters that are not zero (0 between launches), 0}.  Synchronises the device. */
+ * (1 merged lanes across the chip, 2 lines, 3 merged lanes inside one XCD, 0 none yet), the workgroups of the last one on the general plans (a launch on
+ * the zero-iterate plans reports its own in pamg_matrix_lanem_info(which = 4)), tune key 37, entries of the forward hand-off buffer that are NOT sentinels (0 between
+ * launches; -1: no buffers), counters that are not zero (0 between launches), symmetric sweeps (fused or as two launches) that ran on the
+ * zero-iterate plans (tune key 39)}.  Synchronises the device. */
 int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[8]);
 /* relaxation.polynomial (relaxation.py:585-659); coeffs is a HOST array; x_is_zero != 0
  * asserts x == 0 on entry (the reference tests norm(x) == 0, relaxation.py:649). */

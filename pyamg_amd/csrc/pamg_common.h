@@ -243,8 +243,19 @@ struct pamg_matrix_s {
     unsigned *d_sym_sync = nullptr;  // [0] finished groups of phase 1, [1] workgroups that left, [2] / [3] tickets of phase 1 / 2, [4] home XCD + 1, [5] parity: the forward buffer of the next launch
     int sym_cap = 0;                 // co-resident workgroups per CU of the fused kernel (queried once per kernel)
     const void *sym_cap_kernel = nullptr;
+    int zsym_cap = 0;                // the same for the fused kernel's zero-iterate instantiation
+    const void *zsym_cap_kernel = nullptr;
+    int sym_general_grid = 0;        // workgroups of the last fused launch on the general plans (sym_grid: of the last fused launch of either kind)
     int sym_form = 0, sym_grid = 0;  // the last fused launch: 1 = merged lanes, 2 = lines, 3 = merged lanes inside one XCD / its workgroups (diagnostics)
     long long sym_launches = 0, sym_zero_launches = 0;   // fused launches enqueued or captured / those with x known to be zero
+    // zero-iterate plans (pamg_lane.hip): merged plans of tril(A) forward / triu(A) backward for symmetric sweeps that start from x = 0, and the
+    // vector of numerators the forward half hands to the backward half
+    int zero_plans = 0;              // tune key 39: 0 = automatic (a solver builds them on the levels below its finest; a bare operator has none), 1 = off, 2 = on
+    int zero_merge = 0;              // tune key 40: dependency levels merged per super-level in those plans (0 = automatic, 2..16)
+    struct pamg::LaneMSched *zplan[2] = {nullptr, nullptr};
+    void *d_zw = nullptr;
+    size_t zero_bytes = 0;           // what the plans and d_zw added to `bytes`
+    long long zero_plan_launches = 0;   // symmetric sweeps (fused or as two launches) that ran on the zero-iterate plans
     size_t bytes = 0;
 };
 
@@ -368,6 +379,15 @@ size_t lanem_part_bytes(const GsSchedule *g);
 int lanem_info(const GsSchedule *g, int64_t *info, double *growth);
 int lanem_levels(const GsSchedule *g, int64_t *out, int64_t cap, int64_t *n);
 int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, bool x_zero, hipStream_t s);
+int lanem_plan_info(const struct LaneMSched *t, int64_t *info, double *growth);
+int build_zero_plan(pamg_matrix_s *A, int dir);  // dir 0: forward plan of tril(A), 1: backward plan of triu(A); PAMG_E_ARG: the form does not fit
+void free_zero_plans(pamg_matrix_s *A);
+size_t zero_plan_bytes(const pamg_matrix_s *A);
+bool zero_plans_ready(const pamg_matrix_s *A, const GsSchedule *gf, const GsSchedule *gb);
+int lanem_zero_pair_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, hipStream_t s);
+int ensure_zero_parts(pamg_matrix_s *A, bool build);   // pamg_matrix.hip: complete (or drop) the operator's zero-iterate plans; allocates, never inside a capture
+void matrix_drop_zero_plans(pamg_matrix_s *A);
+int gs_sweep_zero_pair(pamg_matrix_s *A, void *x, const void *b, hipStream_t s, bool *ran);   // symmetric sweep from x = 0 as two launches on the zero-iterate plans
 int sym_fill_sentinels(void *p, int64_t n);      // n f64 sentinels on the null stream, synchronised
 int sweep_error(pamg_matrix_s *A, bool *error);      // spin bound hit since the last call? (caller has synchronised; clears the flag)
 inline size_t tsize(int dtype) { return dtype == PAMG_F64 ? 8 : 4; }

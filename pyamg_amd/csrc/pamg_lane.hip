@@ -27,6 +27,7 @@
 #include "pamg_common.h"
 #include "pamg_lane_plan.h"
 #include "pamg_lanem_plan.h"
+#include "pamg_tile_plan.h"
 
 namespace pamg {
 
@@ -397,6 +398,7 @@ struct LaneMArgs {
     const int *crid;
     const double *crd;
     int crows;
+    double *w;             // zero-iterate forward plan (the kernels' template argument Z): every updated row also stores its numerator b_r - s_r here
 };
 
 // x -> snapshot, sentinels -> hand-off buffer: the two passes every merged sweep starts with, in one launch
@@ -430,6 +432,7 @@ struct MCtx {
     int c[NREG];
     double v[NREG], xv[NREG];
     double bv, xo, rd;         // per lane: its row's b, old value, 1 / a_ii
+    double num;                // per lane: b - sum of its row (m_finish; what a zero-iterate forward plan stores in w)
     int rid;                   // per lane: its row | NODIAG, -1 = dummy slot
     int gate, unit, K, g;      // uniform
 };
@@ -469,7 +472,9 @@ __device__ __forceinline__ void m_slots(const LaneMArgs &a, MCtx<NREG> &C, const
 // xz: the old iterate is known to be all zeros -- every OLD operand (neither an early one nor an entry of b) becomes an idle slot, its product + 0
 // as the padding's is: the same bits for finite data without the gathers.  coh: a.xold was written by other workgroups of THIS launch (the second
 // phase of the fused symmetric sweep), so the row's own old value is read past the L1 as the operands are
-template <int NREG>
+// BCOH: a.b was written by other workgroups of THIS launch too (the backward phase on a zero-iterate plan, whose right-hand side is the vector of
+// numerators the forward phase stored): the row's own entry is read past the L1; the operands that come from b already are
+template <int NREG, bool BCOH = false>
 __device__ __forceinline__ void m_gather(const LaneMArgs &a, MCtx<NREG> &C, int idle, const bool xz = false, const bool coh = false)
 {
 #pragma unroll
@@ -481,7 +486,8 @@ __device__ __forceinline__ void m_gather(const LaneMArgs &a, MCtx<NREG> &C, int 
             if (!(C.c[k] & (LANE_EARLY | LANEM_BSRC))) C.c[k] |= LANE_NONE;
     }
     const int row = C.rid < 0 ? 0 : (C.rid & LANE_MASK);
-    C.bv = a.b[row];
+    if constexpr (BCOH) C.bv = __hip_atomic_load(a.b + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else C.bv = a.b[row];
     C.xo = coh ? __hip_atomic_load(a.xold + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.xold[row];      // used by rows without a diagonal only
     // every operand by an L1-bypassing load: early ones poll the hand-off buffer, static ones read the snapshot of x and b (ordinary loads for
     // the static operands were measured 3 - 5 % slower, profiles/r06_microbench_lanem_plain_loads_for_static_operands_not_kept.json)
@@ -566,14 +572,16 @@ __device__ __forceinline__ double m_finish(const LaneMArgs &a, MCtx<NREG> &C, in
     }
     s = seg_allreduce<64 / RPW, T>(s);
     const bool upd = C.rid >= 0 && !(C.rid & LANE_NODIAG);
-    T val = (C.bv - s) * C.rd;
+    C.num = C.bv - s;
+    T val = C.num * C.rd;
     if (!upd) val = C.xo;
     return val;
 }
 
 // PH = 1: the first phase of the fused symmetric sweep -- the hand-off buffer is also where the second phase reads its OLD operands (every row
 // publishes, a row without a diagonal its old value), x is not written
-template <int RPW, int MODE, int NREG, int PH = 0>
+// WST: a zero-iterate forward plan -- the row's numerator goes to a.w
+template <int RPW, int MODE, int NREG, int PH = 0, bool WST = false>
 __device__ __forceinline__ void m_publish(const LaneMArgs &a, const MCtx<NREG> &C, double val)
 {
     if (((threadIdx.x & 63) & (64 / RPW - 1)) == 0 && C.rid >= 0) {
@@ -582,6 +590,9 @@ __device__ __forceinline__ void m_publish(const LaneMArgs &a, const MCtx<NREG> &
         else __hip_atomic_store(a.xs + row, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if constexpr (PH != 1) {
             if (!(C.rid & LANE_NODIAG)) a.y[row] = val;
+        }
+        if constexpr (WST) {                                  // the numerator crosses XCDs inside the fused launch: the flavour of the publishing store
+            if (!(C.rid & LANE_NODIAG)) __hip_atomic_store(a.w + row, C.num, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -595,8 +606,8 @@ constexpr int LANEC_K = 8;                    // units of unique operands / of s
 
 __device__ __forceinline__ int4 c_rec(const int4 *rp, int g, int gend) { return rp[(size_t)(g < gend ? g : gend - 1)]; }
 
-// one group.  PH as in m_publish; xz / coh as in m_gather
-template <int PH>
+// one group.  PH / WST as in m_publish; xz / coh / BCOH as in m_gather
+template <int PH, bool WST = false, bool BCOH = false>
 __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const int4 &q, int g, int lane, int idle, const bool xz, const bool coh)
 {
     using T = double;
@@ -639,7 +650,9 @@ __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const i
     const int rid = unused ? -1 : a.crid[ri];
     const T rd = a.crd[ri];
     const int row = rid < 0 ? 0 : (rid & LANE_MASK);
-    const T bv = a.b[row];
+    T bv;
+    if constexpr (BCOH) bv = __hip_atomic_load(a.b + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else bv = a.b[row];
     const T xo = coh ? __hip_atomic_load(a.xold + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.xold[row];      // used by rows without a diagonal only
     unsigned pend = 0;
 #pragma unroll
@@ -703,12 +716,16 @@ __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const i
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // the next group's values overwrite what was read here
     __builtin_amdgcn_wave_barrier();
     const bool upd = rid >= 0 && !(rid & LANE_NODIAG);
-    T val = (bv - s) * rd;
+    const T num = bv - s;
+    T val = num * rd;
     if (!upd) val = xo;
     if (tail && rid >= 0) {
         __hip_atomic_store(a.xs + row, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if constexpr (PH != 1) {
             if (upd) a.y[row] = val;
+        }
+        if constexpr (WST) {
+            if (upd) __hip_atomic_store(a.w + row, num, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -716,7 +733,9 @@ __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const i
 // NREG = units of a group held in registers: 2 (one row per wave) / 4 (two rows per wave) on the large levels, where eight waves per SIMD matter;
 // 8 on the small levels, whose sweeps are bound by their hand-offs -- there the sequential tail of a long row sits on the critical path (level 2 of the
 // 256^3 hierarchy at s = 6: 56 % of the rows hold three and more units)
-template <int MODE, int RPW, int NREG>
+// Z = 1: the forward plan of a zero-iterate pair run as a launch of its own (the numerators go to a.w; the backward plan then runs as Z = 0 with
+// b = that vector: the kernel boundary orders the two)
+template <int MODE, int RPW, int NREG, int Z = 0>
 __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -733,7 +752,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
         int4 q = c_rec(rp, g, gend);
         for (; g < gend; g += W) {
             const int4 nq = c_rec(rp, g + W, gend);
-            c_group<0>(a, c_lds + wib * LANEC_UMAX, q, g, lane, idle, false, false);
+            c_group<0, Z != 0>(a, c_lds + wib * LANEC_UMAX, q, g, lane, idle, false, false);
             q = nq;
         }
     } else {
@@ -757,7 +776,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
                 long long t2 = 0;
                 unsigned sp = 0;
                 const double val = m_finish<RPW, NREG>(a, X, idle, &t2, &sp);
-                m_publish<RPW, MODE, NREG>(a, X, val);
+                m_publish<RPW, MODE, NREG, 0, Z != 0>(a, X, val);
                 if (lane == 0) {
                     long long *o = a.prof + (size_t)g * 4;
                     o[0] = t0 | ((long long)(sp > 4095u ? 4095u : sp) << 52);
@@ -767,7 +786,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
                 m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
                 m_gather<NREG>(a, X, idle);
                 const double val = m_finish<RPW, NREG>(a, X, idle);
-                m_publish<RPW, MODE, NREG>(a, X, val);
+                m_publish<RPW, MODE, NREG, 0, Z != 0>(a, X, val);
             }
             q0 = n0; q1 = n1;
         }
@@ -797,7 +816,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
             m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
             m_gather<NREG>(a, X, idle);
             const double val = m_finish<RPW, NREG>(a, X, idle);
-            m_publish<RPW, MODE, NREG>(a, X, val);
+            m_publish<RPW, MODE, NREG, 0, Z != 0>(a, X, val);
             if (g2 >= gend) break;
             g = g2; q0 = n0; q1 = n1;
             g2 = (int)__builtin_amdgcn_readfirstlane(tk3);
@@ -851,7 +870,7 @@ __device__ __forceinline__ void m_wipe(double *w, int g, int G, int q, int r, in
 }
 
 // one phase of the fused sweep by one wave; returns the groups it finished
-template <int MODE, int RPW, int NREG, int PH>
+template <int MODE, int RPW, int NREG, int PH, int Z = 0>
 __device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, int wq, int wr, int wblk, unsigned *ticket, const bool xz, int lane, int wib, int idle, double *c_lds)
 {
     const int4 *rp = reinterpret_cast<const int4 *>(a.rec);
@@ -865,7 +884,7 @@ __device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, in
         int4 q = c_rec(rp, g, gend);
         for (; g < gend; g += W) {
             const int4 nq = c_rec(rp, g + W, gend);
-            c_group<PH>(a, c_lds + wib * LANEC_UMAX, q, g, lane, idle, xz, PH == 2);
+            c_group<PH, Z && PH == 1, Z && PH == 2>(a, c_lds + wib * LANEC_UMAX, q, g, lane, idle, xz, PH == 2);
             m_wipe<MODE>(wipe, g, gend, wq, wr, wblk, lane);
             ++done;
             q = nq;
@@ -882,9 +901,9 @@ __device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, in
             int4 n0, n1;
             m_rec(rp, g + W, gend, n0, n1);
             m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
-            m_gather<NREG>(a, X, idle, xz, PH == 2);
+            m_gather<NREG, Z && PH == 2>(a, X, idle, xz, PH == 2);
             const double val = m_finish<RPW, NREG>(a, X, idle, nullptr, nullptr, xz);
-            m_publish<RPW, MODE, NREG, PH>(a, X, val);
+            m_publish<RPW, MODE, NREG, PH, Z && PH == 1>(a, X, val);
             m_wipe<MODE>(wipe, g, gend, wq, wr, wblk, lane);      // behind the publishing stores: nobody waits for these
             ++done;
             q0 = n0; q1 = n1;
@@ -904,9 +923,9 @@ __device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, in
             unsigned tk3 = 0;
             if (g2 < gend && lane == 0) tk3 = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
-            m_gather<NREG>(a, X, idle, xz, PH == 2);
+            m_gather<NREG, Z && PH == 2>(a, X, idle, xz, PH == 2);
             const double val = m_finish<RPW, NREG>(a, X, idle, nullptr, nullptr, xz);
-            m_publish<RPW, MODE, NREG, PH>(a, X, val);
+            m_publish<RPW, MODE, NREG, PH, Z && PH == 1>(a, X, val);
             m_wipe<MODE>(wipe, g, gend, wq, wr, wblk, lane);
             ++done;
             if (g2 >= gend) break;
@@ -954,7 +973,8 @@ __device__ __forceinline__ void sym_leave(unsigned *sync, unsigned parity)
     }
 }
 
-template <int MODE, int RPW, int NREG>
+// Z = 1: the two phases run the operator's zero-iterate plans (x = 0 on entry): phase 1 stores the numerators in ph[0].w, phase 2 reads them as its b
+template <int MODE, int RPW, int NREG, int Z = 0>
 __global__ __launch_bounds__(BLK) void gs_lanem_sym_kernel(const LaneMSymArgs a)
 {
     __shared__ unsigned sh_done;
@@ -980,9 +1000,9 @@ __global__ __launch_bounds__(BLK) void gs_lanem_sym_kernel(const LaneMSymArgs a)
         LaneMArgs p1 = a.ph[0], p2 = a.ph[1];
         p1.xs = hf; p1.y = nullptr;
         p2.xold = hf;
-        const unsigned done = m_phase<MODE, RPW, NREG, 1>(p1, p2.xs, a.wq[0], a.wr[0], a.wblk[0], a.sync + 2, a.xzero != 0, lane, wib, idle, c_lds);
+        const unsigned done = m_phase<MODE, RPW, NREG, 1, Z>(p1, p2.xs, a.wq[0], a.wr[0], a.wblk[0], a.sync + 2, a.xzero != 0, lane, wib, idle, c_lds);
         sym_phase_barrier(a.sync, p1.err, &sh_done, done, (unsigned)p1.ngroups);
-        (void)m_phase<MODE, RPW, NREG, 2>(p2, hf_next, a.wq[1], a.wr[1], a.wblk[1], a.sync + 3, false, lane, wib, idle, c_lds);
+        (void)m_phase<MODE, RPW, NREG, 2, Z>(p2, hf_next, a.wq[1], a.wr[1], a.wblk[1], a.sync + 3, false, lane, wib, idle, c_lds);
     }
     sym_leave(a.sync, parity);
 }
@@ -1228,6 +1248,8 @@ int lanem_smax(const pamg_matrix_s *A, const GsSchedule *g)
     return A->nrows > 131072 ? (lanem_cluster_rows(A) ? 4 : 3) : 8;
 }
 
+static int lanem_to_device(const LaneMPlan &P, int s_max, LaneMSched **out);
+
 int build_lanem_part(pamg_matrix_s *A, GsSchedule *g)
 {
     if (g->lanem) return PAMG_OK;
@@ -1248,7 +1270,24 @@ int build_lanem_part(pamg_matrix_s *A, GsSchedule *g)
                          s_max, 1e3, P, LANEM_KMAX * 64, rpw, cluster))
         return PAMG_E_ARG;
     hAx = PlanVec<double>();
-    // nothing gained (every group closed at once: an operator the growth bound rejects): the unmerged form is the cheaper layout
+    LaneMSched *t = nullptr;
+    PAMG_TRY(lanem_to_device(P, s_max, &t));
+    if (!g->d_xold) {                                          // the snapshot of x (allocated here: sweeps may run inside a graph capture)
+        const size_t xb = ((size_t)A->nrows + 8) * sizeof(double);
+        const int st = (int)hipMalloc(&g->d_xold, xb);
+        if (st) { free_lanem_part(t); return st; }
+        t->bytes += xb;
+    }
+    g->lanem = t;
+    g->bytes += t->bytes;
+    return PAMG_OK;
+}
+
+// a finished plan -> its device arrays.  PAMG_E_ARG: nothing gained (every group closed at once: an operator the growth bound rejects) -- the
+// unmerged form is the cheaper layout
+static int lanem_to_device(const LaneMPlan &P, int s_max, LaneMSched **out)
+{
+    *out = nullptr;
     if (P.nsuper * 10 > P.nlevels * 9) return PAMG_E_ARG;
     LaneMSched *t = new (std::nothrow) LaneMSched();
     if (!t) return PAMG_E_ALLOC;
@@ -1270,15 +1309,9 @@ int build_lanem_part(pamg_matrix_s *A, GsSchedule *g)
         if (!st) st = lane_upload(&t->d_sidx, P.sidx.data(), P.sidx.size() * sizeof(unsigned short), &t->bytes);
         if (!st) st = lane_upload(&t->d_crid, P.rid.data(), P.rid.size() * sizeof(int), &t->bytes);
         if (!st) st = lane_upload(&t->d_crd, P.rdiag.data(), P.rdiag.size() * sizeof(double), &t->bytes);
-        if (!st && !g->d_xold) {
-            const size_t xb = ((size_t)A->nrows + 8) * sizeof(double);
-            st = (int)hipMalloc(&g->d_xold, xb);
-            if (!st) t->bytes += xb;
-        }
         if (st) { free_lanem_part(t); return st; }
         if (getenv("PAMG_TIMING")) fprintf(stderr, "[pamg timing]     lanem plan: cluster layout, %d rows per wave: %zu bytes uploaded\n", P.cluster, t->bytes);
-        g->lanem = t;
-        g->bytes += t->bytes;
+        *out = t;
         return PAMG_OK;
     }
     std::vector<LaneMRec> rec((size_t)P.ngroups);
@@ -1297,16 +1330,102 @@ int build_lanem_part(pamg_matrix_s *A, GsSchedule *g)
     int st = lane_upload(&t->d_rec, rec.data(), rec.size() * sizeof(LaneMRec), &t->bytes);
     if (!st) st = lane_upload(&t->d_cols, P.cols.data(), P.cols.size() * sizeof(int), &t->bytes);
     if (!st) st = lane_upload(&t->d_vals, P.vals.data(), P.vals.size() * sizeof(double), &t->bytes);
-    if (!st && !g->d_xold) {                                   // the snapshot of x (allocated here: sweeps may run inside a graph capture)
-        const size_t xb = ((size_t)A->nrows + 8) * sizeof(double);
-        st = (int)hipMalloc(&g->d_xold, xb);
-        if (!st) t->bytes += xb;
-    }
     if (st) { free_lanem_part(t); return st; }
     if (getenv("PAMG_TIMING")) fprintf(stderr, "[pamg timing]     lanem plan: %d row(s) per wave: %zu bytes uploaded\n", P.rpw, t->bytes);
-    g->lanem = t;
-    g->bytes += t->bytes;
+    *out = t;
     return PAMG_OK;
+}
+
+// =================================================================== zero-iterate plans (tune key 39)
+// A cycle enters every coarse level with x = 0 (cycle_rec), and a symmetric sweep from zero needs half the operator in each direction:
+//   forward : (D + L) y = b -- the strictly upper entries multiply zeros;
+//   backward: after the forward sweep b_r - sum_{j<r} a_rj y_j = a_rr y_r for every updated row r, so the backward half is the backward sweep of
+//             the UPPER triangle, (D + U) x = w with w_r = a_rr y_r: the numerator b_r - s_r the forward row holds before it multiplies by 1 / a_rr.
+// The planner is linear in the operator's entries: Zf = the forward plan of tril(A), Zb = the backward plan of triu(A), same layouts and gates as the
+// general plans, built from host copies of the triangles (no second device copy of the operator).  Rows without a usable diagonal keep their old
+// value; they are the only source of OLD operands in these plans.  The forward kernel stores w (LaneMArgs::w), the backward kernel runs with b = w.
+// Depth: tune key 40 (2..16), 0 = automatic -- what won the scan of the 256^3 hierarchy by more than the spread of three repetitions (0.1 - 0.2 %),
+// fused launch announced to start from zero (profiles/r09_microbench_zero_plan_scan.json; the general plans in the same session: level 1 2.92 ms, level 2 0.924):
+//   level 1 (2.03 M rows, cluster layout, 512 workgroups): s = 4 2.556 ms, 5 2.298, 6 2.269, 8 2.804 (2.448 with 768 workgroups; s = 4 / 5 / 6 lose 2 - 5 %
+//            with 768) -- a triangular row at s = 6 carries 62.5 operands, 30 unique per row: less than the full plan at s = 4 (78.6 / 46.2), with 374
+//            instead of 561 hand-offs per direction;
+//   level 2 (44.6 K rows, one row per wave): s = 8 0.831 ms, 12 0.811, 16 0.806 (142 / 128 / 123 super-levels; the full plan closes 217 at the
+//            512-operand cap, and from s = 12 on most of these groups close there too).
+int lanem_zero_smax(const pamg_matrix_s *A)
+{
+    if (A->zero_merge >= 2) return A->zero_merge;
+    static const int env = [] { const char *e = getenv("PAMG_ZERO_MERGE"); return e ? atoi(e) : 0; }();
+    if (env >= 2) return env;
+    return A->nrows > 131072 ? 6 : 16;
+}
+
+int build_zero_plan(pamg_matrix_s *A, int dir)
+{
+    if (dir < 0 || dir > 1 || A->zplan[dir]) return PAMG_OK;
+    if (A->dtype != PAMG_F64 || A->R != 1 || A->nrows < 2 || A->nrows != A->ncols || !A->d_Ax) return PAMG_E_ARG;
+    PhaseTimer pt_(dir ? "build_zero_plan (backward, triu)" : "build_zero_plan (forward, tril)", A->nnz);
+    const int n = (int)A->nrows;
+    PlanVec<double> hAx;
+    hAx.resize((size_t)A->nnz + 1);
+    if (A->nnz) PAMG_HIP(hipMemcpy(hAx.data(), A->d_Ax, (size_t)A->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    // the triangle with its diagonal, entries in storage order
+    const int *Ap = A->h_Ap.data(), *Aj = A->h_Aj.data();
+    std::vector<int> Tp((size_t)n + 1, 0);
+    lane_parallel(n, [&](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            int c = 0;
+            for (int p = Ap[i]; p < Ap[i + 1]; ++p) c += dir ? (Aj[p] >= (int)i) : (Aj[p] <= (int)i);
+            Tp[(size_t)i + 1] = c;
+        }
+    });
+    for (int i = 0; i < n; ++i) Tp[(size_t)i + 1] += Tp[(size_t)i];
+    PlanVec<int> Tj;
+    PlanVec<double> Tx;
+    Tj.resize((size_t)Tp[(size_t)n] + 1);
+    Tx.resize((size_t)Tp[(size_t)n] + 1);
+    lane_parallel(n, [&](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            int q = Tp[(size_t)i];
+            for (int p = Ap[i]; p < Ap[i + 1]; ++p)
+                if (dir ? (Aj[p] >= (int)i) : (Aj[p] <= (int)i)) { Tj[(size_t)q] = Aj[p]; Tx[(size_t)q] = hAx[(size_t)p]; ++q; }
+        }
+    });
+    hAx = PlanVec<double>();
+    std::vector<int> vis, lvl;
+    int m = 0, nl = 0;
+    if (sweep_levels(n, Tp.data(), Tj.data(), dir ? n - 1 : 0, dir ? -1 : n, dir ? -1 : 1, vis, lvl, m, nl) || m != n || nl < 8) return PAMG_E_ARG;
+    const int s_max = lanem_zero_smax(A);
+    const int rpw = A->lanem_rpw ? A->lanem_rpw : (A->nrows > 131072 ? 2 : 1);
+    LaneMPlan P;
+    if (build_lanem_plan(n, Tp.data(), Tj.data(), Tx.data(), dir ? n - 1 : 0, dir ? -1 : 1, m, nl, vis, lvl, s_max, 1e3, P, LANEM_KMAX * 64, rpw, lanem_cluster_rows(A)))
+        return PAMG_E_ARG;
+    LaneMSched *t = nullptr;
+    PAMG_TRY(lanem_to_device(P, s_max, &t));
+    A->zplan[dir] = t;
+    return PAMG_OK;
+}
+
+void free_zero_plans(pamg_matrix_s *A)
+{
+    for (int d = 0; d < 2; ++d) { free_lanem_part(A->zplan[d]); A->zplan[d] = nullptr; }
+    hipFree(A->d_zw);
+    A->d_zw = nullptr;
+}
+
+size_t zero_plan_bytes(const pamg_matrix_s *A)
+{
+    size_t b = A->d_zw ? ((size_t)A->nrows + 8) * sizeof(double) : 0;
+    for (int d = 0; d < 2; ++d) if (A->zplan[d]) b += A->zplan[d]->bytes;
+    return b;
+}
+
+// both plans in the layout of the general plans of the two schedules, and the numerator vector
+bool zero_plans_ready(const pamg_matrix_s *A, const GsSchedule *gf, const GsSchedule *gb)
+{
+    const LaneMSched *zf = A->zplan[0], *zb = A->zplan[1];
+    if (A->zero_plans == 1 || !zf || !zb || !A->d_zw || !gf || !gb || !gf->lanem || !gb->lanem) return false;
+    return zf->rpw == zb->rpw && zf->cluster == zb->cluster && zf->rpw == gf->lanem->rpw && zf->cluster == gf->lanem->cluster &&
+           zb->rpw == gb->lanem->rpw && zb->cluster == gb->lanem->cluster && zf->ngroups >= 1 && zb->ngroups >= 1;
 }
 
 // the layout-dependent operands of a launch
@@ -1317,15 +1436,16 @@ static void lanem_layout_args(const LaneMSched *t, LaneMArgs &a)
     a.sidx = t->d_sidx; a.crid = t->d_crid; a.crd = t->d_crd; a.crows = t->cluster;
 }
 
-int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStream_t s)
+// t: the schedule's own plan, or a zero-iterate plan of the operator run on the schedule's buffers (w: where Zf stores its numerators)
+static int lanem_launch_plan(pamg_matrix_s *A, GsSchedule *g, LaneMSched *t, void *x, const void *b, double *w, hipStream_t s)
 {
-    LaneMSched *t = g->lanem;
     if (!t || !g->d_xold) return PAMG_E_STATE;
     const int64_t n = A->nrows;
     LaneMArgs a;
     lanem_layout_args(t, a);
     a.use_gate = (A->lane_flags & 1) ? 1 : 0;
     a.xold = (const double *)g->d_xold; a.y = (double *)x; a.xs = (double *)g->d_xs; a.b = (const double *)b;
+    a.w = w;
     a.err = g->d_sync + 1; a.ticket = g->d_sync + 20;
     a.ngroups = (int)t->ngroups;
     a.nidle = (int)std::max<int64_t>(1, std::min<int64_t>(n, 1 << 20));
@@ -1346,6 +1466,11 @@ int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStr
                   : t->rpw == 2 ? (xcd ? (const void *)gs_lanem_kernel<1, 2, 4> : (const void *)gs_lanem_kernel<0, 2, 4>)
                   : all_regs    ? (xcd ? (const void *)gs_lanem_kernel<1, 1, 8> : (const void *)gs_lanem_kernel<0, 1, 8>)
                                 : (xcd ? (const void *)gs_lanem_kernel<1, 1, 2> : (const void *)gs_lanem_kernel<0, 1, 2>);
+    if (w)
+        k = t->cluster  ? (const void *)gs_lanem_kernel<0, 0, 8, 1>
+          : t->rpw == 2 ? (xcd ? (const void *)gs_lanem_kernel<1, 2, 4, 1> : (const void *)gs_lanem_kernel<0, 2, 4, 1>)
+          : all_regs    ? (xcd ? (const void *)gs_lanem_kernel<1, 1, 8, 1> : (const void *)gs_lanem_kernel<0, 1, 8, 1>)
+                        : (xcd ? (const void *)gs_lanem_kernel<1, 1, 2, 1> : (const void *)gs_lanem_kernel<0, 1, 2, 1>);
     static thread_local int cus = 0;
     if (!cus) cus = device_cus_lane();
     if (!(t->cap > 0 && t->cap_kernel == k)) {
@@ -1379,6 +1504,19 @@ int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStr
     return PAMG_OK;
 }
 
+int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStream_t s) { return lanem_launch_plan(A, g, g->lanem, x, b, nullptr, s); }
+
+// the symmetric sweep from x = 0 as two launches on the zero-iterate plans (tune key 37 = 0, or where the fused kernel does not apply): what the
+// fused launch computes, bit for bit -- the same plans, the same row sums, w across the kernel boundary
+int lanem_zero_pair_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, hipStream_t s)
+{
+    if (!zero_plans_ready(A, gf, gb)) return PAMG_E_UNSUPPORTED;
+    PAMG_TRY(lanem_launch_plan(A, gf, A->zplan[0], x, b, (double *)A->d_zw, s));
+    PAMG_TRY(lanem_launch_plan(A, gb, A->zplan[1], x, A->d_zw, nullptr, s));
+    A->zero_plan_launches++;
+    return PAMG_OK;
+}
+
 int sym_fill_sentinels(void *p, int64_t n)
 {
     if (n <= 0) return PAMG_OK;
@@ -1395,18 +1533,22 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
 {
     LaneMSched *tf = gf->lanem, *tb = gb->lanem;
     if (!tf || !tb || !A->d_sym_hf[0] || !A->d_sym_hf[1] || !A->d_sym_hb || !A->d_sym_sync) return PAMG_E_STATE;
+    // x = 0 and the operator holds its zero-iterate plans: phase 1 runs Zf and stores the numerators, phase 2 runs Zb on them
+    const bool zero = x_zero && zero_plans_ready(A, gf, gb);
+    if (zero) { tf = A->zplan[0]; tb = A->zplan[1]; }
     const int64_t n = A->nrows;
     auto one_xcd = [&](const GsSchedule *g) { return !g->lanem->cluster && (A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= 8192)); };
     const bool xcd = one_xcd(gf);
     if (xcd != one_xcd(gb) || tf->rpw != tb->rpw || tf->cluster != tb->cluster || tf->ngroups < 1 || tb->ngroups < 1) return PAMG_E_UNSUPPORTED;
     LaneMSymArgs a;
-    GsSchedule *gs2[2] = {gf, gb};
+    LaneMSched *ts2[2] = {tf, tb};
     for (int p = 0; p < 2; ++p) {
-        LaneMSched *t = gs2[p]->lanem;
+        LaneMSched *t = ts2[p];
         LaneMArgs &q = a.ph[p];
         lanem_layout_args(t, q);
         q.use_gate = (A->lane_flags & 1) ? 1 : 0;
         q.b = (const double *)b;
+        q.w = nullptr;
         q.err = gf->d_sync + 1; q.ticket = nullptr;
         q.ngroups = (int)t->ngroups;
         q.nidle = (int)std::max<int64_t>(1, std::min<int64_t>(n, 1 << 20));
@@ -1417,6 +1559,7 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
     }
     a.ph[0].xold = (const double *)x; a.ph[0].y = nullptr;     a.ph[0].xs = nullptr;                     // (xs / xold of the parity's H_f: set by the kernel)
     a.ph[1].xold = nullptr;           a.ph[1].y = (double *)x; a.ph[1].xs = (double *)A->d_sym_hb;
+    if (zero) { a.ph[0].w = (double *)A->d_zw; a.ph[1].b = (const double *)A->d_zw; }
     a.hf[0] = (double *)A->d_sym_hf[0]; a.hf[1] = (double *)A->d_sym_hf[1];
     a.sync = A->d_sym_sync;
     a.xzero = x_zero ? 1 : 0;
@@ -1426,18 +1569,25 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
                   : tf->rpw == 2 ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4> : (const void *)gs_lanem_sym_kernel<0, 2, 4>)
                   : all_regs     ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 8> : (const void *)gs_lanem_sym_kernel<0, 1, 8>)
                                  : (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 2> : (const void *)gs_lanem_sym_kernel<0, 1, 2>);
+    if (zero)
+        k = tf->cluster  ? (const void *)gs_lanem_sym_kernel<0, 0, 8, 1>
+          : tf->rpw == 2 ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4, 1> : (const void *)gs_lanem_sym_kernel<0, 2, 4, 1>)
+          : all_regs     ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 8, 1> : (const void *)gs_lanem_sym_kernel<0, 1, 8, 1>)
+                         : (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 2, 1> : (const void *)gs_lanem_sym_kernel<0, 1, 2, 1>);
     static thread_local int cus = 0;
     if (!cus) cus = device_cus_lane();
-    if (!(A->sym_cap > 0 && A->sym_cap_kernel == k)) {
+    int &kcap = zero ? A->zsym_cap : A->sym_cap;               // (the two kernels alternate within a cycle: one cached answer each)
+    const void *&kcap_kernel = zero ? A->zsym_cap_kernel : A->sym_cap_kernel;
+    if (!(kcap > 0 && kcap_kernel == k)) {
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess) nb = 2;
-        A->sym_cap = std::max(1, std::min(nb - 1, 8));          // every workgroup must be resident (the query can over-report by one)
-        A->sym_cap_kernel = k;
+        kcap = std::max(1, std::min(nb - 1, 8));                // every workgroup must be resident (the query can over-report by one)
+        kcap_kernel = k;
     }
-    const int cap = A->sym_cap;
+    const int cap = kcap;
     int G = 1;
     for (int p = 0; p < 2; ++p) {                               // the directional rule (lanem_launch), the larger wish of the two
-        const LaneMSched *t = gs2[p]->lanem;
+        const LaneMSched *t = ts2[p];
         const int per_level = (int)((t->ngroups + t->nsuper - 1) / std::max(1, t->nsuper));
         const int64_t want_waves = std::max<int64_t>(128, ((int64_t)A->lanem_ahead10 * per_level + 9) / 10);
         int Gp = (int)std::min<int64_t>((want_waves + LANE_WPB - 1) / LANE_WPB, (int64_t)std::min(cap, (t->rpw == 2 || t->cluster) ? 2 : 3) * cus);
@@ -1449,8 +1599,11 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
     void *args[] = {(void *)&a};
     PAMG_HIP(hipLaunchKernel(k, dim3(G), dim3(BLK), args, 0, s));
     A->sym_form = xcd ? 3 : 1; A->sym_grid = G;
+    if (zero) tf->last_grid = tb->last_grid = G;               // (diagnostics: the grid of the zero-iterate launch, which differs from the general one's)
+    else A->sym_general_grid = G;
     A->sym_launches++;
     if (x_zero) A->sym_zero_launches++;
+    if (zero) A->zero_plan_launches++;
     return PAMG_OK;
 }
 
@@ -1459,12 +1612,13 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
 // info[12..19] = rows per wave of the cluster layout (0: the row / pair layout), groups (waves' work items), padded slots (64 x units), units of unique
 //               operands, unique early / old / b operands and distinct 64-byte lines of the unique early operands, each summed over the groups (the
 //               row / pair layouts share nothing: their unique operands ARE info[4..6], lines are not counted)
-int lanem_info(const GsSchedule *g, int64_t *info, double *growth)
+int lanem_info(const GsSchedule *g, int64_t *info, double *growth) { return lanem_plan_info(g ? g->lanem : nullptr, info, growth); }
+
+int lanem_plan_info(const LaneMSched *t, int64_t *info, double *growth)
 {
     for (int i = 0; i < 20; ++i) info[i] = 0;
     if (growth) *growth = 0.0;
-    if (!g || !g->lanem) return PAMG_OK;
-    const LaneMSched *t = g->lanem;
+    if (!t) return PAMG_OK;
     info[0] = t->nsuper; info[1] = t->nlevels; info[2] = t->nrows; info[3] = t->n_units; info[4] = t->n_early; info[5] = t->n_old; info[6] = t->n_b;
     info[7] = t->max_len; info[8] = t->s_max; info[9] = t->closed_by_length; info[10] = t->closed_by_growth; info[11] = t->last_grid;
     info[12] = t->cluster; info[13] = t->ngroups; info[14] = t->n_units * 64; info[15] = t->n_uunits;

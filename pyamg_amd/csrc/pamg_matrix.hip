@@ -898,6 +898,7 @@ void matrix_drop_schedules(pamg_matrix_s *A)
         free_schedule(g);
         if (l) free_line_schedule(l);
     }
+    matrix_drop_zero_plans(A);                                 // they hold the operator's values too
     matrix_drop_point_twin(A);
 }
 
@@ -1454,7 +1455,92 @@ int gs_sweep_symmetric(pamg_matrix_s *A, void *x, const void *b, bool x_zero, hi
         PAMG_TRY(ensure_sym_parts(A));
         if (!A->d_sym_hf[0]) return PAMG_OK;
     }
+    if (form == 1 && x_zero && A->zero_plans == 2 && !A->zplan[0] && !A->zplan[1]) {
+        // a bare operator with tune key 39 = 2: its first sweep from zero builds the zero-iterate plans (a solver built them with its schedules)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        PAMG_HIP(hipStreamIsCapturing(s, &cs));
+        if (cs == hipStreamCaptureStatusNone) {
+            PAMG_TRY(ensure_zero_parts(A, true));
+            if (!zero_plans_ready(A, gf, gb)) A->zero_plans = 1;
+        }
+    }
     const int st = form == 2 ? line_sym_launch(A, gf, gb, x, b, s) : lanem_sym_launch(A, gf, gb, x, b, x_zero, s);
+    if (st == PAMG_E_UNSUPPORTED) return PAMG_OK;
+    if (st == PAMG_OK) *ran = true;
+    return st;
+}
+
+// ---- zero-iterate plans (pamg_lane.hip, tune key 39).  The plans are used where a symmetric sweep is announced to start from x = 0 and BOTH schedules
+// take the merged lane form; whatever is missing is built here when `build` says so (a solver, per level; a bare operator with key = 2 at its first
+// such sweep), and plans that cannot be used are dropped.
+void matrix_drop_zero_plans(pamg_matrix_s *A)
+{
+    if (!A || (!A->zplan[0] && !A->zplan[1] && !A->d_zw)) return;
+    free_zero_plans(A);
+    std::lock_guard<std::mutex> lk(g_sched_mu);
+    A->bytes -= std::min(A->bytes, A->zero_bytes);
+    A->zero_bytes = 0;
+}
+
+static bool zero_form_of(pamg_matrix_s *A, GsSchedule **pf, GsSchedule **pb)
+{
+    if (A->zero_plans == 1 || A->R != 1 || A->dtype != PAMG_F64 || A->gs_order != 1 || A->gs_mode != 0 || A->gs_prof || A->nrows < 2) return false;
+    const int n = (int)A->nrows;
+    GsSchedule *gf = nullptr, *gb = nullptr;
+    if (get_schedule(A, 0, n, 1, &gf) != PAMG_OK || get_schedule(A, n - 1, -1, -1, &gb) != PAMG_OK) return false;
+    if (ensure_parts(A, gf) != PAMG_OK || ensure_parts(A, gb) != PAMG_OK) return false;
+    if (gf->nrows != A->nrows || gb->nrows != A->nrows) return false;
+    if (want_lines(A, gf) || want_lines(A, gb)) return false;
+    if (!(want_lanes(A, gf) && want_lanes(A, gb) && gf->lanem && gb->lanem)) return false;
+    *pf = gf; *pb = gb;
+    return true;
+}
+
+int ensure_zero_parts(pamg_matrix_s *A, bool build)
+{
+    if (!A) return PAMG_OK;
+    GsSchedule *gf = nullptr, *gb = nullptr;
+    if (!zero_form_of(A, &gf, &gb)) { matrix_drop_zero_plans(A); return PAMG_OK; }
+    if (A->d_zw && A->zplan[0] && A->zplan[1]) return PAMG_OK;
+    if (build && (!A->zplan[0] || !A->zplan[1])) {
+        int st[2] = {PAMG_OK, PAMG_OK};
+        int dev = 0;
+        PAMG_HIP(hipGetDevice(&dev));
+        std::thread other([&] { st[1] = (int)hipSetDevice(dev); if (!st[1]) st[1] = build_zero_plan(A, 1); });
+        st[0] = build_zero_plan(A, 0);
+        other.join();
+        for (int d = 0; d < 2; ++d) if (st[d] != PAMG_OK && st[d] != PAMG_E_ARG) { matrix_drop_zero_plans(A); return st[d]; }
+    }
+    if (!A->zplan[0] || !A->zplan[1]) { matrix_drop_zero_plans(A); return PAMG_OK; }       // one direction does not fit the form: the general plans keep the sweep
+    if (!A->d_zw) {
+        const size_t vb = ((size_t)A->nrows + 8) * sizeof(double);
+        PAMG_HIP(hipMalloc(&A->d_zw, vb));
+        PAMG_HIP(hipMemset(A->d_zw, 0, vb));
+    }
+    if (!zero_plans_ready(A, gf, gb)) { matrix_drop_zero_plans(A); return PAMG_OK; }
+    std::lock_guard<std::mutex> lk(g_sched_mu);
+    A->bytes -= std::min(A->bytes, A->zero_bytes);
+    A->zero_bytes = zero_plan_bytes(A);
+    A->bytes += A->zero_bytes;
+    return PAMG_OK;
+}
+
+int gs_sweep_zero_pair(pamg_matrix_s *A, void *x, const void *b, hipStream_t s, bool *ran)
+{
+    *ran = false;
+    if (A->zero_plans == 1 || (A->zero_plans == 0 && !A->zplan[0])) return PAMG_OK;
+    GsSchedule *gf = nullptr, *gb = nullptr;
+    if (!zero_form_of(A, &gf, &gb)) return PAMG_OK;
+    if (!zero_plans_ready(A, gf, gb)) {
+        if (A->zero_plans != 2 || A->zplan[0] || A->zplan[1]) return PAMG_OK;
+        // a bare operator with key = 2: its first sweep from zero builds the plans -- allocations, so never inside a graph capture
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        PAMG_HIP(hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone) return PAMG_OK;
+        PAMG_TRY(ensure_zero_parts(A, true));
+        if (!zero_plans_ready(A, gf, gb)) { A->zero_plans = 1; return PAMG_OK; }      // the form does not fit: not asked again
+    }
+    const int st = lanem_zero_pair_launch(A, gf, gb, x, b, s);
     if (st == PAMG_E_UNSUPPORTED) return PAMG_OK;
     if (st == PAMG_OK) *ran = true;
     return st;
@@ -1969,6 +2055,7 @@ int pamg_matrix_destroy(pamg_matrix_t A)
     for (int k = 0; k < 4; ++k) free_schedule(A->gs[k]);
     for (int k = 0; k < 4; ++k) pamg::free_line_schedule(A->ls[k]);
     hipFree(A->d_sym_hf[0]); hipFree(A->d_sym_hf[1]); hipFree(A->d_sym_hb); hipFree(A->d_sym_sync);
+    pamg::free_zero_plans(A);
     if (A->point_twin) pamg_matrix_destroy(A->point_twin);
     delete A;
     return PAMG_OK;
@@ -2065,6 +2152,8 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
         case 36: if (value < 0 || value > 98304) return PAMG_E_ARG; A->lds_pad = value & ~15; return PAMG_OK;
         case 34: if (value < 1 || value > 400) return PAMG_E_ARG; A->lanem_ahead10 = value; matrix_drop_point_twin(A); return PAMG_OK;
         case 37: if (value < 0 || value > 1) return PAMG_E_ARG; A->sym_fused = value; return PAMG_OK;      // read at launch time; refused above while a solver's graphs hold the choice
+        case 39: if (value < 0 || value > 2) return PAMG_E_ARG; A->zero_plans = value; if (value == 1) matrix_drop_zero_plans(A); return PAMG_OK;
+        case 40: if (value != 0 && (value < 2 || value > 16)) return PAMG_E_ARG; A->zero_merge = value; matrix_drop_zero_plans(A); return PAMG_OK;
         case 30:                                               // 2: also where the estimate favours the lane form
             if (value < 0 || value > 2) return PAMG_E_ARG;
             A->line_scan = value;
@@ -2078,6 +2167,7 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
     }
     if (key == 25 || key == 33 || key == 35 || key == 38) {         // lane geometry / merging: drop the lane parts only (and the point twin, which copied the keys)
         matrix_drop_point_twin(A);
+        matrix_drop_zero_plans(A);                                  // (they follow the layout of the merged parts)
         for (int k = 0; k < 4; ++k) {
             GsSchedule *g = A->gs[k];
             if (g) g->lane_unfit = false;
@@ -2099,6 +2189,7 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
         return PAMG_OK;
     }
     for (int k = 0; k < 4; ++k) { if (A->gs[k]) A->bytes -= A->gs[k]->bytes; free_schedule(A->gs[k]); A->gs[k] = nullptr; }
+    matrix_drop_zero_plans(A);
     matrix_drop_point_twin(A);                          // it sweeps for the schedules just dropped
     return replan(A);
 }
@@ -2270,7 +2361,8 @@ int pamg_matrix_kz_info(pamg_matrix_t A, int which, int64_t info[8])
 
 int pamg_matrix_lanem_info(pamg_matrix_t A, int which, int64_t info[20], double *growth)
 {
-    if (!A || !info || which < 0 || which > 3) return PAMG_E_ARG;
+    if (!A || !info || which < 0 || which > 5) return PAMG_E_ARG;
+    if (which >= 4) return pamg::lanem_plan_info(A->zplan[which - 4], info, growth);      // 4 / 5: the zero-iterate plans Zf / Zb (tune key 39)
     return pamg::lanem_info(A->gs[which], info, growth);
 }
 
@@ -2278,8 +2370,9 @@ int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[8])
 {
     if (!A || !info) return PAMG_E_ARG;
     for (int k = 0; k < 8; ++k) info[k] = 0;
-    info[0] = A->sym_launches; info[1] = A->sym_zero_launches; info[2] = A->sym_form; info[3] = A->sym_grid; info[4] = A->sym_fused;
+    info[0] = A->sym_launches; info[1] = A->sym_zero_launches; info[2] = A->sym_form; info[3] = A->sym_general_grid ? A->sym_general_grid : A->sym_grid; info[4] = A->sym_fused;
     info[5] = -1; info[6] = -1;
+    info[7] = A->zero_plan_launches;
     if (!A->d_sym_hf[0]) return PAMG_OK;
     PAMG_HIP(hipDeviceSynchronize());
     // the invariant between launches: every entry of the forward hand-off buffer the NEXT launch publishes in a sentinel, the counters zero

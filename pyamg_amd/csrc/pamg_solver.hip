@@ -113,6 +113,9 @@ int gs_apply(pamg_matrix_s *A, void *x, const void *b, int sweep, double omega, 
             bool ran = false;
             PAMG_TRY(gs_sweep_symmetric(A, x, b, x_zero && it == 0, s, &ran));
             if (ran) continue;
+            // two launches: from x = 0 on the operator's zero-iterate plans where it holds them (what the fused launch runs: the same bits)
+            if (x_zero && it == 0) PAMG_TRY(gs_sweep_zero_pair(A, x, b, s, &ran));
+            if (ran) continue;
             PAMG_TRY(one(PAMG_FORWARD, 1.0));
             PAMG_TRY(one(PAMG_BACKWARD, 1.0));
         }
@@ -296,7 +299,7 @@ int apply_smoother(pamg_solver_s *S, Level &L, const Smoother &sm, bool x_zero, 
 }
 
 void drop_graphs(pamg_solver_s *S);
-int prebuild_schedules(Level &L, const Smoother &sm);
+int prebuild_schedules(Level &L, const Smoother &sm, bool zero = false);
 
 // after a synchronising entry point: did any persistent sweep give up waiting?
 int check_sweeps(pamg_solver_s *S)
@@ -341,6 +344,7 @@ int fall_back_to_level_launches(pamg_solver_s *S)
         L.A->gs_mode = 1;
         L.A->tile_default = false;
         PAMG_TRY(sym_reset(L.A));                             // (the fused symmetric sweep declines from here on: gs_mode 1)
+        matrix_drop_zero_plans(L.A);                          // (so do the zero-iterate plans: every sweep takes the general path)
         for (Smoother *sm : {&L.pre, &L.post}) {
             // kz_lane_launch is gated on gs_mode == 0 of the operator the sweep runs on (pamg_matrix.hip: kaczmarz_sweep)
             if (sm->At) sm->At->gs_mode = 1;
@@ -486,7 +490,18 @@ static bool sor_takes_omega(const pamg_matrix_s *A, const Smoother &sm)
     return sm.kind == PAMG_SMOOTH_SOR && A->R == 1 && A->flavour != PAMG_BSR && sm.sweep != PAMG_SYMMETRIC && sm.omega != 1.0;
 }
 
-int prebuild_schedules(Level &L, const Smoother &sm)
+// Zero-iterate plans (tune key 39) for the pre-smoother of level l: a cycle enters every level below the finest with x = 0 (cycle_rec), so a
+// symmetric Gauss-Seidel pre-smoother there sweeps half the operator per direction.  The finest level only on request (key = 2): its pre-smoother
+// starts from zero in the preconditioning cycles alone.
+static bool zero_plans_wanted(const pamg_matrix_s *A, const Smoother &pre, const Smoother &post, int l)
+{
+    if (A->zero_plans == 1 || (l == 0 && A->zero_plans != 2)) return false;
+    if (pre.kind != PAMG_SMOOTH_GS || pre.sweep != PAMG_SYMMETRIC || pre.iterations < 1) return false;
+    if (sor_takes_omega(A, post)) return false;              // the operator keeps the unmerged layout
+    return A->R == 1 && A->dtype == PAMG_F64 && A->gs_order == 1 && A->gs_mode == 0 && A->nrows >= 2;
+}
+
+int prebuild_schedules(Level &L, const Smoother &sm, bool zero)
 {
     if (sm.kind == PAMG_SMOOTH_GS_NE || sm.kind == PAMG_SMOOTH_GS_NR) {
         // the Kaczmarz line schedules allocate: build them here, never inside a graph capture
@@ -513,15 +528,30 @@ int prebuild_schedules(Level &L, const Smoother &sm)
     }
     // the fused symmetric sweep's hand-off buffers (allocated here: the first cycle may be a graph capture)
     if (sm.sweep == PAMG_SYMMETRIC && sm.kind != PAMG_SMOOTH_BLOCK_GS) PAMG_TRY(ensure_sym_parts(L.A));
+    // the zero-iterate plans (found built where the schedule jobs ran) and their numerator vector: allocations, so here and never inside a capture
+    if (zero) PAMG_TRY(ensure_zero_parts(L.A, true));
     return PAMG_OK;
 }
 
 // the order-exact schedules of all levels and both directions, built side by side on host threads (dependency analysis,
 // tile planning and packing are host work: a 256^3 hierarchy spends seconds there).  Jobs are (operator, sweep bounds);
 // duplicates (pre- and post-smoother of a level share theirs) are dropped.
-struct SchedJob { pamg_matrix_s *A; int r0, r1, rs; int st; bool block_gs; };
+struct SchedJob { pamg_matrix_s *A; int r0, r1, rs; int st; bool block_gs; int zero_dir; };      // zero_dir: 0 / 1 = the job goes on with that zero-iterate plan, -1 = none
 
-void sched_jobs_of(Level &L, const Smoother &sm, std::vector<SchedJob> &jobs)
+// a schedule job's second half: the zero-iterate plan of its direction, on the thread that has just finished the general plan (the plans of the
+// other levels and directions are being built beside it)
+static int sched_job_run(SchedJob &j)
+{
+    PAMG_TRY(ensure_schedule(j.A, j.r0, j.r1, j.rs, j.block_gs));
+    if (j.zero_dir < 0) return PAMG_OK;
+    GsSchedule *g = nullptr;
+    PAMG_TRY(get_schedule(j.A, j.r0, j.r1, j.rs, &g));
+    if (!g || !g->lanem) return PAMG_OK;
+    const int st = build_zero_plan(j.A, j.zero_dir);
+    return st == PAMG_E_ARG ? PAMG_OK : st;                  // does not fit the form: the general plans keep the sweep
+}
+
+void sched_jobs_of(Level &L, const Smoother &sm, std::vector<SchedJob> &jobs, bool zero = false)
 {
     const bool gs = sm.kind == PAMG_SMOOTH_GS || sm.kind == PAMG_SMOOTH_SOR || sm.kind == PAMG_SMOOTH_BLOCK_GS;
     if (!gs || L.A->nrows == 0) return;
@@ -529,7 +559,7 @@ void sched_jobs_of(Level &L, const Smoother &sm, std::vector<SchedJob> &jobs)
         int r0, r1, rs;
         if (sweep_bounds(L.A, dir, r0, r1, rs)) return;
         for (const SchedJob &j : jobs) if (j.A == L.A && j.r0 == r0 && j.r1 == r1 && j.rs == rs && j.block_gs == (sm.kind == PAMG_SMOOTH_BLOCK_GS)) return;
-        jobs.push_back({L.A, r0, r1, rs, PAMG_OK, sm.kind == PAMG_SMOOTH_BLOCK_GS});
+        jobs.push_back({L.A, r0, r1, rs, PAMG_OK, sm.kind == PAMG_SMOOTH_BLOCK_GS, zero ? (dir == PAMG_BACKWARD ? 1 : 0) : -1});
     };
     if (sm.sweep == PAMG_FORWARD || sm.sweep == PAMG_SYMMETRIC) add(PAMG_FORWARD);
     if (sm.sweep == PAMG_BACKWARD || sm.sweep == PAMG_SYMMETRIC) add(PAMG_BACKWARD);
@@ -543,14 +573,14 @@ int run_sched_jobs(std::vector<SchedJob> &jobs)
     const char *e = getenv("PAMG_SCHED_THREADS");
     const bool serial = (e && *e == '1' && !e[1]) || jobs.size() == 1;
     if (serial) {
-        for (SchedJob &j : jobs) PAMG_TRY(ensure_schedule(j.A, j.r0, j.r1, j.rs, j.block_gs));
+        for (SchedJob &j : jobs) PAMG_TRY(sched_job_run(j));
         return PAMG_OK;
     }
     std::vector<std::thread> th;
     for (SchedJob &j : jobs)
         th.emplace_back([&j, dev] {
             j.st = (int)hipSetDevice(dev);
-            if (!j.st) j.st = ensure_schedule(j.A, j.r0, j.r1, j.rs, j.block_gs);
+            if (!j.st) j.st = sched_job_run(j);
         });
     for (auto &t : th) t.join();
     for (const SchedJob &j : jobs) if (j.st) return j.st;
@@ -1600,12 +1630,16 @@ int pamg_solver_finalize(pamg_solver_t S)
     }
     {
         std::vector<SchedJob> jobs;
-        for (int l = 0; l < nsm; ++l) { sched_jobs_of(S->levels[l], S->levels[l].pre, jobs); sched_jobs_of(S->levels[l], S->levels[l].post, jobs); }
+        for (int l = 0; l < nsm; ++l) {
+            Level &L = S->levels[l];
+            sched_jobs_of(L, L.pre, jobs, zero_plans_wanted(L.A, L.pre, L.post, l));
+            sched_jobs_of(L, L.post, jobs);
+        }
         PAMG_TRY(run_sched_jobs(jobs));
     }
     for (int l = 0; l < nsm; ++l) {            // whatever the jobs did not cover (Kaczmarz line schedules); the rest is found built
         Level &L = S->levels[l];
-        PAMG_TRY(prebuild_schedules(L, L.pre));
+        PAMG_TRY(prebuild_schedules(L, L.pre, zero_plans_wanted(L.A, L.pre, L.post, l)));
         PAMG_TRY(prebuild_schedules(L, L.post));
     }
     PAMG_TRY(dalloc(S, (void **)&S->d_slot, 16 * sizeof(double)));

@@ -89,6 +89,16 @@ def kernel_map(dml, smoother_kind):
                                     "bytes_streamed": int(sum(_lanem_bytes(l_, n, vb) for l_ in lm)),
                                     "format": _lanem_format(lm[0]),
                                     "dependency_levels": int(lm[0]["super_levels"] + lm[1]["super_levels"])})
+                        if sym.get("zero_plan_launches"):
+                            # the pre-smoothing launch of a level the cycle enters with x = 0: the zero-iterate plans (tune key 39) in the kernel's
+                            # `zero` instantiation -- the forward plan of tril(A), the backward plan of triu(A), and the numerator vector (written, read)
+                            zm = [A.lanem_info(w) for w in (4, 5)]
+                            out.append({"family": "gs_lanem_zero", "grid": int(zm[0]["launch_grid"]), "level": i, "op": "A",
+                                        "what": f"symmetric GS sweep from x = 0, one launch (zero-iterate plans: {zm[0]['super_levels']} + {zm[1]['super_levels']} super-levels of <= {zm[0]['s_max']} dependency levels)",
+                                        "rows": int(n), "nnz": int(nnz), "bytes_alg": int(2 * alg),
+                                        "bytes_streamed": int(sum(_lanem_bytes(l_, n, vb) for l_ in zm) + 2 * vb * n),
+                                        "format": _lanem_format(zm[0]),
+                                        "dependency_levels": int(zm[0]["super_levels"] + zm[1]["super_levels"])})
                 for which, dirn in directions:
                     lane, tile, line, lanem = A.lane_info(which), A.tile_info(which), A.line_info(which), A.lanem_info(which)
                     if lanem["rows"] and lanem["launch_grid"]:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Fused symmetric Gauss-Seidel sweeps on level 1 of the 256^3 SA hierarchy, nothing else: the command to run under rocprofv3 --pmc (kernel trace
-only) with a tune dict as JSON, e.g. '{"lanem_cluster": 1}' (profiles/r08_pmc_lanem_cluster_level1.json).  Not product code."""
+only) with a tune dict as JSON, e.g. '{"lanem_cluster": 1}' (profiles/r08_pmc_lanem_cluster_level1.json); "x_zero": 1 in the dict announces x = 0 to every
+sweep, as a cycle's pre-smoothing does (with "zero_plans": 2 the launches run the zero-iterate plans: profiles/r09_pmc_zero_plan_level1.json).  Not product code."""
 import sys, json
 from pathlib import Path
 import numpy as np
@@ -13,6 +14,7 @@ from pyamg_amd.hierarchy import sparse_op
 from pyamg_amd.multilevel import DeviceMatrix
 
 tune = json.loads(sys.argv[1]) if len(sys.argv) > 1 else {}
+x_zero = bool(tune.pop("x_zero", 0))
 cache = Path("/tmp/pamg_level1_256.npz")
 if not cache.exists():
     import oracle.refimport  # noqa
@@ -34,7 +36,7 @@ dA.tune(gs_order=1, **tune)
 rng = np.random.RandomState(1)
 dx, db = capi.DeviceArray.from_host(rng.rand(n)), capi.DeviceArray.from_host(rng.rand(n))
 for _ in range(6):
-    dA.gauss_seidel_x0(dx, db, sweep="symmetric", iterations=1, x_is_zero=False)
+    dA.gauss_seidel_x0(dx, db, sweep="symmetric", iterations=1, x_is_zero=x_zero)
 capi.sync()
-print("level 1", n, A.nnz, dA.lanem_info(0), dA.sym_info(), flush=True)
+print("level 1", n, A.nnz, dA.lanem_info(4 if dA.sym_info()["zero_plan_launches"] else 0), dA.sym_info(), flush=True)
 dA.free()

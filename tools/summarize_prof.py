@@ -41,16 +41,16 @@ def short(name):
     m = re.search(r"gs_lane_kernel<(\w+), *(\d+), *(\d+), *(\d+), *(\w+)>", name)
     if m:
         return f"gs_lane<{m.group(1)},{EPI[int(m.group(2))]},L{m.group(3)},K{m.group(4)},{'oneXCD' if m.group(5) in ('true', '1') else 'chip'}>"
-    m = re.search(r"gs_lanem_sym_kernel<(\w+), *(\d+), *(\d+)>", name)      # the fused symmetric sweeps: forward + backward in one launch
-    if m:
-        return f"gs_lanem_sym<double,GS,{'oneXCD' if m.group(1) in ('true', '1') else 'chip'},rpw{m.group(2)},regs{m.group(3)}>"
+    m = re.search(r"gs_lanem_sym_kernel<(\w+), *(\d+), *(\d+)(?:, *(\d+))?>", name)      # the fused symmetric sweeps: forward + backward in one launch
+    if m:                                                                                 # (a 4th argument of 1: the launch ran the zero-iterate plans, tune key 39)
+        return f"gs_lanem_sym<double,GS,{'oneXCD' if m.group(1) in ('true', '1') else 'chip'},rpw{m.group(2)},regs{m.group(3)}{',zero' if m.group(4) == '1' else ''}>"
     m = re.search(r"gs_line_sym_kernel<(\w+), *(\d+)>", name)
     if m:
         return f"gs_line_sym<{m.group(1)},GS,K{m.group(2)}>"
-    m = re.search(r"gs_lanem\w*_kernel<(\w+)(?:, *(\d+))?(?:, *(\d+))?>", name)
+    m = re.search(r"gs_lanem\w*_kernel<(\w+)(?:, *(\d+))?(?:, *(\d+))?(?:, *(\d+))?>", name)
     if m:
         return (f"gs_lanem<double,GS,{'oneXCD' if m.group(1) in ('true', '1') else 'chip'}" + (f",rpw{m.group(2)}" if m.group(2) else "")
-                + (f",regs{m.group(3)}" if m.group(3) else "") + ">")
+                + (f",regs{m.group(3)}" if m.group(3) else "") + (",zero" if m.group(4) == "1" else "") + ">")
     m = re.search(r"gs_line_kernel<(\w+), *(\d+), *(\d+)>", name)
     if m:
         return f"gs_line<{m.group(1)},{EPI[int(m.group(2))]},K{m.group(3)}>"
@@ -70,7 +70,7 @@ def family(k):
         m = re.search(r",(\w+?)(,npl\d|,kz\d|,nu\d)?>", k)
         return "csr", (m.group(1) if m else None)
     if k.startswith("gs_lanem"):
-        return "gs_lanem", None
+        return ("gs_lanem_zero" if ",zero>" in k else "gs_lanem"), None
     if k.startswith("gs_lane"):
         return "gs_lane", None
     if k.startswith("gs_line"):
@@ -114,7 +114,7 @@ for f in glob.glob(str(out / "trace" / "**" / "*kernel_trace.csv"), recursive=Tr
         import math
         for (k, g) in list(durs):
             fam, epi = family(k)
-            if fam not in ("gs_lane", "gs_lanem", "gs_line", "gs_tile", "gs_gran"):        # (block sweeps: the kernel name carries the block size of its level)
+            if fam not in ("gs_lane", "gs_lanem", "gs_lanem_zero", "gs_line", "gs_tile", "gs_gran"):        # (block sweeps: the kernel name carries the block size of its level)
                 continue
             lv = sorted({e["level"] for e in kmap["entries"] if e["family"] == fam and e.get("grid") == g})      # (entries that name THIS grid: a family without grids is told apart otherwise)
             if len(lv) < 2 or len(durs[(k, g)]) < 2 * len(lv):
