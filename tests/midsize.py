@@ -173,8 +173,8 @@ def chebyshev_coefficients(A, degree=3):
 
 
 # ----------------------------------------------------------------- smoother specs, filled directly
-def gs(sweep="symmetric"):
-    return lambda A, bs, lvl: SmootherSpec("gauss_seidel", 1, 1.0, sweep, name="gauss_seidel")
+def gs(sweep="symmetric", iterations=1):
+    return lambda A, bs, lvl: SmootherSpec("gauss_seidel", int(iterations), 1.0, sweep, name="gauss_seidel")
 
 
 def sor(omega=1.3, sweep="forward"):
