@@ -377,6 +377,11 @@ int pamg_matrix_info(pamg_matrix_t A, int64_t info[8]);
  * in floating point.  0 (default) = automatic: pamg_solver_finalize builds them on every level below the finest whose pre-smoother takes the merged
  * form in both directions, a bare operator has none; 1 = off; 2 = on (a solver: the finest level too; a bare operator builds them at its first such
  * sweep outside a graph capture).  40 = their merge depth (2..16; 0 = automatic).
+ * 41 = CORRECTION FORM of a solver's symmetric Gauss-Seidel smoothing steps that start from x != 0 (round 10: post-smoothing, the re-entries of W and F
+ * cycles, iterations 2.. of a smoother): Gauss-Seidel is affine, sweep(x, b) = x + sweep(0, b - A x), so such a step runs as r = b - A x followed by the
+ * launch announced from zero on the zero-iterate plans of key 39, whose backward half adds to x.  Equal to the direct sweep in exact arithmetic, to
+ * rounding in floating point.  0 (default) = automatic: levels that hold the plans and have at least 16 384 rows; 1 = off; 2 = on wherever the plans
+ * exist.  A bare operator's sweeps never take it (pamg_matrix_gauss_seidel_correction asks for it by name).
  * Returns PAMG_E_STATE while a solver holds the operator (captured graphs point into the plans). */
 int pamg_matrix_tune(pamg_matrix_t A, int key, int value);
 /* n_values = size of the operator's value dictionary when the whole-operator kernels stream 8-bit value codes
@@ -518,8 +523,13 @@ int pamg_matrix_gauss_seidel_x0(pamg_matrix_t A, void *x, const void *b, int swe
  * (1 merged lanes across the chip, 2 lines, 3 merged lanes inside one XCD, 0 none yet), the workgroups of the last one on the general plans (a launch on
  * the zero-iterate plans reports its own in pamg_matrix_lanem_info(which = 4)), tune key 37, entries of the forward hand-off buffer that are NOT sentinels (0 between
  * launches; -1: no buffers), counters that are not zero (0 between launches), symmetric sweeps (fused or as two launches) that ran on the
- * zero-iterate plans (tune key 39)}.  Synchronises the device. */
-int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[8]);
+ * zero-iterate plans (tune key 39) -- announced from zero, or in correction form --, symmetric smoothing steps that ran in correction form (tune key 41;
+ * each is also counted as a sweep announced from zero on the zero-iterate plans: it is one, on the residual)}.  Synchronises the device. */
+int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[9]);
+/* One symmetric Gauss-Seidel sweep per iteration in CORRECTION FORM, whatever tune key 41 says: r = b - A x, then x += sweep(0, r) on the operator's
+ * zero-iterate plans (r: DEVICE scratch vector of the operator's size, overwritten).  PAMG_E_UNSUPPORTED where the operator holds no such plans (a bare
+ * operator with key 39 = 2 builds them here, outside a graph capture). */
+int pamg_matrix_gauss_seidel_correction(pamg_matrix_t A, void *x, const void *b, void *r, int iterations, pamg_stream_t s);
 /* relaxation.polynomial (relaxation.py:585-659); coeffs is a HOST array; x_is_zero != 0
  * asserts x == 0 on entry (the reference tests norm(x) == 0, relaxation.py:649). */
 int pamg_matrix_polynomial(pamg_matrix_t A, void *x, const void *b, void *work,

@@ -155,6 +155,7 @@ def _declare(lib):
     f("pamg_solver_set_cf_block_smoother", _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _i, _vp, _i, _vp, _i)
     f("pamg_matrix_gauss_seidel", _vp, _vp, _vp, _i, _d, _i, _vp)
     f("pamg_matrix_gauss_seidel_x0", _vp, _vp, _vp, _i, _d, _i, _i, _vp)
+    f("pamg_matrix_gauss_seidel_correction", _vp, _vp, _vp, _vp, _i, _vp)
     f("pamg_matrix_sym_info", _vp, P(C.c_int64))
     f("pamg_matrix_polynomial", _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp)
     f("pamg_matrix_block_jacobi", _vp, _vp, _vp, _vp, _vp, _d, _i, _vp)

@@ -245,6 +245,8 @@ struct pamg_matrix_s {
     const void *sym_cap_kernel = nullptr;
     int zsym_cap = 0;                // the same for the fused kernel's zero-iterate instantiation
     const void *zsym_cap_kernel = nullptr;
+    int csym_cap = 0;                // and for its accumulating instantiation (the correction form)
+    const void *csym_cap_kernel = nullptr;
     int sym_general_grid = 0;        // workgroups of the last fused launch on the general plans (sym_grid: of the last fused launch of either kind)
     int sym_form = 0, sym_grid = 0;  // the last fused launch: 1 = merged lanes, 2 = lines, 3 = merged lanes inside one XCD / its workgroups (diagnostics)
     long long sym_launches = 0, sym_zero_launches = 0;   // fused launches enqueued or captured / those with x known to be zero
@@ -255,7 +257,10 @@ struct pamg_matrix_s {
     struct pamg::LaneMSched *zplan[2] = {nullptr, nullptr};
     void *d_zw = nullptr;
     size_t zero_bytes = 0;           // what the plans and d_zw added to `bytes`
-    long long zero_plan_launches = 0;   // symmetric sweeps (fused or as two launches) that ran on the zero-iterate plans
+    long long zero_plan_launches = 0;   // symmetric sweeps (fused or as two launches) that ran on the zero-iterate plans: announced from x = 0, or in correction form
+    // correction form of a symmetric sweep from x != 0 (a solver's cycle driver): r = b - A x, then x += sweep(0, r) on the zero-iterate plans
+    int gs_correction = 0;           // tune key 41: 0 = automatic (levels of at least GS_CORRECTION_MIN_ROWS rows), 1 = off, 2 = on wherever the plans exist
+    long long correction_launches = 0;  // symmetric smoothing steps that ran in correction form (fused or as two launches)
     size_t bytes = 0;
 };
 
@@ -378,16 +383,23 @@ void free_lanem_part(struct LaneMSched *t);
 size_t lanem_part_bytes(const GsSchedule *g);
 int lanem_info(const GsSchedule *g, int64_t *info, double *growth);
 int lanem_levels(const GsSchedule *g, int64_t *out, int64_t cap, int64_t *n);
-int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, bool x_zero, hipStream_t s);
+int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, bool x_zero, hipStream_t s, bool acc = false);
 int lanem_plan_info(const struct LaneMSched *t, int64_t *info, double *growth);
 int build_zero_plan(pamg_matrix_s *A, int dir);  // dir 0: forward plan of tril(A), 1: backward plan of triu(A); PAMG_E_ARG: the form does not fit
 void free_zero_plans(pamg_matrix_s *A);
 size_t zero_plan_bytes(const pamg_matrix_s *A);
 bool zero_plans_ready(const pamg_matrix_s *A, const GsSchedule *gf, const GsSchedule *gb);
-int lanem_zero_pair_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, hipStream_t s);
+int lanem_zero_pair_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, bool acc, hipStream_t s);
 int ensure_zero_parts(pamg_matrix_s *A, bool build);   // pamg_matrix.hip: complete (or drop) the operator's zero-iterate plans; allocates, never inside a capture
 void matrix_drop_zero_plans(pamg_matrix_s *A);
 int gs_sweep_zero_pair(pamg_matrix_s *A, void *x, const void *b, hipStream_t s, bool *ran);   // symmetric sweep from x = 0 as two launches on the zero-iterate plans
+// a symmetric sweep from x != 0 in correction form: r = b - A x (r: a scratch vector of the operator's size), then x += sweep(0, r) on the zero-iterate
+// plans, fused or as two launches.  *ran = false: not applicable (no plans, switched off by tune key 41, or a level below the automatic threshold
+// unless `force`) -- nothing was enqueued
+int gs_sweep_correction(pamg_matrix_s *A, void *x, const void *b, void *r, bool force, hipStream_t s, bool *ran);
+// tune key 41 = 0: the correction form runs on levels of at least this many rows (the two extra small launches cost a small level more than the
+// triangular plans save).  A placeholder from round 9's kernel times until tools/microbench_gs_correction.py has been run
+constexpr int64_t GS_CORRECTION_MIN_ROWS = 16384;
 int sym_fill_sentinels(void *p, int64_t n);      // n f64 sentinels on the null stream, synchronised
 int sweep_error(pamg_matrix_s *A, bool *error);      // spin bound hit since the last call? (caller has synchronised; clears the flag)
 inline size_t tsize(int dtype) { return dtype == PAMG_F64 ? 8 : 4; }

@@ -474,7 +474,8 @@ __device__ __forceinline__ void m_slots(const LaneMArgs &a, MCtx<NREG> &C, const
 // phase of the fused symmetric sweep), so the row's own old value is read past the L1 as the operands are
 // BCOH: a.b was written by other workgroups of THIS launch too (the backward phase on a zero-iterate plan, whose right-hand side is the vector of
 // numerators the forward phase stored): the row's own entry is read past the L1; the operands that come from b already are
-template <int NREG, bool BCOH = false>
+// XOZ: the sweep runs on a virtual zero iterate (the correction form, Z = 2 of the kernels): a row without a diagonal carries 0, not what a.xold holds
+template <int NREG, bool BCOH = false, bool XOZ = false>
 __device__ __forceinline__ void m_gather(const LaneMArgs &a, MCtx<NREG> &C, int idle, const bool xz = false, const bool coh = false)
 {
 #pragma unroll
@@ -488,7 +489,8 @@ __device__ __forceinline__ void m_gather(const LaneMArgs &a, MCtx<NREG> &C, int 
     const int row = C.rid < 0 ? 0 : (C.rid & LANE_MASK);
     if constexpr (BCOH) C.bv = __hip_atomic_load(a.b + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else C.bv = a.b[row];
-    C.xo = coh ? __hip_atomic_load(a.xold + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.xold[row];      // used by rows without a diagonal only
+    if constexpr (XOZ) C.xo = 0.0;
+    else C.xo = coh ? __hip_atomic_load(a.xold + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.xold[row];      // used by rows without a diagonal only
     // every operand by an L1-bypassing load: early ones poll the hand-off buffer, static ones read the snapshot of x and b (ordinary loads for
     // the static operands were measured 3 - 5 % slower, profiles/r06_microbench_lanem_plain_loads_for_static_operands_not_kept.json)
 #pragma unroll
@@ -581,7 +583,9 @@ __device__ __forceinline__ double m_finish(const LaneMArgs &a, MCtx<NREG> &C, in
 // PH = 1: the first phase of the fused symmetric sweep -- the hand-off buffer is also where the second phase reads its OLD operands (every row
 // publishes, a row without a diagonal its old value), x is not written
 // WST: a zero-iterate forward plan -- the row's numerator goes to a.w
-template <int RPW, int MODE, int NREG, int PH = 0, bool WST = false>
+// ACC: the correction form -- the row's value is ADDED to a.y (y is read by nobody else in a zero-iterate launch, and the row has one owning lane:
+// a plain load, add, store)
+template <int RPW, int MODE, int NREG, int PH = 0, bool WST = false, bool ACC = false>
 __device__ __forceinline__ void m_publish(const LaneMArgs &a, const MCtx<NREG> &C, double val)
 {
     if (((threadIdx.x & 63) & (64 / RPW - 1)) == 0 && C.rid >= 0) {
@@ -589,7 +593,10 @@ __device__ __forceinline__ void m_publish(const LaneMArgs &a, const MCtx<NREG> &
         if constexpr (MODE == 1) __hip_atomic_store(a.xs + row, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         else __hip_atomic_store(a.xs + row, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if constexpr (PH != 1) {
-            if (!(C.rid & LANE_NODIAG)) a.y[row] = val;
+            if (!(C.rid & LANE_NODIAG)) {
+                if constexpr (ACC) a.y[row] = a.y[row] + val;
+                else a.y[row] = val;
+            }
         }
         if constexpr (WST) {                                  // the numerator crosses XCDs inside the fused launch: the flavour of the publishing store
             if (!(C.rid & LANE_NODIAG)) __hip_atomic_store(a.w + row, C.num, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -606,8 +613,8 @@ constexpr int LANEC_K = 8;                    // units of unique operands / of s
 
 __device__ __forceinline__ int4 c_rec(const int4 *rp, int g, int gend) { return rp[(size_t)(g < gend ? g : gend - 1)]; }
 
-// one group.  PH / WST as in m_publish; xz / coh / BCOH as in m_gather
-template <int PH, bool WST = false, bool BCOH = false>
+// one group.  PH / WST / ACC as in m_publish; xz / coh / BCOH as in m_gather (ACC in phase 1: XOZ)
+template <int PH, bool WST = false, bool BCOH = false, bool ACC = false>
 __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const int4 &q, int g, int lane, int idle, const bool xz, const bool coh)
 {
     using T = double;
@@ -653,7 +660,8 @@ __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const i
     T bv;
     if constexpr (BCOH) bv = __hip_atomic_load(a.b + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else bv = a.b[row];
-    const T xo = coh ? __hip_atomic_load(a.xold + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.xold[row];      // used by rows without a diagonal only
+    T xo = T(0);                                                // used by rows without a diagonal only
+    if constexpr (!(ACC && PH == 1)) xo = coh ? __hip_atomic_load(a.xold + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.xold[row];
     unsigned pend = 0;
 #pragma unroll
     for (int k = 0; k < LANEC_K; ++k)
@@ -722,7 +730,10 @@ __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const i
     if (tail && rid >= 0) {
         __hip_atomic_store(a.xs + row, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if constexpr (PH != 1) {
-            if (upd) a.y[row] = val;
+            if (upd) {
+                if constexpr (ACC) a.y[row] = a.y[row] + val;
+                else a.y[row] = val;
+            }
         }
         if constexpr (WST) {
             if (upd) __hip_atomic_store(a.w + row, num, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -735,6 +746,7 @@ __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const i
 // 256^3 hierarchy at s = 6: 56 % of the rows hold three and more units)
 // Z = 1: the forward plan of a zero-iterate pair run as a launch of its own (the numerators go to a.w; the backward plan then runs as Z = 0 with
 // b = that vector: the kernel boundary orders the two)
+// Z = 2: the backward plan of a zero-iterate pair in the correction form: its values are added to a.y
 template <int MODE, int RPW, int NREG, int Z = 0>
 __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
 {
@@ -752,7 +764,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
         int4 q = c_rec(rp, g, gend);
         for (; g < gend; g += W) {
             const int4 nq = c_rec(rp, g + W, gend);
-            c_group<0, Z != 0>(a, c_lds + wib * LANEC_UMAX, q, g, lane, idle, false, false);
+            c_group<0, Z == 1, false, Z == 2>(a, c_lds + wib * LANEC_UMAX, q, g, lane, idle, false, false);
             q = nq;
         }
     } else {
@@ -776,7 +788,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
                 long long t2 = 0;
                 unsigned sp = 0;
                 const double val = m_finish<RPW, NREG>(a, X, idle, &t2, &sp);
-                m_publish<RPW, MODE, NREG, 0, Z != 0>(a, X, val);
+                m_publish<RPW, MODE, NREG, 0, Z == 1, Z == 2>(a, X, val);
                 if (lane == 0) {
                     long long *o = a.prof + (size_t)g * 4;
                     o[0] = t0 | ((long long)(sp > 4095u ? 4095u : sp) << 52);
@@ -786,7 +798,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
                 m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
                 m_gather<NREG>(a, X, idle);
                 const double val = m_finish<RPW, NREG>(a, X, idle);
-                m_publish<RPW, MODE, NREG, 0, Z != 0>(a, X, val);
+                m_publish<RPW, MODE, NREG, 0, Z == 1, Z == 2>(a, X, val);
             }
             q0 = n0; q1 = n1;
         }
@@ -816,7 +828,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
             m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
             m_gather<NREG>(a, X, idle);
             const double val = m_finish<RPW, NREG>(a, X, idle);
-            m_publish<RPW, MODE, NREG, 0, Z != 0>(a, X, val);
+            m_publish<RPW, MODE, NREG, 0, Z == 1, Z == 2>(a, X, val);
             if (g2 >= gend) break;
             g = g2; q0 = n0; q1 = n1;
             g2 = (int)__builtin_amdgcn_readfirstlane(tk3);
@@ -884,7 +896,7 @@ __device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, in
         int4 q = c_rec(rp, g, gend);
         for (; g < gend; g += W) {
             const int4 nq = c_rec(rp, g + W, gend);
-            c_group<PH, Z && PH == 1, Z && PH == 2>(a, c_lds + wib * LANEC_UMAX, q, g, lane, idle, xz, PH == 2);
+            c_group<PH, Z && PH == 1, Z && PH == 2, Z == 2>(a, c_lds + wib * LANEC_UMAX, q, g, lane, idle, xz, PH == 2);
             m_wipe<MODE>(wipe, g, gend, wq, wr, wblk, lane);
             ++done;
             q = nq;
@@ -901,9 +913,9 @@ __device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, in
             int4 n0, n1;
             m_rec(rp, g + W, gend, n0, n1);
             m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
-            m_gather<NREG, Z && PH == 2>(a, X, idle, xz, PH == 2);
+            m_gather<NREG, Z && PH == 2, Z == 2 && PH == 1>(a, X, idle, xz, PH == 2);
             const double val = m_finish<RPW, NREG>(a, X, idle, nullptr, nullptr, xz);
-            m_publish<RPW, MODE, NREG, PH, Z && PH == 1>(a, X, val);
+            m_publish<RPW, MODE, NREG, PH, Z && PH == 1, Z == 2 && PH == 2>(a, X, val);
             m_wipe<MODE>(wipe, g, gend, wq, wr, wblk, lane);      // behind the publishing stores: nobody waits for these
             ++done;
             q0 = n0; q1 = n1;
@@ -923,9 +935,9 @@ __device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, in
             unsigned tk3 = 0;
             if (g2 < gend && lane == 0) tk3 = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
-            m_gather<NREG, Z && PH == 2>(a, X, idle, xz, PH == 2);
+            m_gather<NREG, Z && PH == 2, Z == 2 && PH == 1>(a, X, idle, xz, PH == 2);
             const double val = m_finish<RPW, NREG>(a, X, idle, nullptr, nullptr, xz);
-            m_publish<RPW, MODE, NREG, PH, Z && PH == 1>(a, X, val);
+            m_publish<RPW, MODE, NREG, PH, Z && PH == 1, Z == 2 && PH == 2>(a, X, val);
             m_wipe<MODE>(wipe, g, gend, wq, wr, wblk, lane);
             ++done;
             if (g2 >= gend) break;
@@ -974,6 +986,8 @@ __device__ __forceinline__ void sym_leave(unsigned *sync, unsigned parity)
 }
 
 // Z = 1: the two phases run the operator's zero-iterate plans (x = 0 on entry): phase 1 stores the numerators in ph[0].w, phase 2 reads them as its b
+// Z = 2: the correction form -- the same two phases on a VIRTUAL zero iterate (b is a residual, x is never read as an operand: rows without a
+//        diagonal carry 0 through both phases), phase 2 adds its values to x instead of storing them: x += sweep(0, b)
 template <int MODE, int RPW, int NREG, int Z = 0>
 __global__ __launch_bounds__(BLK) void gs_lanem_sym_kernel(const LaneMSymArgs a)
 {
@@ -1437,7 +1451,9 @@ static void lanem_layout_args(const LaneMSched *t, LaneMArgs &a)
 }
 
 // t: the schedule's own plan, or a zero-iterate plan of the operator run on the schedule's buffers (w: where Zf stores its numerators)
-static int lanem_launch_plan(pamg_matrix_s *A, GsSchedule *g, LaneMSched *t, void *x, const void *b, double *w, hipStream_t s)
+// acc: the backward half of the correction form -- the schedule's snapshot already holds the forward half's values (the caller swept into it), so
+// only the hand-off buffer is prepared, and the kernel adds its values to x
+static int lanem_launch_plan(pamg_matrix_s *A, GsSchedule *g, LaneMSched *t, void *x, const void *b, double *w, hipStream_t s, bool acc = false)
 {
     if (!t || !g->d_xold) return PAMG_E_STATE;
     const int64_t n = A->nrows;
@@ -1455,7 +1471,8 @@ static int lanem_launch_plan(pamg_matrix_s *A, GsSchedule *g, LaneMSched *t, voi
     }
     a.prof = (A->gs_prof && !t->cluster) ? t->d_prof : nullptr;
     const int fgrid = (int)std::min<int64_t>(4096, (n + BLK - 1) / BLK);
-    hipLaunchKernelGGL(lanem_prepare_kernel, dim3(fgrid), dim3(BLK), 0, s, (const double *)x, (double *)g->d_xold, (double *)g->d_xs, n);
+    if (acc) hipLaunchKernelGGL((lane_fill_sentinel_kernel<double>), dim3(fgrid), dim3(BLK), 0, s, (double *)g->d_xs, n);
+    else hipLaunchKernelGGL(lanem_prepare_kernel, dim3(fgrid), dim3(BLK), 0, s, (const double *)x, (double *)g->d_xold, (double *)g->d_xs, n);
     PAMG_HIP(hipGetLastError());
     // the ticket form inside one XCD only for tiny levels: one row per group means one ticket per ROW, and the ticket counter is one address whose
     // atomics serialise (11.4 ns each) -- level 2 of the 256^3 hierarchy (44.6 K rows): 0.58 ms inside one XCD, 0.48 across the chip
@@ -1471,6 +1488,11 @@ static int lanem_launch_plan(pamg_matrix_s *A, GsSchedule *g, LaneMSched *t, voi
           : t->rpw == 2 ? (xcd ? (const void *)gs_lanem_kernel<1, 2, 4, 1> : (const void *)gs_lanem_kernel<0, 2, 4, 1>)
           : all_regs    ? (xcd ? (const void *)gs_lanem_kernel<1, 1, 8, 1> : (const void *)gs_lanem_kernel<0, 1, 8, 1>)
                         : (xcd ? (const void *)gs_lanem_kernel<1, 1, 2, 1> : (const void *)gs_lanem_kernel<0, 1, 2, 1>);
+    if (acc)
+        k = t->cluster  ? (const void *)gs_lanem_kernel<0, 0, 8, 2>
+          : t->rpw == 2 ? (xcd ? (const void *)gs_lanem_kernel<1, 2, 4, 2> : (const void *)gs_lanem_kernel<0, 2, 4, 2>)
+          : all_regs    ? (xcd ? (const void *)gs_lanem_kernel<1, 1, 8, 2> : (const void *)gs_lanem_kernel<0, 1, 8, 2>)
+                        : (xcd ? (const void *)gs_lanem_kernel<1, 1, 2, 2> : (const void *)gs_lanem_kernel<0, 1, 2, 2>);
     static thread_local int cus = 0;
     if (!cus) cus = device_cus_lane();
     if (!(t->cap > 0 && t->cap_kernel == k)) {
@@ -1508,11 +1530,20 @@ int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStr
 
 // the symmetric sweep from x = 0 as two launches on the zero-iterate plans (tune key 37 = 0, or where the fused kernel does not apply): what the
 // fused launch computes, bit for bit -- the same plans, the same row sums, w across the kernel boundary
-int lanem_zero_pair_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, hipStream_t s)
+// acc: the correction form, x += sweep(0, b).  The forward half sweeps a zeroed vector -- the backward schedule's snapshot buffer, which the backward
+// half would otherwise fill with a copy of exactly these values -- and the backward half adds what it computes to x: no scratch vector, no copy, no add pass
+int lanem_zero_pair_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, bool acc, hipStream_t s)
 {
     if (!zero_plans_ready(A, gf, gb)) return PAMG_E_UNSUPPORTED;
-    PAMG_TRY(lanem_launch_plan(A, gf, A->zplan[0], x, b, (double *)A->d_zw, s));
-    PAMG_TRY(lanem_launch_plan(A, gb, A->zplan[1], x, A->d_zw, nullptr, s));
+    if (acc) {
+        if (!gb->d_xold) return PAMG_E_STATE;
+        PAMG_HIP(hipMemsetAsync(gb->d_xold, 0, (size_t)A->nrows * sizeof(double), s));
+        PAMG_TRY(lanem_launch_plan(A, gf, A->zplan[0], gb->d_xold, b, (double *)A->d_zw, s));
+        PAMG_TRY(lanem_launch_plan(A, gb, A->zplan[1], x, A->d_zw, nullptr, s, true));
+    } else {
+        PAMG_TRY(lanem_launch_plan(A, gf, A->zplan[0], x, b, (double *)A->d_zw, s));
+        PAMG_TRY(lanem_launch_plan(A, gb, A->zplan[1], x, A->d_zw, nullptr, s));
+    }
     A->zero_plan_launches++;
     return PAMG_OK;
 }
@@ -1529,10 +1560,14 @@ int sym_fill_sentinels(void *p, int64_t n)
 
 // The fused symmetric sweep (gs_lanem_sym_kernel).  PAMG_E_UNSUPPORTED: the two schedules would not run the same kernel -- the caller sweeps
 // them one after the other.  The grid is the larger of the two directional wishes (lanem_launch) under the fused kernel's own co-residency cap.
-int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, bool x_zero, hipStream_t s)
+// acc: the correction form, x += sweep(0, b), on the zero-iterate plans (PAMG_E_UNSUPPORTED without them): the launch announced from zero whose second
+// phase adds to x
+int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, bool x_zero, hipStream_t s, bool acc)
 {
     LaneMSched *tf = gf->lanem, *tb = gb->lanem;
     if (!tf || !tb || !A->d_sym_hf[0] || !A->d_sym_hf[1] || !A->d_sym_hb || !A->d_sym_sync) return PAMG_E_STATE;
+    if (acc && !zero_plans_ready(A, gf, gb)) return PAMG_E_UNSUPPORTED;
+    if (acc) x_zero = true;                                     // (the VIRTUAL iterate is zero: phase 1 skips its OLD operands)
     // x = 0 and the operator holds its zero-iterate plans: phase 1 runs Zf and stores the numerators, phase 2 runs Zb on them
     const bool zero = x_zero && zero_plans_ready(A, gf, gb);
     if (zero) { tf = A->zplan[0]; tb = A->zplan[1]; }
@@ -1574,10 +1609,15 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
           : tf->rpw == 2 ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4, 1> : (const void *)gs_lanem_sym_kernel<0, 2, 4, 1>)
           : all_regs     ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 8, 1> : (const void *)gs_lanem_sym_kernel<0, 1, 8, 1>)
                          : (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 2, 1> : (const void *)gs_lanem_sym_kernel<0, 1, 2, 1>);
+    if (acc)
+        k = tf->cluster  ? (const void *)gs_lanem_sym_kernel<0, 0, 8, 2>
+          : tf->rpw == 2 ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4, 2> : (const void *)gs_lanem_sym_kernel<0, 2, 4, 2>)
+          : all_regs     ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 8, 2> : (const void *)gs_lanem_sym_kernel<0, 1, 8, 2>)
+                         : (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 2, 2> : (const void *)gs_lanem_sym_kernel<0, 1, 2, 2>);
     static thread_local int cus = 0;
     if (!cus) cus = device_cus_lane();
-    int &kcap = zero ? A->zsym_cap : A->sym_cap;               // (the two kernels alternate within a cycle: one cached answer each)
-    const void *&kcap_kernel = zero ? A->zsym_cap_kernel : A->sym_cap_kernel;
+    int &kcap = acc ? A->csym_cap : zero ? A->zsym_cap : A->sym_cap;      // (the kernels alternate within a cycle: one cached answer each)
+    const void *&kcap_kernel = acc ? A->csym_cap_kernel : zero ? A->zsym_cap_kernel : A->sym_cap_kernel;
     if (!(kcap > 0 && kcap_kernel == k)) {
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess) nb = 2;

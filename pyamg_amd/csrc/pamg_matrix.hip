@@ -1540,10 +1540,46 @@ int gs_sweep_zero_pair(pamg_matrix_s *A, void *x, const void *b, hipStream_t s, 
         PAMG_TRY(ensure_zero_parts(A, true));
         if (!zero_plans_ready(A, gf, gb)) { A->zero_plans = 1; return PAMG_OK; }      // the form does not fit: not asked again
     }
-    const int st = lanem_zero_pair_launch(A, gf, gb, x, b, s);
+    const int st = lanem_zero_pair_launch(A, gf, gb, x, b, false, s);
     if (st == PAMG_E_UNSUPPORTED) return PAMG_OK;
     if (st == PAMG_OK) *ran = true;
     return st;
+}
+
+// ---- the correction form (tune key 41).  Gauss-Seidel is an affine iteration: sweep(x, b) = x + sweep(0, b - A x), for the symmetric sweep as for
+// each half.  A symmetric sweep from x != 0 can therefore run on the zero-iterate plans: one residual launch, then the launch announced from zero on
+// r whose backward half ADDS to x (the accumulating instantiation of the kernels, pamg_lane.hip).  Only a solver's cycle driver asks for it (it owns
+// the scratch vector); a bare operator's sweeps keep the general plans unless the caller asks by name (pamg_matrix_gauss_seidel_correction).
+int gs_sweep_correction(pamg_matrix_s *A, void *x, const void *b, void *r, bool force, hipStream_t s, bool *ran)
+{
+    *ran = false;
+    if (!r || A->zero_plans == 1) return PAMG_OK;
+    if (!force && (A->gs_correction == 1 || (A->gs_correction == 0 && A->nrows < GS_CORRECTION_MIN_ROWS))) return PAMG_OK;
+    if (!A->zplan[0] || !A->zplan[1] || !A->d_zw) {
+        if (!force || A->zero_plans != 2 || A->zplan[0] || A->zplan[1]) return PAMG_OK;
+        // a bare operator with key 39 = 2, asked by name: the plans are built here -- allocations, so never inside a graph capture
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        PAMG_HIP(hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone) return PAMG_OK;
+        PAMG_TRY(ensure_zero_parts(A, true));
+    }
+    GsSchedule *gf = nullptr, *gb = nullptr;
+    if (!zero_form_of(A, &gf, &gb) || !zero_plans_ready(A, gf, gb)) return PAMG_OK;
+    GsSchedule *sf = nullptr, *sb = nullptr;
+    bool fused = sym_form_of(A, &sf, &sb) == 1;
+    if (fused && !A->d_sym_hf[0]) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        PAMG_HIP(hipStreamIsCapturing(s, &cs));
+        if (cs == hipStreamCaptureStatusNone) PAMG_TRY(ensure_sym_parts(A));
+        fused = A->d_sym_hf[0] != nullptr;
+    }
+    PAMG_TRY(stream_launch(A, EPI_RESID, x, b, r, 0.0, 0.0, nullptr, s));                     // r = b - A x
+    int st = fused ? lanem_sym_launch(A, gf, gb, x, r, true, s, true) : PAMG_E_UNSUPPORTED;
+    if (st == PAMG_E_UNSUPPORTED) st = lanem_zero_pair_launch(A, gf, gb, x, r, true, s);     // (the two directions would not run the same fused kernel, or key 37 = 0)
+    if (st != PAMG_OK) return st;
+    A->correction_launches++;
+    *ran = true;
+    return PAMG_OK;
 }
 
 int ensure_schedule(pamg_matrix_s *A, int row_start, int row_stop, int row_step, bool block_gs)
@@ -2154,6 +2190,7 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
         case 37: if (value < 0 || value > 1) return PAMG_E_ARG; A->sym_fused = value; return PAMG_OK;      // read at launch time; refused above while a solver's graphs hold the choice
         case 39: if (value < 0 || value > 2) return PAMG_E_ARG; A->zero_plans = value; if (value == 1) matrix_drop_zero_plans(A); return PAMG_OK;
         case 40: if (value != 0 && (value < 2 || value > 16)) return PAMG_E_ARG; A->zero_merge = value; matrix_drop_zero_plans(A); return PAMG_OK;
+        case 41: if (value < 0 || value > 2) return PAMG_E_ARG; A->gs_correction = value; return PAMG_OK;     // read at launch time; refused above while a solver's graphs hold the choice
         case 30:                                               // 2: also where the estimate favours the lane form
             if (value < 0 || value > 2) return PAMG_E_ARG;
             A->line_scan = value;
@@ -2366,13 +2403,14 @@ int pamg_matrix_lanem_info(pamg_matrix_t A, int which, int64_t info[20], double 
     return pamg::lanem_info(A->gs[which], info, growth);
 }
 
-int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[8])
+int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[9])
 {
     if (!A || !info) return PAMG_E_ARG;
-    for (int k = 0; k < 8; ++k) info[k] = 0;
+    for (int k = 0; k < 9; ++k) info[k] = 0;
     info[0] = A->sym_launches; info[1] = A->sym_zero_launches; info[2] = A->sym_form; info[3] = A->sym_general_grid ? A->sym_general_grid : A->sym_grid; info[4] = A->sym_fused;
     info[5] = -1; info[6] = -1;
     info[7] = A->zero_plan_launches;
+    info[8] = A->correction_launches;
     if (!A->d_sym_hf[0]) return PAMG_OK;
     PAMG_HIP(hipDeviceSynchronize());
     // the invariant between launches: every entry of the forward hand-off buffer the NEXT launch publishes in a sentinel, the counters zero

@@ -95,7 +95,9 @@ int block_jacobi_pp(pamg_matrix_s *A, void **px, void **palt, const void *b, con
 // relaxation.gauss_seidel / relaxation.sor as the reference runs them (relaxation.py:265-346,
 // :100-154).  Quirks mirrored on purpose: sweep='symmetric' drops omega (:326-330), the BSR
 // flavour ignores omega (:343-346).
-int gs_apply(pamg_matrix_s *A, void *x, const void *b, int sweep, double omega, int its, hipStream_t s, bool x_zero = false)
+// r: a scratch vector of the operator's size (a solver's level residual) -- a symmetric sweep that is not announced to start from zero may then run in
+// correction form (gs_sweep_correction, tune key 41); nullptr (a bare operator): never
+int gs_apply(pamg_matrix_s *A, void *x, const void *b, int sweep, double omega, int its, hipStream_t s, bool x_zero = false, void *r = nullptr)
 {
     if (!square_ok(A)) return PAMG_E_ARG;
     if (A->nrows == 0) return PAMG_OK;
@@ -111,6 +113,9 @@ int gs_apply(pamg_matrix_s *A, void *x, const void *b, int sweep, double omega, 
         for (int it = 0; it < its; ++it) {
             // one launch where both directions take the same fast form (x_zero holds for the first iteration only)
             bool ran = false;
+            // from x != 0 on a level that holds zero-iterate plans: r = b - A x, then x += sweep(0, r) on those plans
+            if (r && !(x_zero && it == 0)) PAMG_TRY(gs_sweep_correction(A, x, b, r, false, s, &ran));
+            if (ran) continue;
             PAMG_TRY(gs_sweep_symmetric(A, x, b, x_zero && it == 0, s, &ran));
             if (ran) continue;
             // two launches: from x = 0 on the operator's zero-iterate plans where it holds them (what the fused launch runs: the same bits)
@@ -211,8 +216,9 @@ int apply_smoother(pamg_solver_s *S, Level &L, const Smoother &sm, bool x_zero, 
     switch (sm.kind) {
         case PAMG_SMOOTH_NONE: return PAMG_OK;
         case PAMG_SMOOTH_JACOBI: return jacobi_pp(L.A, &L.x, &L.xalt, L.b, sm.omega, sm.iterations, s);
-        case PAMG_SMOOTH_GS: return gs_apply(L.A, L.x, L.b, sm.sweep, 1.0, sm.iterations, s, x_zero);
-        case PAMG_SMOOTH_SOR: return gs_apply(L.A, L.x, L.b, sm.sweep, sm.omega, sm.iterations, s, x_zero);
+        // (L.r is dead while a smoother runs: cycle_rec recomputes it before every restriction)
+        case PAMG_SMOOTH_GS: return gs_apply(L.A, L.x, L.b, sm.sweep, 1.0, sm.iterations, s, x_zero, L.r);
+        case PAMG_SMOOTH_SOR: return gs_apply(L.A, L.x, L.b, sm.sweep, sm.omega, sm.iterations, s, x_zero, L.r);
         case PAMG_SMOOTH_POLY:
             return poly_apply(L.A, L.x, L.b, L.work, sm.coeffs.data(), (int)sm.coeffs.size(),
                               sm.iterations, x_zero ? 1 : 0, s);
@@ -1281,6 +1287,18 @@ int pamg_matrix_gauss_seidel_x0(pamg_matrix_t A, void *x, const void *b, int swe
     if (!A || !x || !b || iterations < 0) return PAMG_E_ARG;
     if (sweep < PAMG_FORWARD || sweep > PAMG_SYMMETRIC) return PAMG_E_ARG;
     return gs_apply(A, x, b, sweep, omega, iterations, (hipStream_t)s, x_is_zero != 0);
+}
+
+int pamg_matrix_gauss_seidel_correction(pamg_matrix_t A, void *x, const void *b, void *r, int iterations, pamg_stream_t s)
+{
+    if (!A || !x || !b || !r || iterations < 0) return PAMG_E_ARG;
+    if (!square_ok(A)) return PAMG_E_ARG;
+    for (int it = 0; it < iterations; ++it) {
+        bool ran = false;
+        PAMG_TRY(gs_sweep_correction(A, x, b, r, true, (hipStream_t)s, &ran));
+        if (!ran) return PAMG_E_UNSUPPORTED;
+    }
+    return PAMG_OK;
 }
 
 int pamg_matrix_polynomial(pamg_matrix_t A, void *x, const void *b, void *work, const double *coeffs,

@@ -99,6 +99,19 @@ def kernel_map(dml, smoother_kind):
                                         "bytes_streamed": int(sum(_lanem_bytes(l_, n, vb) for l_ in zm) + 2 * vb * n),
                                         "format": _lanem_format(zm[0]),
                                         "dependency_levels": int(zm[0]["super_levels"] + zm[1]["super_levels"])})
+                        if sym.get("correction_launches"):
+                            # the steps from x != 0 in correction form (tune key 41): the whole-operator residual kernel once more (the same kernel and grid
+                            # as the residual in front of the restriction: the trace cannot tell the two apart, summarize_prof.py shares the launches out),
+                            # then the zero-iterate plans in the kernel's accumulating instantiation (x is read and written once more than in `zero`)
+                            r_ = _op_entry(i, "A", A, "RESID", "A residual for the post-smoothing correction")
+                            r_["shares_launches_with"] = "residual r = b - A x"
+                            out.append(r_)
+                            out.append({"family": "gs_lanem_corr", "grid": int(zm[0]["launch_grid"]), "level": i, "op": "A",
+                                        "what": f"correction sweep x += sweep(0, r), one launch (zero-iterate plans: {zm[0]['super_levels']} + {zm[1]['super_levels']} super-levels)",
+                                        "rows": int(n), "nnz": int(nnz), "bytes_alg": int(2 * alg),
+                                        "bytes_streamed": int(sum(_lanem_bytes(l_, n, vb) for l_ in zm) + 3 * vb * n),
+                                        "format": _lanem_format(zm[0]),
+                                        "dependency_levels": int(zm[0]["super_levels"] + zm[1]["super_levels"])})
                 for which, dirn in directions:
                     lane, tile, line, lanem = A.lane_info(which), A.tile_info(which), A.line_info(which), A.lanem_info(which)
                     if lanem["rows"] and lanem["launch_grid"]:

@@ -19,6 +19,7 @@ from pathlib import Path
 
 out, wl, tag = Path(sys.argv[1]), sys.argv[2], sys.argv[3]
 BKIND = ["BLK_JACOBI", "BLK_GS", "PNT_JACOBI", "PNT_GS"]
+ZSUF = {"1": ",zero", "2": ",corr"}      # 4th template argument of the merged sweeps: the zero-iterate plans, announced from zero / in correction form
 EPI = ["SET", "ACC", "RESID", "AXPBY", "ACC_AXPBY", "SUMSQ", "ACCSEQ", "JACOBI", "JACOBI_B", "GS", "GS_B", "SOR", "JACOBI_IDX"]
 
 
@@ -42,15 +43,15 @@ def short(name):
     if m:
         return f"gs_lane<{m.group(1)},{EPI[int(m.group(2))]},L{m.group(3)},K{m.group(4)},{'oneXCD' if m.group(5) in ('true', '1') else 'chip'}>"
     m = re.search(r"gs_lanem_sym_kernel<(\w+), *(\d+), *(\d+)(?:, *(\d+))?>", name)      # the fused symmetric sweeps: forward + backward in one launch
-    if m:                                                                                 # (a 4th argument of 1: the launch ran the zero-iterate plans, tune key 39)
-        return f"gs_lanem_sym<double,GS,{'oneXCD' if m.group(1) in ('true', '1') else 'chip'},rpw{m.group(2)},regs{m.group(3)}{',zero' if m.group(4) == '1' else ''}>"
+    if m:                                                                                 # (a 4th argument of 1: the launch ran the zero-iterate plans, tune key 39; 2: in correction form, key 41)
+        return f"gs_lanem_sym<double,GS,{'oneXCD' if m.group(1) in ('true', '1') else 'chip'},rpw{m.group(2)},regs{m.group(3)}{ZSUF.get(m.group(4), '')}>"
     m = re.search(r"gs_line_sym_kernel<(\w+), *(\d+)>", name)
     if m:
         return f"gs_line_sym<{m.group(1)},GS,K{m.group(2)}>"
     m = re.search(r"gs_lanem\w*_kernel<(\w+)(?:, *(\d+))?(?:, *(\d+))?(?:, *(\d+))?>", name)
     if m:
         return (f"gs_lanem<double,GS,{'oneXCD' if m.group(1) in ('true', '1') else 'chip'}" + (f",rpw{m.group(2)}" if m.group(2) else "")
-                + (f",regs{m.group(3)}" if m.group(3) else "") + (",zero" if m.group(4) == "1" else "") + ">")
+                + (f",regs{m.group(3)}" if m.group(3) else "") + ZSUF.get(m.group(4), "") + ">")
     m = re.search(r"gs_line_kernel<(\w+), *(\d+), *(\d+)>", name)
     if m:
         return f"gs_line<{m.group(1)},{EPI[int(m.group(2))]},K{m.group(3)}>"
@@ -70,7 +71,7 @@ def family(k):
         m = re.search(r",(\w+?)(,npl\d|,kz\d|,nu\d)?>", k)
         return "csr", (m.group(1) if m else None)
     if k.startswith("gs_lanem"):
-        return ("gs_lanem_zero" if ",zero>" in k else "gs_lanem"), None
+        return ("gs_lanem_zero" if ",zero>" in k else "gs_lanem_corr" if ",corr>" in k else "gs_lanem"), None
     if k.startswith("gs_lane"):
         return "gs_lane", None
     if k.startswith("gs_line"):
@@ -114,7 +115,7 @@ for f in glob.glob(str(out / "trace" / "**" / "*kernel_trace.csv"), recursive=Tr
         import math
         for (k, g) in list(durs):
             fam, epi = family(k)
-            if fam not in ("gs_lane", "gs_lanem", "gs_lanem_zero", "gs_line", "gs_tile", "gs_gran"):        # (block sweeps: the kernel name carries the block size of its level)
+            if fam not in ("gs_lane", "gs_lanem", "gs_lanem_zero", "gs_lanem_corr", "gs_line", "gs_tile", "gs_gran"):        # (block sweeps: the kernel name carries the block size of its level)
                 continue
             lv = sorted({e["level"] for e in kmap["entries"] if e["family"] == fam and e.get("grid") == g})      # (entries that name THIS grid: a family without grids is told apart otherwise)
             if len(lv) < 2 or len(durs[(k, g)]) < 2 * len(lv):
@@ -143,6 +144,21 @@ for f in glob.glob(str(out / "trace" / "**" / "*kernel_trace.csv"), recursive=Tr
               f"{'kernel [workgroups]':46s} {'lvl':>3s} {'op':>2s} {'role':44s} {'calls':>6s} {'avg_us':>9s} {'alg_MB':>9s} {'alg_GB/s':>9s} {'%peak':>6s} {'strm_MB':>9s} {'strm_GB/s':>9s} {'%peak':>6s} {'%ceil':>6s}"]
         table = []
         used = set()
+
+        def _row(k, g, e, c, avg):
+            a_gbs = e["bytes_alg"] / avg / 1e3
+            s_gbs = e["bytes_streamed"] / avg / 1e3 if e.get("bytes_streamed") else None
+            rec = {"kernel": k, "grid": g, "level": e["level"], "op": e["op"], "role": e["what"], "calls": c, "avg_us": round(avg, 2), "bytes_alg": e["bytes_alg"],
+                   "GBps_alg": round(a_gbs, 1), "pct_peak_alg": round(100 * a_gbs / peak, 2), "bytes_streamed": e.get("bytes_streamed"),
+                   "GBps_streamed": round(s_gbs, 1) if s_gbs else None, "pct_peak_streamed": round(100 * s_gbs / peak, 2) if s_gbs else None,
+                   "pct_ceiling_streamed": round(100 * s_gbs / ceil, 2) if (s_gbs and ceil) else None, "format": e.get("format")}
+            if e.get("dependency_levels"):
+                rec["us_per_dependency_level"] = round(avg / e["dependency_levels"], 3)
+            table.append(rec)
+            rl.append(f"{(k + ' [' + str(g) + ']')[:46]:46s} {e['level']:3d} {e['op']:>2s} {e['what'][:44]:44s} {c:6d} {avg:9.2f} {e['bytes_alg'] / 1e6:9.2f} {a_gbs:9.1f} {100 * a_gbs / peak:6.2f} "
+                      + (f"{e['bytes_streamed'] / 1e6:9.2f} {s_gbs:9.1f} {100 * s_gbs / peak:6.2f} " + (f"{100 * s_gbs / ceil:6.2f}" if ceil else f"{'':6s}") if s_gbs else f"{'-':>9s} {'-':>9s} {'-':>6s} {'-':>6s}")
+                      + (f"   {rec['us_per_dependency_level']} us per dependency level x {e['dependency_levels']}" if e.get("dependency_levels") else ""))
+
         for (k, g), (c, t) in rows:
             fam, epi = family(k)
             if not fam:
@@ -173,18 +189,14 @@ for f in glob.glob(str(out / "trace" / "**" / "*kernel_trace.csv"), recursive=Tr
             used.add(i)
             e = ents[i]
             avg = t / c
-            a_gbs = e["bytes_alg"] / avg / 1e3
-            s_gbs = e["bytes_streamed"] / avg / 1e3 if e.get("bytes_streamed") else None
-            rec = {"kernel": k, "grid": g, "level": e["level"], "op": e["op"], "role": e["what"], "calls": c, "avg_us": round(avg, 2), "bytes_alg": e["bytes_alg"],
-                   "GBps_alg": round(a_gbs, 1), "pct_peak_alg": round(100 * a_gbs / peak, 2), "bytes_streamed": e.get("bytes_streamed"),
-                   "GBps_streamed": round(s_gbs, 1) if s_gbs else None, "pct_peak_streamed": round(100 * s_gbs / peak, 2) if s_gbs else None,
-                   "pct_ceiling_streamed": round(100 * s_gbs / ceil, 2) if (s_gbs and ceil) else None, "format": e.get("format")}
-            if e.get("dependency_levels"):
-                rec["us_per_dependency_level"] = round(avg / e["dependency_levels"], 3)
-            table.append(rec)
-            rl.append(f"{(k + ' [' + str(g) + ']')[:46]:46s} {e['level']:3d} {e['op']:>2s} {e['what'][:44]:44s} {c:6d} {avg:9.2f} {e['bytes_alg'] / 1e6:9.2f} {a_gbs:9.1f} {100 * a_gbs / peak:6.2f} "
-                      + (f"{e['bytes_streamed'] / 1e6:9.2f} {s_gbs:9.1f} {100 * s_gbs / peak:6.2f} " + (f"{100 * s_gbs / ceil:6.2f}" if ceil else f"{'':6s}") if s_gbs else f"{'-':>9s} {'-':>9s} {'-':>6s} {'-':>6s}")
-                      + (f"   {rec['us_per_dependency_level']} us per dependency level x {e['dependency_levels']}" if e.get("dependency_levels") else ""))
+            # roles that run ONE kernel with ONE grid on one operator (the residual in front of the restriction and the residual of the correction
+            # form): the trace cannot tell their launches apart -- the launches are shared out evenly, every role at the common average
+            share = [j for j in cand if j not in used and ents[j].get("shares_launches_with") == e["what"] and ents[j]["level"] == e["level"] and ents[j]["op"] == e["op"]]
+            used.update(share)
+            roles = [e] + [ents[j] for j in share]
+            c_all, c = c, c // len(roles)
+            for e in roles:
+                _row(k, g, e, c + (c_all - c * len(roles) if e is roles[0] else 0), avg)
         # coverage: launches that belong to the cycle = kernels launched at least once per timed iteration (the level-0 convergence-check norm
         # runs once per iteration); share of their time that the table explains
         iters = max([r_["calls"] for r_ in table if "convergence-check" in r_["role"]] or [1])
