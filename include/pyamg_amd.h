@@ -50,6 +50,8 @@ extern "C" {
 #define PAMG_E_TIMEOUT      -6   /* a persistent sweep hit its spin bound (a workgroup it waited for never
                                     ran): the vectors it touched are invalid     */
 /* -7 = PAMG_E_COMM, declared with the sharded cycle below */
+#define PAMG_E_NOCONV       -8   /* an iteration inside a setup kernel hit its cap (pamg_dev_schwarz_blocks: a
+                                    Jacobi SVD after 60 sweeps): the arrays it wrote are invalid */
 
 #define PAMG_F64 0
 #define PAMG_F32 1
@@ -164,6 +166,18 @@ int pamg_overlapping_schwarz_csr_f32(const int32_t *Ap, int Ap_size, const int32
                                      const int32_t *Tp, int Tp_size, const int32_t *Sj, int Sj_size,
                                      const int32_t *Sp, int Sp_size, int32_t nsdomains, int32_t nrows,
                                      int32_t row_start, int32_t row_stop, int32_t row_step);
+/* amg_core::extract_subblocks, relaxation.h:1333-1396: Tx[Tp[d] + r*m + c] = A[Sj[Sp[d]+r], Sj[Sp[d]+c]] (zero where A
+ * stores nothing) for every subdomain d, m = Sp[d+1] - Sp[d]; Tx[0 .. Tp[nsdomains]) is cleared first.  Rows of A and
+ * every subdomain list sorted; of several stored entries with one column the first is copied, like the reference's
+ * walk.  Tp is the caller's.  Subdomains of more than 64 rows: PAMG_E_UNSUPPORTED. */
+int pamg_extract_subblocks_f64(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size,
+                               const double *Ax, int Ax_size, double *Tx, int Tx_size,
+                               const int32_t *Tp, int Tp_size, const int32_t *Sj, int Sj_size,
+                               const int32_t *Sp, int Sp_size, int32_t nsdomains, int32_t nrows);
+int pamg_extract_subblocks_f32(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size,
+                               const float *Ax, int Ax_size, float *Tx, int Tx_size,
+                               const int32_t *Tp, int Tp_size, const int32_t *Sj, int Sj_size,
+                               const int32_t *Sp, int Sp_size, int32_t nsdomains, int32_t nrows);
 /* amg_core::gauss_seidel_indexed, relaxation.h:736-745: the rows Id[row_start], Id[row_start + row_step], ... in that order,
  * in place (a row may be listed more than once) */
 int pamg_gauss_seidel_indexed_f64(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size,
@@ -543,6 +557,23 @@ int pamg_matrix_block_gauss_seidel(pamg_matrix_t A, void *x, const void *b, cons
 
 /* pinv_array on a DEVICE array (m, n, n), in place, stream-ordered */
 int pamg_dev_pinv_array(int dtype, void *AA, int64_t m, int n, int transA, pamg_stream_t s);
+
+/* The setup of overlapping Schwarz (relaxation.schwarz_parameters, relaxation.py:1002-1075) on a resident scalar CSR operator A
+ * with sorted rows: the dense diagonal block A[S_d, S_d] of every subdomain (amg_core::extract_subblocks, bit for bit) and, with
+ * invert != 0, its pseudo-inverse in place -- a one-sided Jacobi SVD per block, singular values <= rank_tol * sigma_max
+ * treated as zero (what LAPACK's gelss does with cond = rank_tol in the reference; equal to it to rounding, not bit for bit).
+ * d_Sp [nsub + 1] / d_Sj: DEVICE, the sorted row list of every subdomain (d_Sp non-decreasing, within d_Sj: the caller's
+ * responsibility; row numbers are checked).  d_Tp [nsub + 1] (DEVICE) receives the exclusive scan of m^2, d_Tx (DEVICE,
+ * Tx_capacity values of dtype) the blocks, row-major.  info: total entries, largest m, Jacobi sweeps of the slowest block,
+ * blocks with a truncated singular value.  Enqueued on s, which is synchronised before the call returns.
+ * PAMG_E_UNSUPPORTED (before anything is written to d_Tp / d_Tx; info[0..1] are set): a subdomain of more than 64 rows, or
+ * more than 2^31 - 1 entries in all.  PAMG_E_ARG: Tx_capacity too small, a row number outside A.  PAMG_E_NOCONV: a block
+ * was not diagonalised after 60 sweeps. */
+int pamg_dev_schwarz_blocks(int dtype, pamg_matrix_t A, int nsub, const int32_t *d_Sp, const int32_t *d_Sj, int32_t *d_Tp,
+                            void *d_Tx, int64_t Tx_capacity, double rank_tol, int invert, pamg_stream_t s, int64_t info[4]);
+/* the same with HOST Sp / Sj / Tp / Tx: uploads the lists, downloads the blocks (default stream, synchronous) */
+int pamg_schwarz_blocks(int dtype, pamg_matrix_t A, int nsub, const int32_t *Sp, const int32_t *Sj, int32_t *Tp, void *Tx,
+                        int64_t Tx_capacity, double rank_tol, int invert, int64_t info[4]);
 
 /* BLAS-1 on DEVICE vectors */
 int pamg_vec_sumsq(int dtype, int64_t n, const void *x, double *out_sumsq, pamg_stream_t s);

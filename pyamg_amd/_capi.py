@@ -16,7 +16,7 @@ LIB_PATH = Path(os.environ.get("PAMG_LIB", PKG / "libpyamg_amd.so"))    # PAMG_L
 
 OK = 0
 E_ARG, E_UNSUPPORTED, E_NODEVICE, E_STATE, E_ALLOC = -1, -2, -3, -4, -5
-E_TIMEOUT, E_COMM = -6, -7
+E_TIMEOUT, E_COMM, E_NOCONV = -6, -7, -8
 F64, F32 = 0, 1
 CSR, BSR = 0, 1
 SPMV_SET, SPMV_ACC, SPMV_RESID, SPMV_AXPBY, SPMV_ACC_AXPBY = 0, 1, 2, 3, 4
@@ -92,6 +92,7 @@ def _declare(lib):
         f(f"pamg_sor_gauss_seidel_{sfx}", *csr5, _i, _i, _i, ct)
         f(f"pamg_overlapping_schwarz_csr_{sfx}", *csr5, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i)
         f(f"pamg_gauss_seidel_indexed_{sfx}", *csr5, _vp, _i, _i, _i, _i)
+        f(f"pamg_extract_subblocks_{sfx}", _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i)
         f(f"pamg_bsr_gauss_seidel_{sfx}", *csr5, _i, _i, _i, _i)
         f(f"pamg_jacobi_{sfx}", *csr5, _vp, _i, _i, _i, _i, _vp, _i)
         f(f"pamg_bsr_jacobi_{sfx}", *csr5, _vp, _i, _i, _i, _i, _i, _vp, _i)
@@ -105,6 +106,8 @@ def _declare(lib):
     f("pamg_pinv_array_f64", _vp, _i, _i, _i, C.c_char)
     f("pamg_pinv_array_f32", _vp, _i, _i, _i, C.c_char)
     f("pamg_dev_pinv_array", _i, _vp, C.c_int64, _i, _i, _vp)
+    f("pamg_dev_schwarz_blocks", _i, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, _d, _i, _vp, P(C.c_int64))
+    f("pamg_schwarz_blocks", _i, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, _d, _i, P(C.c_int64))
     f("pamg_bsr_transpose_f64", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp)
     f("pamg_bsr_transpose_f32", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp)
     f("pamg_standard_aggregation", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, P(_i))

@@ -745,8 +745,20 @@ def _rho_or_reference(reference_fn):
     return approximate_spectral_radius_
 
 
+def _schwarz_parameters_or_reference(reference_fn):
+    """the patched ``schwarz_parameters``: real CSR operators get their subdomain blocks from the device (subdomains above its cap
+    from the host, with one warning: relaxation.schwarz_parameters(device=True)); what the device path does not take -- complex
+    operators, other formats -- stays with the reference function that was patched out"""
+    def schwarz_parameters(A, subdomain=None, subdomain_ptr=None, inv_subblock=None, inv_subblock_ptr=None):
+        from .relaxation import schwarz_parameters as device_fn
+        if sp.issparse(A) and A.format == "csr" and A.dtype in (np.float64, np.float32) and A.has_sorted_indices:
+            return device_fn(A, subdomain, subdomain_ptr, inv_subblock, inv_subblock_ptr, device=True)
+        return reference_fn(A, subdomain, subdomain_ptr, inv_subblock, inv_subblock_ptr)
+    return schwarz_parameters
+
+
 @contextlib.contextmanager
-def device_setup(pyamg, prolongation=True, products=True, aggregation=False):
+def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -761,7 +773,11 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False):
     patched too.  ``aggregation=True`` also routes ``standard_aggregation`` to the device: the same aggregates, integer for
     integer -- but the reference's greedy pass costs ~6 ns per node on one host core, while the device version is a
     topological traversal of launch-latency-bound rounds (measured: 0.08 vs 0.05 s at 8 M nodes, 0.24 vs 0.03 s on a
-    30-entries-per-row SA level), so it is off by default and meant for pipelines that keep the strength matrix in HBM."""
+    30-entries-per-row SA level), so it is off by default and meant for pipelines that keep the strength matrix in HBM.
+    ``schwarz=True`` patches ``schwarz_parameters`` in ``<pyamg>.relaxation.relaxation`` -- the attribute both ``smoothing.setup_schwarz`` and
+    ``relaxation.schwarz`` resolve -- with the device version (``relaxation.schwarz_parameters(device=True)``).  Off by default: the
+    inverted blocks then equal LAPACK's to rounding (a one-sided Jacobi SVD with the same rank rule), not bit for bit, so a hierarchy
+    set up this way no longer reproduces the reference's iterates to the last bit."""
     import importlib
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
@@ -773,7 +789,8 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False):
                           ("aggregation.smooth", "approximate_spectral_radius", approximate_spectral_radius),
                           ("relaxation.smoothing", "approximate_spectral_radius", approximate_spectral_radius),
                           ("relaxation.chebyshev", "approximate_spectral_radius", approximate_spectral_radius),
-                          ("util.linalg", "approximate_spectral_radius", approximate_spectral_radius)):
+                          ("util.linalg", "approximate_spectral_radius", approximate_spectral_radius),
+                          ("relaxation.relaxation", "schwarz_parameters", None)):
         try:
             m = importlib.import_module(f"{pyamg.__name__}.{mod}")
         except ImportError:     # pragma: no cover
@@ -782,11 +799,15 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False):
             continue
         if not aggregation and name == "standard_aggregation":
             continue
+        if not schwarz and name == "schwarz_parameters":
+            continue
         if hasattr(m, name):
             old = getattr(m, name)
             targets.append((m, name, old))
             if name == "approximate_spectral_radius":
                 setattr(m, name, _rho_or_reference(old))
+            elif name == "schwarz_parameters":
+                setattr(m, name, _schwarz_parameters_or_reference(old))
             elif name in ("standard_aggregation", "fit_candidates"):
                 setattr(m, name, _device_or_reference(fn, old))
             else:

@@ -14,7 +14,7 @@ import numpy as np
 from . import _capi as capi
 
 __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_gauss_seidel",
-           "jacobi", "bsr_jacobi", "block_jacobi", "block_jacobi_indexed", "block_gauss_seidel", "jacobi_indexed", "gauss_seidel_indexed", "overlapping_schwarz_csr", "gauss_seidel_ne",
+           "jacobi", "bsr_jacobi", "block_jacobi", "block_jacobi_indexed", "block_gauss_seidel", "jacobi_indexed", "gauss_seidel_indexed", "overlapping_schwarz_csr", "extract_subblocks", "gauss_seidel_ne",
            "gauss_seidel_nr", "jacobi_ne", "pinv_array", "standard_aggregation", "fit_candidates"]
 
 
@@ -154,6 +154,20 @@ def overlapping_schwarz_csr(Ap, Aj, Ax, x, b, Tx, Tp, Sj, Sp, nsdomains, nrows, 
                                                                        capi.ptr(Sp), Sp.size, int(nsdomains), int(nrows),
                                                                        int(row_start), int(row_stop), int(row_step)),
                "overlapping_schwarz_csr")
+
+
+def extract_subblocks(Ap, Aj, Ax, Tx, Tp, Sj, Sp, nsdomains, nrows):
+    """amg_core.extract_subblocks (relaxation.h:1333-1396): Tx <- the dense diagonal block of every subdomain, at the caller's
+    offsets Tp.  Subdomains of at most 64 rows."""
+    _idx(Ap, Aj)
+    for a, n in ((Tp, "Tp"), (Sj, "Sj"), (Sp, "Sp")):
+        if a.dtype != np.int32:
+            raise TypeError(f"extract_subblocks(): incompatible function arguments ({n} must be int32)")
+    s = _sfx(Ax, Tx)
+    p = capi.ptr
+    capi.check(getattr(capi.lib(), f"pamg_extract_subblocks_{s}")(p(Ap), Ap.size, p(Aj), Aj.size, p(Ax), Ax.size, p(Tx), Tx.size,
+                                                                 p(Tp), Tp.size, p(Sj), Sj.size, p(Sp), Sp.size, int(nsdomains),
+                                                                 int(nrows)), "extract_subblocks")
 
 
 def gauss_seidel_indexed(Ap, Aj, Ax, x, b, Id, row_start, row_stop, row_step):

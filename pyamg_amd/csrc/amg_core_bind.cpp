@@ -46,6 +46,7 @@ template <typename T> struct L1;
         static constexpr auto gauss_seidel_indexed = pamg_gauss_seidel_indexed_##S;        \
         static constexpr auto overlapping_schwarz_csr = pamg_overlapping_schwarz_csr_##S;  \
         static constexpr auto pinv_array = pamg_pinv_array_##S;                            \
+        static constexpr auto extract_subblocks = pamg_extract_subblocks_##S;              \
         static constexpr auto fit_candidates = pamg_fit_candidates_##S;                    \
     };
 PAMG_L1(double, f64)
@@ -116,6 +117,10 @@ void bind(py::module_ &m)
                                         row_start, row_stop, row_step), "overlapping_schwarz_csr");
     }, nc("Ap"), nc("Aj"), nc("Ax"), nc("x"), nc("b"), nc("Tx"), nc("Tp"), nc("Sj"), nc("Sp"), py::arg("nsdomains"), py::arg("nrows"),
        py::arg("row_start"), py::arg("row_stop"), py::arg("row_step"));
+    m.def("extract_subblocks", [](Idx &Ap, Idx &Aj, Vec<T> &Ax, Vec<T> &Tx, Idx &Tp, Idx &Sj, Idx &Sp, int nsdomains, int nrows) {
+        done(F::extract_subblocks(Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), Tx.mutable_data(), len(Tx), Tp.data(), len(Tp),
+                                  Sj.data(), len(Sj), Sp.data(), len(Sp), nsdomains, nrows), "extract_subblocks");
+    }, nc("Ap"), nc("Aj"), nc("Ax"), nc("Tx"), nc("Tp"), nc("Sj"), nc("Sp"), py::arg("nsdomains"), py::arg("nrows"));
     m.def("gauss_seidel_indexed", [](Idx &Ap, Idx &Aj, Vec<T> &Ax, Vec<T> &x, Vec<T> &b, Idx &Id, int row_start, int row_stop, int row_step) {
         done(F::gauss_seidel_indexed(Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), x.mutable_data(), len(x), b.data(), len(b),
                                      Id.data(), len(Id), row_start, row_stop, row_step), "gauss_seidel_indexed");

@@ -266,6 +266,38 @@ int l1_schwarz(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, c
     return st;
 }
 
+// amg_core::extract_subblocks (relaxation.h:1333-1396); the caller's Tp is honoured
+template <typename T>
+int l1_extract_subblocks(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const T *Ax, int Ax_size, T *Tx, int Tx_size,
+                         const int32_t *Tp, int Tp_size, const int32_t *Sj, int Sj_size, const int32_t *Sp, int Sp_size, int nsdomains, int nrows)
+{
+    if (!Tp || !Sp || nsdomains < 0 || Sp_size < nsdomains + 1 || Tp_size < nsdomains + 1 || Tx_size < 0 || Sj_size < 0) return PAMG_E_ARG;
+    PAMG_TRY(check_csr(Ap, Ap_size, Aj_size, Ax_size, 1));
+    const int n = Ap_size - 1;
+    if (n != nrows) return PAMG_E_ARG;
+    if (Sp[0] < 0 || Sp[nsdomains] > Sj_size || Tp[nsdomains] < 0 || Tp[nsdomains] > Tx_size) return PAMG_E_ARG;
+    if ((Tx_size && !Tx) || (Sp[nsdomains] && !Sj)) return PAMG_E_ARG;
+    int mmax = 0;
+    for (int d = 0; d < nsdomains; ++d) {
+        const int64_t m = (int64_t)Sp[d + 1] - Sp[d];
+        if (m < 0 || Tp[d] < 0 || (int64_t)Tp[d] + m * m > (int64_t)Tp[nsdomains]) return PAMG_E_ARG;
+        mmax = std::max<int>(mmax, (int)std::min<int64_t>(m, INT32_MAX));
+    }
+    if (mmax > 64) return PAMG_E_UNSUPPORTED;
+    std::lock_guard<std::mutex> lock(l1_mu);
+    MatGuard g;
+    PAMG_TRY(l1_acquire(g, dt<T>(), PAMG_CSR, n, n, 1, 1, Ap, Aj, Ax));
+    DevBuf dSp, dSj, dTp, dTx;
+    PAMG_TRY(dSp.put(Sp, sizeof(int32_t) * ((size_t)nsdomains + 1)));
+    PAMG_TRY(dSj.put(Sj, sizeof(int32_t) * (size_t)Sp[nsdomains]));
+    PAMG_TRY(dTp.put(Tp, sizeof(int32_t) * ((size_t)nsdomains + 1)));
+    PAMG_TRY(dTx.alloc(sizeof(T) * (size_t)Tp[nsdomains]));
+    int64_t info[4];
+    PAMG_TRY(schwarz_blocks_device(dt<T>(), g.A, nsdomains, (const int *)dSp.p, (const int *)dSj.p, (int *)dTp.p, dTx.p, Tp[nsdomains], 0.0, 0, true,
+                                   nullptr, info));
+    return dTx.get(Tx, sizeof(T) * (size_t)Tp[nsdomains]);
+}
+
 // jacobi / bsr_jacobi: the device sweep relaxes every row out of place; only the rows of the
 // (row_start,row_stop,row_step) slice are copied back, as in the reference.
 template <typename T>
@@ -507,6 +539,7 @@ const char *pamg_status_string(int st)
         case PAMG_E_ALLOC: return "host allocation failed";
         case PAMG_E_TIMEOUT: return "a persistent sweep hit its spin bound; results are invalid";
         case PAMG_E_COMM: return "RCCL / transport failure in the sharded cycle";
+        case PAMG_E_NOCONV: return "an iteration of a setup kernel did not converge; results are invalid";
     }
     if (st > 0) return hipGetErrorString((hipError_t)st);
     return "unknown error";
@@ -733,6 +766,12 @@ int pamg_event_elapsed_ms(pamg_event_t a, pamg_event_t b, float *ms) { return ms
                                            int32_t row_stop, int32_t row_step)                                  \
     { return l1_schwarz<T>(Ap, Ap_size, Aj, Aj_size, Ax, Ax_size, x, x_size, b, b_size, Tx, Tx_size, Tp, Tp_size,\
                            Sj, Sj_size, Sp, Sp_size, nsdomains, nrows, row_start, row_stop, row_step); }        \
+    int pamg_extract_subblocks_##SFX(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size,            \
+                                     const T *Ax, int Ax_size, T *Tx, int Tx_size, const int32_t *Tp,           \
+                                     int Tp_size, const int32_t *Sj, int Sj_size, const int32_t *Sp,            \
+                                     int Sp_size, int32_t nsdomains, int32_t nrows)                             \
+    { return l1_extract_subblocks<T>(Ap, Ap_size, Aj, Aj_size, Ax, Ax_size, Tx, Tx_size, Tp, Tp_size, Sj,       \
+                                     Sj_size, Sp, Sp_size, nsdomains, nrows); }                                 \
     int pamg_sor_gauss_seidel_##SFX(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size,             \
                                     const T *Ax, int Ax_size, T *x, int x_size, const T *b, int b_size,         \
                                     int32_t row_start, int32_t row_stop, int32_t row_step, T omega)             \

@@ -274,6 +274,9 @@ int schwarz_sweep(pamg_schwarz_s *h, void *x, const void *b, int start, int stop
 int schwarz_prepare(pamg_schwarz_s *h, int sweep);
 int schwarz_error(pamg_schwarz_s *h, bool *error);
 void schwarz_level_launches(pamg_schwarz_s *h);
+// pamg_schwarz_setup.hip
+int schwarz_blocks_device(int dtype, pamg_matrix_s *A, int nsub, const int *d_Sp, const int *d_Sj, int *d_Tp, void *d_Tx,
+                          int64_t Tx_capacity, double rank_tol, int invert, bool tp_given, hipStream_t s, int64_t info[4]);
 // launch wrappers implemented in pamg_matrix.hip
 int stream_launch(pamg_matrix_s *A, int epi, const void *x, const void *b, void *y, double c,
                   double omega, double *partial, hipStream_t s);

@@ -93,6 +93,8 @@ class SmootherSpec:
     subdomain_ptr: Optional[np.ndarray] = None
     inv_subblock: Optional[np.ndarray] = None   # schwarz: inverted diagonal blocks, row-major, one after another
     inv_subblock_ptr: Optional[np.ndarray] = None
+    blocks_by: str = "reference"                # schwarz: what built inv_subblock -- 'reference' (LAPACK gelss, the reference's blocks) or 'device'
+    setup_report: Optional[dict] = None         #   the device setup's report (relaxation._schwarz_blocks_device)
     tol: float = 0.0                            # Krylov smoothers
     restart: int = 0
 
@@ -162,7 +164,7 @@ def _closure_vars(fn) -> dict:
     return {n: c.cell_contents for n, c in zip(names, cells)}
 
 
-def smoother_spec(fn, A) -> SmootherSpec:
+def smoother_spec(fn, A, schwarz_setup="reference") -> SmootherSpec:
     """Translate one smoother callable ``fn(A, x, b)`` into a SmootherSpec.
 
     Dispatch is on the *wrapped* function (``partial.func``) or on the closure contents,
@@ -228,8 +230,12 @@ def smoother_spec(fn, A) -> SmootherSpec:
         if Acsr is None:
             Acsr = A.tocsr()
         Acsr.sort_indices()
-        sub, sptr, inv, iptr = schwarz_parameters(Acsr, cv["subdomain"], cv["subdomain_ptr"], None, None)
-        return _schwarz_spec(lvl, A, int(cv["iterations"]), cv["sweep"], sub, sptr, inv, iptr, shown, Acsr=Acsr)
+        sub, sptr, inv, iptr = schwarz_parameters(Acsr, cv["subdomain"], cv["subdomain_ptr"], None, None, device=schwarz_setup == "device")
+        sm = _schwarz_spec(lvl, A, int(cv["iterations"]), cv["sweep"], sub, sptr, inv, iptr, shown, Acsr=Acsr)
+        report = getattr(Acsr, "schwarz_setup_report", None)
+        if schwarz_setup == "device" and report is not None:         # (blocks cached on Acsr by an earlier host setup are rebuilt at upload)
+            sm.blocks_by, sm.setup_report = "device", dict(report)
+        return sm
     if shown in KRYLOV_SMOOTHERS and "tol" in cv and "maxiter" in cv:
         return _krylov_spec(shown, A, cv.get("tol"), cv.get("maxiter"), cv.get("restart"), cv)
     if shown == "none" and not cv:                                  # smoothing.py setup_none: def none(A, x, b): pass
@@ -430,8 +436,9 @@ def _coarse_operator(ml, A_c) -> Tuple[str, Optional[np.ndarray], str]:
 
 
 # --------------------------------------------------------------------------- entry point
-def extract(ml) -> HierarchySpec:
-    """Read a constructed reference ``MultilevelSolver`` into a HierarchySpec."""
+def extract(ml, schwarz_setup="reference") -> HierarchySpec:
+    """Read a constructed reference ``MultilevelSolver`` into a HierarchySpec.  ``schwarz_setup='device'``: blocks of a
+    ``strength_based_schwarz`` smoother that are not cached yet are built by ``schwarz_parameters(device=True)``."""
     levels = ml.levels
     if len(levels) == 0:
         raise ValueError("empty hierarchy")
@@ -444,8 +451,8 @@ def extract(ml) -> HierarchySpec:
         if i < len(levels) - 1:
             ls.P = sparse_op(lvl.P)
             ls.R = sparse_op(lvl.R)
-            ls.pre = smoother_spec(getattr(lvl, "presmoother", None), lvl.A)
-            ls.post = smoother_spec(getattr(lvl, "postsmoother", None), lvl.A)
+            ls.pre = smoother_spec(getattr(lvl, "presmoother", None), lvl.A, schwarz_setup)
+            ls.post = smoother_spec(getattr(lvl, "postsmoother", None), lvl.A, schwarz_setup)
             kinds = {sm.kind for sm in (ls.pre, ls.post) if sm is not None}
             if kinds & {"gauss_seidel_ne", "jacobi_ne"} and lvl.A.format == "csr" and not lvl.A.has_sorted_indices:
                 # the reference's wrappers call get_diagonal(lvl.Acsr) -- lvl.Acsr IS lvl.A for a CSR level -- which

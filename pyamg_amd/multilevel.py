@@ -275,7 +275,7 @@ class DeviceMatrix:
         self.free()
 
 
-def _set_smoother(lib, S, level, which, s: Optional[SmootherSpec], dtype, aux, fast=False):
+def _set_smoother(lib, S, level, which, s: Optional[SmootherSpec], dtype, aux, fast=False, schwarz=None):
     if s is None or s.kind == "none":
         capi.check(lib.pamg_solver_set_smoother(S, level, which, 0, 0, 1.0, 0, None, 0, None, 1), "set_smoother")
         return
@@ -322,7 +322,21 @@ def _set_smoother(lib, S, level, which, s: Optional[SmootherSpec], dtype, aux, f
             Ar = DeviceMatrix(s.Ar)
             aux.append(Ar)                      # borrowed by the solver: keep it alive
         Sp, Sj = np.ascontiguousarray(s.subdomain_ptr, dtype=np.int32), np.ascontiguousarray(s.subdomain, dtype=np.int32)
-        Tp, Tx = np.ascontiguousarray(s.inv_subblock_ptr, dtype=np.int32), np.ascontiguousarray(s.inv_subblock, dtype=dtype)
+        report = {"path": s.blocks_by, **(s.setup_report or {})}
+        if schwarz is not None and schwarz["setup"] == "device" and s.blocks_by != "device":
+            # the blocks are rebuilt on the device from the operator the sweep runs on and the smoother's subdomains
+            from .relaxation import _schwarz_blocks_device
+            last = schwarz.get("last")
+            if last is not None and last[0] == level and np.array_equal(last[1], Sj) and np.array_equal(last[2], Sp):
+                Tx, Tp, report = last[3:]       # pre- and post-smoother over the same subdomains: built once
+            else:
+                host_op = s.Ar if s.Ar is not None else schwarz["A_host"]
+                Tx, Tp, report = _schwarz_blocks_device(host_op.to_scipy(), Sj, Sp, dA=Ar if Ar is not None else schwarz["A_dev"])
+                schwarz["last"] = (level, Sj, Sp, Tx, Tp, report)
+        else:
+            Tp, Tx = np.ascontiguousarray(s.inv_subblock_ptr, dtype=np.int32), np.ascontiguousarray(s.inv_subblock, dtype=dtype)
+        if schwarz is not None:
+            schwarz["reports"].setdefault(level, {})["pre" if which == 0 else "post"] = report
         capi.check(lib.pamg_solver_set_schwarz_smoother(S, level, which, int(s.iterations), capi.SWEEP.get(s.sweep, 0),
                                                         Ar.handle if Ar else None, Sp.size - 1, capi.ptr(Sp), capi.ptr(Sj),
                                                         capi.ptr(Tp), capi.ptr(Tx)),
@@ -368,6 +382,10 @@ class DeviceMultilevelSolver:
         a wave share a row (parallel partial sums, multiplication by 1/a_ii): the same iterates up to rounding -- residual
         norms agree with the reference to ~1e-15 relative per cycle (BASELINE's bar is 1e-10) -- at about half the
         latency per dependency level.  Every other kernel is bit-identical to the reference in both modes.
+    schwarz_setup : 'reference' (default) or 'device' -- the inverted subdomain blocks of Schwarz smoothers.  'reference' ships the blocks the
+        hierarchy holds (LAPACK gelss: the reference's own).  'device' builds them on the GPU from the operator the sweep runs on and the
+        smoother's subdomains (``relaxation.schwarz_parameters(device=True)``: equal to the reference's to rounding, not bit for bit);
+        ``stats()['schwarz_setup']`` says per level what was done.
     renumber : bool, number the unknowns of the large interior levels blob by blob on the DEVICE copy of the hierarchy (renumber.py;
         default OFF, PAMG_RENUMBER=1 enables -- it costs about as much host time as the upload of the level and pays back only over
         hundreds of cycles: DESIGN 3, round 6).  Speed only: rows are moved and columns renamed, row sums keep their stored order, the
@@ -376,15 +394,20 @@ class DeviceMultilevelSolver:
     """
 
     def __init__(self, ml, device: Optional[int] = None, graph: bool = True, autotune: Optional[bool] = None,
-                 level_tune=None, order: Optional[str] = None, strict: bool = True, renumber: Optional[bool] = None):
+                 level_tune=None, order: Optional[str] = None, strict: bool = True, renumber: Optional[bool] = None,
+                 schwarz_setup: str = "reference"):
         import os
         self.fallback = None
+        if schwarz_setup not in ("reference", "device"):
+            raise ValueError("schwarz_setup must be 'reference' or 'device'")
+        self.schwarz_setup, self._schwarz_reports = schwarz_setup, {}
         if not strict:
             # "unsupported smoothers / cycles / coarse solvers => transparent fallback to the wrapped ml (or an explicit
             # NotImplementedError if strict=True)".  The fallback is the CALLER's own solver object -- never the oracle, never a
             # CPU restatement of ours -- and it is announced once.
             try:
-                self.__init__(ml, device=device, graph=graph, autotune=autotune, level_tune=level_tune, order=order, strict=True, renumber=renumber)
+                self.__init__(ml, device=device, graph=graph, autotune=autotune, level_tune=level_tune, order=order, strict=True, renumber=renumber,
+                              schwarz_setup=schwarz_setup)
                 return
             except NotImplementedError as e:
                 if isinstance(ml, HierarchySpec) or not hasattr(ml, "solve"):
@@ -411,7 +434,7 @@ class DeviceMultilevelSolver:
         self._device, self._graph, self._autotune, self._level_tune = device, graph, autotune, level_tune
         # reading the hierarchy comes first: what is not on the device path is refused (NotImplementedError) before any device is touched
         self.ml = None if isinstance(ml, HierarchySpec) else ml
-        self.spec = ml if isinstance(ml, HierarchySpec) else extract(ml)
+        self.spec = ml if isinstance(ml, HierarchySpec) else extract(ml, schwarz_setup)
         lib = capi.lib()
         if renumber is None:
             renumber = os.environ.get("PAMG_RENUMBER", "0") != "0"
@@ -485,12 +508,14 @@ class DeviceMultilevelSolver:
             capi.check(lib.pamg_solver_add_level(h, A.handle, P.handle if P else None, R.handle if R else None),
                        "pamg_solver_add_level")
             if i < nlev - 1:
-                _set_smoother(lib, h, i, 0, L.pre, self.dtype, self._aux, fast=order == "fast")
-                _set_smoother(lib, h, i, 1, L.post, self.dtype, self._aux, fast=order == "fast")
+                sw = {"setup": schwarz_setup, "A_host": L.A, "A_dev": A, "reports": self._schwarz_reports}
+                _set_smoother(lib, h, i, 0, L.pre, self.dtype, self._aux, fast=order == "fast", schwarz=sw)
+                _set_smoother(lib, h, i, 1, L.post, self.dtype, self._aux, fast=order == "fast", schwarz=sw)
         n_c = self.spec.levels[-1].A.shape[0]
         if self.spec.coarse_kind == "relax":
             # multilevel.py:765-782: sweeps of a relaxation method from x = 0 -- the smoother slot of the coarsest level
-            _set_smoother(lib, h, nlev - 1, 0, self.spec.coarse_smoother, self.dtype, self._aux, fast=order == "fast")
+            _set_smoother(lib, h, nlev - 1, 0, self.spec.coarse_smoother, self.dtype, self._aux, fast=order == "fast",
+                          schwarz={"setup": schwarz_setup, "A_host": dev_spec.levels[-1].A, "A_dev": self.A[-1], "reports": self._schwarz_reports})
             capi.check(lib.pamg_solver_set_coarse_relax(h), "set_coarse_relax")
         elif self.spec.coarse_kind == "host":
             # multilevel.py:752-762 (Krylov names other than 'cg' / 'gmres') and :786-788 (callables): the caller's own solver
@@ -547,8 +572,14 @@ class DeviceMultilevelSolver:
         self._need_device("stats")
         a = (C.c_int64 * 8)()
         capi.check(capi.lib().pamg_solver_stats(self.handle, a), "pamg_solver_stats")
-        return {"levels": int(a[0]), "gs_level_launches": int(a[1]), "hbm_bytes": int(a[2]), "graphs": int(a[3]),
-                "sweep_timeouts_recovered": int(a[4])}
+        out = {"levels": int(a[0]), "gs_level_launches": int(a[1]), "hbm_bytes": int(a[2]), "graphs": int(a[3]),
+               "sweep_timeouts_recovered": int(a[4])}
+        if self._schwarz_reports:
+            # levels smoothed by Schwarz: what built the inverted blocks of the pre- / post-smoother ('reference': the blocks of the
+            # hierarchy as given; 'device': pamg_schwarz_blocks, with its info -- entries, largest block, Jacobi sweeps of the slowest
+            # block, blocks with a truncated singular value, subdomains handed to the host)
+            out["schwarz_setup"] = {lvl: {k: dict(v) for k, v in r.items()} for lvl, r in sorted(self._schwarz_reports.items())}
+        return out
 
     def cycle_device(self, xd, bd, cycle="V", cycles_per_level=1, stream=None):
         """One cycle on DEVICE vectors (DeviceArray) in place."""

@@ -177,11 +177,106 @@ def _subdomain_blocks(A, subdomain, subdomain_ptr):
     return out, ptr
 
 
-def schwarz_parameters(A, subdomain=None, subdomain_ptr=None, inv_subblock=None, inv_subblock_ptr=None):
+def _rank_tol(dtype):
+    """the reference's set_tol (util/params.py): the rank tolerance gelss gets in schwarz_parameters"""
+    single = np.dtype(dtype).char.lower() == "f"
+    return (1e3 * np.finfo(np.single).eps) if single else (1e6 * np.finfo(np.double).eps)
+
+
+def _invert_blocks_host(dtype, inv_subblock, inv_subblock_ptr, subdomain_ptr):
+    """every extracted block replaced by its pseudo-inverse: one LAPACK gelss call per subdomain, like the reference"""
+    import scipy.linalg as la
+    rank_tol = _rank_tol(dtype)
+    gelss, = la.get_lapack_funcs(["gelss"], (np.ones((1,), dtype=dtype),))
+    for d, m in enumerate(np.diff(subdomain_ptr)):
+        blk = inv_subblock[inv_subblock_ptr[d]:inv_subblock_ptr[d + 1]]
+        # pseudo-inverse of the block: least-squares solve against the identity, like the reference does it
+        blk[:] = np.ravel(gelss(blk.reshape(m, m), np.eye(m, m, dtype=dtype), cond=rank_tol, overwrite_a=True, overwrite_b=True)[1])
+
+
+DEVICE_BLOCK_CAP = 64             # largest subdomain pamg_dev_schwarz_blocks takes
+
+
+def _take_subdomains(subdomain, subdomain_ptr, ids):
+    """the row lists of the subdomains ``ids``, one after another, with their own pointer"""
+    sizes = np.diff(subdomain_ptr)[ids].astype(np.int64)
+    ptr = np.zeros(ids.size + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum(sizes)
+    take = np.repeat(np.asarray(subdomain_ptr, dtype=np.int64)[ids] - ptr[:-1], sizes) + np.arange(ptr[-1])
+    return np.asarray(subdomain)[take], ptr
+
+
+def _device_blocks(dA, dtype, subdomain, subdomain_ptr, invert=True):
+    """pamg_schwarz_blocks on the resident operator dA: (Tx, Tp, info[4]) -- the dense diagonal blocks of the subdomains (inverted
+    when ``invert``), their int32 pointer, and [entries, largest m, Jacobi sweeps of the slowest block, blocks with a truncated
+    singular value]."""
+    import ctypes as C
+    Sp = np.ascontiguousarray(subdomain_ptr, dtype=np.int32)
+    Sj = np.ascontiguousarray(subdomain, dtype=np.int32)
+    m = np.diff(Sp).astype(np.int64)
+    total = int(np.sum(m * m))
+    Tp = np.zeros(Sp.size, dtype=np.int32)
+    Tx = np.zeros(total, dtype=dtype)
+    info = (C.c_int64 * 4)()
+    st = capi.lib().pamg_schwarz_blocks(capi.dtype_code(dtype), dA.handle, Sp.size - 1, capi.ptr(Sp), capi.ptr(Sj), capi.ptr(Tp), capi.ptr(Tx),
+                                        total, float(_rank_tol(dtype)), int(bool(invert)), info)
+    if st == capi.E_NOCONV:
+        raise RuntimeError("pamg_schwarz_blocks: the Jacobi SVD of a subdomain block did not converge; no blocks were produced")
+    capi.check(st, "pamg_schwarz_blocks")
+    return Tx, Tp, [int(v) for v in info]
+
+
+def _schwarz_blocks_device(A, subdomain, subdomain_ptr, dA=None):
+    """The inverted diagonal blocks of the subdomains of A (CSR, sorted rows) built on the device: (inv_subblock, inv_subblock_ptr,
+    report).  Subdomains of more than DEVICE_BLOCK_CAP rows are inverted by the host code instead, announced by ONE warning.
+    ``dA``: A as a resident DeviceMatrix (uploaded here when None)."""
+    if np.dtype(A.dtype).type not in (np.float64, np.float32):
+        raise NotImplementedError(f"schwarz_parameters(device=True): dtype {A.dtype} is not on the device path")
+    sizes = np.diff(subdomain_ptr).astype(np.int64)
+    big = np.flatnonzero(sizes > DEVICE_BLOCK_CAP)
+    own = dA is None
+    if own:
+        dA = DeviceMatrix(sparse_op(A))
+    try:
+        if big.size == 0:
+            Tx, Tp, info = _device_blocks(dA, A.dtype, subdomain, subdomain_ptr)
+        else:
+            small = np.flatnonzero(sizes <= DEVICE_BLOCK_CAP)
+            Tp = np.zeros(sizes.size + 1, dtype=np.int64)
+            Tp[1:] = np.cumsum(sizes * sizes)
+            if Tp[-1] > np.iinfo(np.int32).max:
+                raise NotImplementedError("schwarz_parameters(device=True): more than 2^31 - 1 block entries")
+            Tx = np.zeros(int(Tp[-1]), dtype=A.dtype)
+            Sj_s, Sp_s = _take_subdomains(subdomain, subdomain_ptr, small)
+            Tx_s, _, info = _device_blocks(dA, A.dtype, Sj_s, Sp_s)
+            Sj_b, Sp_b = _take_subdomains(subdomain, subdomain_ptr, big)
+            Tx_b, Tp_b = _subdomain_blocks(A, Sj_b, Sp_b)
+            _invert_blocks_host(A.dtype, Tx_b, Tp_b, Sp_b)
+            for ids, part in ((small, Tx_s), (big, Tx_b)):
+                n2 = (sizes * sizes)[ids]
+                at = np.zeros(ids.size + 1, dtype=np.int64)
+                at[1:] = np.cumsum(n2)
+                Tx[np.repeat(Tp[ids] - at[:-1], n2) + np.arange(at[-1])] = part
+            warn(f"schwarz_parameters(device=True): {big.size} of {sizes.size} subdomains have more than {DEVICE_BLOCK_CAP} rows; their "
+                 "blocks were inverted on the host", RuntimeWarning, stacklevel=3)
+            Tp = Tp.astype(np.int32)
+            info[1] = int(sizes.max())
+    finally:
+        if own:
+            dA.free()
+    report = {"path": "device", "entries": int(Tp[-1]), "largest": info[1], "sweeps": info[2], "truncated": info[3], "on_host": int(big.size)}
+    return Tx, Tp, report
+
+
+def schwarz_parameters(A, subdomain=None, subdomain_ptr=None, inv_subblock=None, inv_subblock_ptr=None, device=False):
     """The subdomains and inverted diagonal blocks of Schwarz relaxation (reference: relaxation.py:1002-1075): by default
     one subdomain per row, its sparsity pattern; every block inverted by LAPACK's gelss with the reference's rank
-    tolerance; cached on the matrix as ``A.schwarz_parameters`` like the reference caches it."""
-    import scipy.linalg as la
+    tolerance; cached on the matrix as ``A.schwarz_parameters`` like the reference caches it.
+
+    ``device=True`` builds the blocks on the GPU instead (``pamg_schwarz_blocks``: extraction bit for bit, pseudo-inverses by a
+    one-sided Jacobi SVD with the same rank rule -- equal to gelss' to rounding, not bit for bit).  Same cache rule, same 4-tuple;
+    A must be CSR with sorted rows.  Subdomains of more than 64 rows are inverted on the host, announced by one warning; what was
+    done is left in ``A.schwarz_setup_report``."""
     cached = getattr(A, "schwarz_parameters", None)
     if cached is not None:
         given = subdomain is not None and subdomain_ptr is not None
@@ -190,27 +285,29 @@ def schwarz_parameters(A, subdomain=None, subdomain_ptr=None, inv_subblock=None,
     if subdomain is None or subdomain_ptr is None:          # default: row i's subdomain = the columns of row i
         subdomain, subdomain_ptr = A.indices.copy(), A.indptr.copy()
     if inv_subblock is None or inv_subblock_ptr is None:
-        inv_subblock, inv_subblock_ptr = _subdomain_blocks(A, subdomain, subdomain_ptr)
-        single = np.dtype(A.dtype).char.lower() == "f"
-        rank_tol = (1e3 * np.finfo(np.single).eps) if single else (1e6 * np.finfo(np.double).eps)    # util/params.py set_tol
-        gelss, = la.get_lapack_funcs(["gelss"], (np.ones((1,), dtype=A.dtype),))
-        for d, m in enumerate(np.diff(subdomain_ptr)):
-            blk = inv_subblock[inv_subblock_ptr[d]:inv_subblock_ptr[d + 1]]
-            # pseudo-inverse of the block: least-squares solve against the identity, like the reference does it
-            blk[:] = np.ravel(gelss(blk.reshape(m, m), np.eye(m, m, dtype=A.dtype), cond=rank_tol, overwrite_a=True, overwrite_b=True)[1])
+        if device:
+            if not (sparse.issparse(A) and A.format == "csr" and A.has_sorted_indices):
+                raise ValueError("schwarz_parameters(device=True) needs a CSR operator with sorted rows")
+            inv_subblock, inv_subblock_ptr, A.schwarz_setup_report = _schwarz_blocks_device(A, subdomain, subdomain_ptr)
+            inv_subblock_ptr = inv_subblock_ptr.astype(A.indices.dtype, copy=False)
+        else:
+            inv_subblock, inv_subblock_ptr = _subdomain_blocks(A, subdomain, subdomain_ptr)
+            _invert_blocks_host(A.dtype, inv_subblock, inv_subblock_ptr, subdomain_ptr)
     A.schwarz_parameters = (subdomain, subdomain_ptr, inv_subblock, inv_subblock_ptr)
     return A.schwarz_parameters
 
 
 def schwarz(A, x, b, iterations=1, subdomain=None, subdomain_ptr=None, inv_subblock=None, inv_subblock_ptr=None,
-            sweep="forward"):
-    """Multiplicative overlapping Schwarz, in place (reference: relaxation.py:157-262)."""
+            sweep="forward", device=False):
+    """Multiplicative overlapping Schwarz, in place (reference: relaxation.py:157-262).  ``device=True``: blocks that have to be
+    built are built on the GPU (see ``schwarz_parameters``)."""
     from . import amg_core
     A, x, b = make_system(A, x, b, formats=["csr"])
     A.sort_indices()
     if subdomain is None and inv_subblock is not None:
         raise ValueError("inv_subblock must be None if subdomain is None")
-    subdomain, subdomain_ptr, inv_subblock, inv_subblock_ptr = schwarz_parameters(A, subdomain, subdomain_ptr, inv_subblock, inv_subblock_ptr)
+    subdomain, subdomain_ptr, inv_subblock, inv_subblock_ptr = schwarz_parameters(A, subdomain, subdomain_ptr, inv_subblock, inv_subblock_ptr,
+                                                                                  device=device)
     nsub = subdomain_ptr.shape[0] - 1
     if sweep == "forward":
         row_start, row_stop, row_step = 0, nsub, 1
