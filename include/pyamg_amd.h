@@ -305,6 +305,53 @@ int pamg_bsr_transpose_f64(int32_t n_brow, int32_t n_bcol, int32_t R, int32_t C,
 int pamg_bsr_transpose_f32(int32_t n_brow, int32_t n_bcol, int32_t R, int32_t C, const int32_t *Ap, const int32_t *Aj,
                            const float *Ax, int32_t *Bp, int32_t *Bi, float *Bx);
 
+/* The setup of classical (Ruge-Stuben) AMG (csrc/pamg_classical.hip, the per-row arithmetic in csrc/pamg_classical.h).  float64, HOST
+ * arrays, amg_core's argument order; every result is the reference's, bit for bit.
+ *
+ * amg_core::classical_strength_of_connection_abs / _min, ruge_stuben.h:64-204, FOLLOWED by what strength.py:237-240 does to their
+ * result: magnitudes, every row scaled by the reciprocal of its largest entry, exact zeros dropped.  Sp [n_row + 1], Sj, Sx receive the
+ * finished strength matrix (Sp[n_row] entries; capacity of Sj / Sx: the entries of A, as in the reference). */
+int pamg_classical_strength_of_connection_abs(int32_t n_row, double theta, const int32_t *Ap, int Ap_size, const int32_t *Aj,
+                                              int Aj_size, const double *Ax, int Ax_size, int32_t *Sp, int Sp_size, int32_t *Sj,
+                                              int Sj_size, double *Sx, int Sx_size);
+int pamg_classical_strength_of_connection_min(int32_t n_row, double theta, const int32_t *Ap, int Ap_size, const int32_t *Aj,
+                                              int Aj_size, const double *Ax, int Ax_size, int32_t *Sp, int Sp_size, int32_t *Sj,
+                                              int Sj_size, double *Sx, int Sx_size);
+/* amg_core::maximal_independent_set_parallel, graph.h:140-203, with max_iters = -1 (anything else: PAMG_E_UNSUPPORTED -- a bounded
+ * number of the reference's in-place sweeps depends on the sweep order): the nodes with x[i] == active end as C (in the set) or F.  The
+ * result is the greedy independent set in descending (y, index) order, whatever the sweep order, so synchronous rounds -- one plain
+ * launch each -- give the reference's array.  Symmetric patterns only (PAMG_E_UNSUPPORTED otherwise); self loops are ignored.
+ * *n_mis = nodes added to the set (the reference returns it), *rounds = rounds run (at most num_rows; more: PAMG_E_NOCONV).  Either
+ * pointer may be null. */
+int pamg_maximal_independent_set(int32_t num_rows, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, int32_t active,
+                                 int32_t C, int32_t F, int32_t *x, int x_size, const double *y, int y_size, int32_t max_iters,
+                                 int32_t *n_mis, int32_t *rounds);
+/* classical.split.PMIS (split.py:155-194) after its random draw: the off-diagonal pattern of S, weights = in-degree + rnd, the MIS of
+ * S union S^T (the transposed pattern is built on the device), nodes without a neighbour set to F.  splitting [n_nodes]: 1 = C, 0 = F. */
+int pamg_pmis_splitting(int32_t n_nodes, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size, const double *rnd,
+                        int rnd_size, int32_t *splitting, int splitting_size, int32_t *rounds);
+/* amg_core::rs_direct_interpolation_pass1 / _pass2, ruge_stuben.h:777-907.  Sx holds the values of A on the pattern of the strength
+ * matrix.  Pass 2 checks Pp against pass 1's counts (PAMG_E_ARG).  Rows need not be sorted; no row may hold a column twice. */
+int pamg_rs_direct_interpolation_pass1(int32_t n_nodes, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,
+                                       const int32_t *splitting, int splitting_size, int32_t *Pp, int Pp_size);
+int pamg_rs_direct_interpolation_pass2(int32_t n_nodes, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size,
+                                       const double *Ax, int Ax_size, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,
+                                       const double *Sx, int Sx_size, const int32_t *splitting, int splitting_size,
+                                       const int32_t *Pp, int Pp_size, int32_t *Pj, int Pj_size, double *Px, int Px_size);
+/* amg_core::remove_strong_FF_connections, ruge_stuben.h:1133-1181: Sx of a strong F-F pair without a common strong C-point := 0 */
+int pamg_remove_strong_FF_connections(int32_t n_nodes, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size, double *Sx,
+                                      int Sx_size, const int32_t *splitting, int splitting_size);
+/* amg_core::rs_classical_interpolation_pass1 / _pass2, ruge_stuben.h:1083-1103, :1239-1383 (modified != 0: Eq. (9), else Eq. (8)).  A
+ * group of 8 / 16 / 32 / 64 lanes per F-row; the inner denominator of a strong F-neighbour is computed once, not once per C-neighbour.
+ * Nothing is printed on a zero denominator: the IEEE result is stored, as in the reference.  Same preconditions as direct interpolation. */
+int pamg_rs_classical_interpolation_pass1(int32_t n_nodes, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,
+                                          const int32_t *splitting, int splitting_size, int32_t *Pp, int Pp_size);
+int pamg_rs_classical_interpolation_pass2(int32_t n_nodes, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size,
+                                          const double *Ax, int Ax_size, const int32_t *Sp, int Sp_size, const int32_t *Sj,
+                                          int Sj_size, const double *Sx, int Sx_size, const int32_t *splitting, int splitting_size,
+                                          const int32_t *Pp, int Pp_size, int32_t *Pj, int Pj_size, double *Px, int Px_size,
+                                          int modified);
+
 /* ------------------------------------------------------ Layer 2: resident engine (HBM) */
 /* Operator handle: uploads CSR/BSR arrays (HOST pointers) to HBM once and analyses them
  * (row-block plan for the LDS-streamed kernels; dependency-level schedules for the

@@ -114,6 +114,16 @@ def _declare(lib):
     f("pamg_csr_standard_aggregation", _vp, _vp, _vp, P(_i))
     f("pamg_fit_candidates_f64", _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _d)
     f("pamg_fit_candidates_f32", _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, C.c_float)
+    for nm in ("abs", "min"):
+        f(f"pamg_classical_strength_of_connection_{nm}", _i, _d, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i)
+    f("pamg_maximal_independent_set", _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, P(_i), P(_i))
+    f("pamg_pmis_splitting", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, P(_i))
+    for nm in ("direct", "classical"):
+        f(f"pamg_rs_{nm}_interpolation_pass1", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i)
+    interp2 = (_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i)
+    f("pamg_rs_direct_interpolation_pass2", *interp2)
+    f("pamg_rs_classical_interpolation_pass2", *interp2, _i)
+    f("pamg_remove_strong_FF_connections", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i)
     f("pamg_fit_tentative_f64", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d)
     f("pamg_fit_tentative_f32", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float)
     f("pamg_matrix_create", P(_vp), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp)

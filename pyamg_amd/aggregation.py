@@ -757,8 +757,11 @@ def _schwarz_parameters_or_reference(reference_fn):
     return schwarz_parameters
 
 
+_CLASSICAL_NAMES = ("classical_strength_of_connection", "direct_interpolation", "classical_interpolation", "PMIS", "MIS")
+
+
 @contextlib.contextmanager
-def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False):
+def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -777,8 +780,14 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     ``schwarz=True`` patches ``schwarz_parameters`` in ``<pyamg>.relaxation.relaxation`` -- the attribute both ``smoothing.setup_schwarz`` and
     ``relaxation.schwarz`` resolve -- with the device version (``relaxation.schwarz_parameters(device=True)``).  Off by default: the
     inverted blocks then equal LAPACK's to rounding (a one-sided Jacobi SVD with the same rank rule), not bit for bit, so a hierarchy
-    set up this way no longer reproduces the reference's iterates to the last bit."""
+    set up this way no longer reproduces the reference's iterates to the last bit.
+    ``classical=True`` routes the setup of ``ruge_stuben_solver`` to ``pyamg_amd.classical``: ``classical_strength_of_connection`` (in
+    ``<pyamg>.strength``, ``.classical.classical`` and ``.classical.interpolate``), ``direct_interpolation`` and ``classical_interpolation`` (in
+    ``.classical.classical`` and ``.classical.interpolate``), ``PMIS`` and ``MIS`` (in ``.classical.split``).  The arrays are the reference's, bit
+    for bit, and ``PMIS`` consumes the same random numbers; inputs the device path does not take go to the function that was patched out.
+    Off by default: the first measurements compare two hosts; a same-host run at scale decides a later default."""
     import importlib
+    from . import classical as _cls
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
                           ("aggregation.aggregation", "richardson_prolongation_smoother", richardson_prolongation_smoother),
@@ -790,7 +799,18 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                           ("relaxation.smoothing", "approximate_spectral_radius", approximate_spectral_radius),
                           ("relaxation.chebyshev", "approximate_spectral_radius", approximate_spectral_radius),
                           ("util.linalg", "approximate_spectral_radius", approximate_spectral_radius),
-                          ("relaxation.relaxation", "schwarz_parameters", None)):
+                          ("relaxation.relaxation", "schwarz_parameters", None),
+                          ("strength", "classical_strength_of_connection", _cls.classical_strength_of_connection),
+                          ("classical.classical", "classical_strength_of_connection", _cls.classical_strength_of_connection),
+                          ("classical.interpolate", "classical_strength_of_connection", _cls.classical_strength_of_connection),
+                          ("classical.classical", "direct_interpolation", _cls.direct_interpolation),
+                          ("classical.interpolate", "direct_interpolation", _cls.direct_interpolation),
+                          ("classical.classical", "classical_interpolation", _cls.classical_interpolation),
+                          ("classical.interpolate", "classical_interpolation", _cls.classical_interpolation),
+                          ("classical.split", "PMIS", _cls.PMIS),
+                          ("classical.split", "MIS", _cls.MIS)):
+        if not classical and name in _CLASSICAL_NAMES:
+            continue                            # (before the import: with classical=False nothing of <pyamg>.classical is touched)
         try:
             m = importlib.import_module(f"{pyamg.__name__}.{mod}")
         except ImportError:     # pragma: no cover
@@ -808,7 +828,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                 setattr(m, name, _rho_or_reference(old))
             elif name == "schwarz_parameters":
                 setattr(m, name, _schwarz_parameters_or_reference(old))
-            elif name in ("standard_aggregation", "fit_candidates"):
+            elif name in ("standard_aggregation", "fit_candidates") or name in _CLASSICAL_NAMES:
                 setattr(m, name, _device_or_reference(fn, old))
             else:
                 setattr(m, name, fn)

@@ -15,7 +15,10 @@ from . import _capi as capi
 
 __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_gauss_seidel",
            "jacobi", "bsr_jacobi", "block_jacobi", "block_jacobi_indexed", "block_gauss_seidel", "jacobi_indexed", "gauss_seidel_indexed", "overlapping_schwarz_csr", "extract_subblocks", "gauss_seidel_ne",
-           "gauss_seidel_nr", "jacobi_ne", "pinv_array", "standard_aggregation", "fit_candidates"]
+           "gauss_seidel_nr", "jacobi_ne", "pinv_array", "standard_aggregation", "fit_candidates",
+           "classical_strength_of_connection_abs", "classical_strength_of_connection_min", "maximal_independent_set_parallel", "pmis_splitting",
+           "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2", "remove_strong_FF_connections",
+           "rs_classical_interpolation_pass1", "rs_classical_interpolation_pass2"]
 
 
 def _sfx(Ax, *vals):
@@ -229,3 +232,90 @@ def fit_candidates(n_row, n_col, K1, K2, Ap, Ai, Ax, B, R, tol):
     capi.check(getattr(capi.lib(), f"pamg_fit_candidates_{s}")(int(n_row), int(n_col), int(K1), int(K2), capi.ptr(Ap), Ap.size,
                                                               capi.ptr(Ai), Ai.size, capi.ptr(Ax), Ax.size, capi.ptr(B), B.size,
                                                               capi.ptr(R), R.size, float(tol)), "fit_candidates")
+
+
+# ------------------------------------------------------------------ classical (Ruge-Stuben) setup: csrc/pamg_classical.hip
+def _f64(*arrs):
+    for a in arrs:
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.c_contiguous:
+            raise TypeError("incompatible function arguments (contiguous float64 arrays on the device path)")
+
+
+def _pairs(*arrs):
+    out = []
+    for a in arrs:
+        out += [capi.ptr(a), a.size]
+    return out
+
+
+def _strength(norm, n_row, theta, Ap, Aj, Ax, Sp, Sj, Sx):
+    _idx(Ap, Aj, Sp, Sj)
+    _f64(Ax, Sx)
+    capi.check(getattr(capi.lib(), f"pamg_classical_strength_of_connection_{norm}")(int(n_row), float(theta), *_pairs(Ap, Aj, Ax, Sp, Sj, Sx)),
+               f"classical_strength_of_connection_{norm}")
+
+
+def classical_strength_of_connection_abs(n_row, theta, Ap, Aj, Ax, Sp, Sj, Sx):
+    """amg_core.classical_strength_of_connection_abs (ruge_stuben.h:64-111) followed by strength.py:237-240: Sp / Sj / Sx receive the
+    finished strength matrix -- magnitudes, rows scaled by their largest entry, zeros dropped; Sp[-1] entries of Sj / Sx are set."""
+    _strength("abs", n_row, theta, Ap, Aj, Ax, Sp, Sj, Sx)
+
+
+def classical_strength_of_connection_min(n_row, theta, Ap, Aj, Ax, Sp, Sj, Sx):
+    """amg_core.classical_strength_of_connection_min (ruge_stuben.h:156-204), finished like the _abs form."""
+    _strength("min", n_row, theta, Ap, Aj, Ax, Sp, Sj, Sx)
+
+
+def maximal_independent_set_parallel(num_rows, Ap, Aj, active, C, F, x, y, max_iters=-1, rounds=None):
+    """amg_core.maximal_independent_set_parallel (graph.h:140-203), max_iters = -1 only; returns the number of nodes added to the
+    set.  ``rounds``: a list that receives the number of synchronous rounds."""
+    import ctypes
+    _idx(Ap, Aj, x)
+    _f64(y)
+    n_mis, nr = ctypes.c_int(0), ctypes.c_int(0)
+    capi.check(capi.lib().pamg_maximal_independent_set(int(num_rows), *_pairs(Ap, Aj), int(active), int(C), int(F), *_pairs(x, y), int(max_iters),
+                                                      ctypes.byref(n_mis), ctypes.byref(nr)), "maximal_independent_set_parallel")
+    if rounds is not None:
+        rounds.append(int(nr.value))
+    return int(n_mis.value)
+
+
+def pmis_splitting(n_nodes, Sp, Sj, rnd, splitting, rounds=None):
+    """classical.split.PMIS after its random draw (no amg_core twin: the reference composes it in Python)."""
+    import ctypes
+    _idx(Sp, Sj, splitting)
+    _f64(rnd)
+    nr = ctypes.c_int(0)
+    capi.check(capi.lib().pamg_pmis_splitting(int(n_nodes), *_pairs(Sp, Sj, rnd, splitting), ctypes.byref(nr)), "pmis_splitting")
+    if rounds is not None:
+        rounds.append(int(nr.value))
+
+
+def rs_direct_interpolation_pass1(n_nodes, Sp, Sj, splitting, Pp):
+    _idx(Sp, Sj, splitting, Pp)
+    capi.check(capi.lib().pamg_rs_direct_interpolation_pass1(int(n_nodes), *_pairs(Sp, Sj, splitting, Pp)), "rs_direct_interpolation_pass1")
+
+
+def rs_direct_interpolation_pass2(n_nodes, Ap, Aj, Ax, Sp, Sj, Sx, splitting, Pp, Pj, Px):
+    _idx(Ap, Aj, Sp, Sj, splitting, Pp, Pj)
+    _f64(Ax, Sx, Px)
+    capi.check(capi.lib().pamg_rs_direct_interpolation_pass2(int(n_nodes), *_pairs(Ap, Aj, Ax, Sp, Sj, Sx, splitting, Pp, Pj, Px)),
+               "rs_direct_interpolation_pass2")
+
+
+def remove_strong_FF_connections(n_nodes, Sp, Sj, Sx, splitting):
+    _idx(Sp, Sj, splitting)
+    _f64(Sx)
+    capi.check(capi.lib().pamg_remove_strong_FF_connections(int(n_nodes), *_pairs(Sp, Sj, Sx, splitting)), "remove_strong_FF_connections")
+
+
+def rs_classical_interpolation_pass1(n_nodes, Sp, Sj, splitting, Pp):
+    _idx(Sp, Sj, splitting, Pp)
+    capi.check(capi.lib().pamg_rs_classical_interpolation_pass1(int(n_nodes), *_pairs(Sp, Sj, splitting, Pp)), "rs_classical_interpolation_pass1")
+
+
+def rs_classical_interpolation_pass2(n_nodes, Ap, Aj, Ax, Sp, Sj, Sx, splitting, Pp, Pj, Px, modified):
+    _idx(Ap, Aj, Sp, Sj, splitting, Pp, Pj)
+    _f64(Ax, Sx, Px)
+    capi.check(capi.lib().pamg_rs_classical_interpolation_pass2(int(n_nodes), *_pairs(Ap, Aj, Ax, Sp, Sj, Sx, splitting, Pp, Pj, Px),
+                                                               int(bool(modified))), "rs_classical_interpolation_pass2")

@@ -160,5 +160,55 @@ PYBIND11_MODULE(_amg_core_pybind, m)
              "standard_aggregation");
         return naggs;
     }, py::arg("n_row"), py::arg("Ap").noconvert(), py::arg("Aj").noconvert(), py::arg("x").noconvert(), py::arg("y").noconvert());
+    // the classical (Ruge-Stuben) setup, float64 (ruge_stuben_bind.cpp, graph_bind.cpp): csrc/pamg_classical.hip
+    using D = Vec<double>;
+    auto nc = [](const char *n) { return py::arg(n).noconvert(); };
+    m.def("classical_strength_of_connection_abs", [](int n_row, double theta, Idx &Ap, Idx &Aj, D &Ax, Idx &Sp, Idx &Sj, D &Sx) {
+        done(pamg_classical_strength_of_connection_abs(n_row, theta, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), Sp.mutable_data(),
+                                                       len(Sp), Sj.mutable_data(), len(Sj), Sx.mutable_data(), len(Sx)),
+             "classical_strength_of_connection_abs");
+    }, py::arg("n_row"), py::arg("theta"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Sp"), nc("Sj"), nc("Sx"));
+    m.def("classical_strength_of_connection_min", [](int n_row, double theta, Idx &Ap, Idx &Aj, D &Ax, Idx &Sp, Idx &Sj, D &Sx) {
+        done(pamg_classical_strength_of_connection_min(n_row, theta, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), Sp.mutable_data(),
+                                                       len(Sp), Sj.mutable_data(), len(Sj), Sx.mutable_data(), len(Sx)),
+             "classical_strength_of_connection_min");
+    }, py::arg("n_row"), py::arg("theta"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Sp"), nc("Sj"), nc("Sx"));
+    m.def("maximal_independent_set_parallel", [](int num_rows, Idx &Ap, Idx &Aj, int active, int C, int F, Idx &x, D &y, int max_iters) {
+        int n_mis = 0, rounds = 0;
+        done(pamg_maximal_independent_set(num_rows, Ap.data(), len(Ap), Aj.data(), len(Aj), active, C, F, x.mutable_data(), len(x), y.data(), len(y),
+                                          max_iters, &n_mis, &rounds), "maximal_independent_set_parallel");
+        return n_mis;
+    }, py::arg("num_rows"), nc("Ap"), nc("Aj"), py::arg("active"), py::arg("C"), py::arg("F"), nc("x"), nc("y"), py::arg("max_iters") = -1);
+    m.def("pmis_splitting", [](int n_nodes, Idx &Sp, Idx &Sj, D &rnd, Idx &splitting) {
+        int rounds = 0;
+        done(pamg_pmis_splitting(n_nodes, Sp.data(), len(Sp), Sj.data(), len(Sj), rnd.data(), len(rnd), splitting.mutable_data(), len(splitting),
+                                 &rounds), "pmis_splitting");
+        return rounds;
+    }, py::arg("n_nodes"), nc("Sp"), nc("Sj"), nc("rnd"), nc("splitting"));
+    m.def("rs_direct_interpolation_pass1", [](int n_nodes, Idx &Sp, Idx &Sj, Idx &splitting, Idx &Pp) {
+        done(pamg_rs_direct_interpolation_pass1(n_nodes, Sp.data(), len(Sp), Sj.data(), len(Sj), splitting.data(), len(splitting), Pp.mutable_data(),
+                                                len(Pp)), "rs_direct_interpolation_pass1");
+    }, py::arg("n_nodes"), nc("Sp"), nc("Sj"), nc("splitting"), nc("Pp"));
+    m.def("rs_classical_interpolation_pass1", [](int n_nodes, Idx &Sp, Idx &Sj, Idx &splitting, Idx &Pp) {
+        done(pamg_rs_classical_interpolation_pass1(n_nodes, Sp.data(), len(Sp), Sj.data(), len(Sj), splitting.data(), len(splitting),
+                                                   Pp.mutable_data(), len(Pp)), "rs_classical_interpolation_pass1");
+    }, py::arg("n_nodes"), nc("Sp"), nc("Sj"), nc("splitting"), nc("Pp"));
+    m.def("rs_direct_interpolation_pass2", [](int n_nodes, Idx &Ap, Idx &Aj, D &Ax, Idx &Sp, Idx &Sj, D &Sx, Idx &splitting, Idx &Pp, Idx &Pj, D &Px) {
+        done(pamg_rs_direct_interpolation_pass2(n_nodes, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), Sp.data(), len(Sp), Sj.data(),
+                                                len(Sj), Sx.data(), len(Sx), splitting.data(), len(splitting), Pp.data(), len(Pp),
+                                                Pj.mutable_data(), len(Pj), Px.mutable_data(), len(Px)), "rs_direct_interpolation_pass2");
+    }, py::arg("n_nodes"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Sp"), nc("Sj"), nc("Sx"), nc("splitting"), nc("Pp"), nc("Pj"), nc("Px"));
+    m.def("rs_classical_interpolation_pass2", [](int n_nodes, Idx &Ap, Idx &Aj, D &Ax, Idx &Sp, Idx &Sj, D &Sx, Idx &splitting, Idx &Pp, Idx &Pj,
+                                                  D &Px, bool modified) {
+        done(pamg_rs_classical_interpolation_pass2(n_nodes, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), Sp.data(), len(Sp), Sj.data(),
+                                                   len(Sj), Sx.data(), len(Sx), splitting.data(), len(splitting), Pp.data(), len(Pp),
+                                                   Pj.mutable_data(), len(Pj), Px.mutable_data(), len(Px), modified ? 1 : 0),
+             "rs_classical_interpolation_pass2");
+    }, py::arg("n_nodes"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Sp"), nc("Sj"), nc("Sx"), nc("splitting"), nc("Pp"), nc("Pj"), nc("Px"),
+       py::arg("modified"));
+    m.def("remove_strong_FF_connections", [](int n_nodes, Idx &Sp, Idx &Sj, D &Sx, Idx &splitting) {
+        done(pamg_remove_strong_FF_connections(n_nodes, Sp.data(), len(Sp), Sj.data(), len(Sj), Sx.mutable_data(), len(Sx), splitting.data(),
+                                               len(splitting)), "remove_strong_FF_connections");
+    }, py::arg("n_nodes"), nc("Sp"), nc("Sj"), nc("Sx"), nc("splitting"));
     m.def("version", [] { return std::string(pamg_version()); });
 }
