@@ -352,6 +352,34 @@ int pamg_rs_classical_interpolation_pass2(int32_t n_nodes, const int32_t *Ap, in
                                           const int32_t *Pp, int Pp_size, int32_t *Pj, int Pj_size, double *Px, int Px_size,
                                           int modified);
 
+/* The setup of approximate ideal restriction (AIR) AMG (csrc/pamg_air.hip, the per-row arithmetic in csrc/pamg_air.h).  float64, HOST
+ * arrays, amg_core's argument order; every result is the reference's, bit for bit.  Rows need not be sorted; no row of A or C may hold a
+ * column twice.
+ *
+ * amg_core::one_point_interpolation, air.h:46-98: n = Pp_size - 1 rows.  A C-row receives (its coarse number, 1.0) -- the reference
+ * writes the column only --, an F-row the stored entry of C with the largest |Cx| among its C-neighbours (strict >: the first stored
+ * entry wins a tie) as (coarse number, -Cx), or nothing.  Pp[n] entries of Pj / Px are written (capacity: PAMG_E_ARG when too small;
+ * n always suffices). */
+int pamg_one_point_interpolation(int32_t *Pp, int Pp_size, int32_t *Pj, int Pj_size, double *Px, int Px_size, const int32_t *Cp,
+                                 int Cp_size, const int32_t *Cj, int Cj_size, const double *Cx, int Cx_size, const int32_t *splitting,
+                                 int splitting_size);
+/* amg_core::approx_ideal_restriction_pass1, air.h:124-163: Rp [Cpts_size + 1]; row r holds the strong F-neighbours of Cpts[r] (and their
+ * strong F-neighbours when distance == 2; any other distance is distance 1, as in the reference, and nothing is printed) plus the
+ * identity entry. */
+int pamg_approx_ideal_restriction_pass1(int32_t *Rp, int Rp_size, const int32_t *Cp, int Cp_size, const int32_t *Cj, int Cj_size,
+                                        const int32_t *Cpts, int Cpts_size, const int32_t *splitting, int splitting_size,
+                                        int32_t distance);
+/* amg_core::approx_ideal_restriction_pass2, air.h:212-327, with least_squares (linalg.h:1172-1472) as the local solve: per row the
+ * neighbourhood Nf ascending, then (Cpts[r], 1.0) LAST; the values solve A[Nf, Nf]^T x = -A[Cpts[r], Nf] by the reference's Householder
+ * QR, operation for operation.  A group of 8 / 16 / 32 / 64 lanes per row by its N; rows with N > 64 are solved by the same routine on
+ * the host threads inside the library.  Rj / Rx need no initialisation (the reference wants Rx zeroed).  Pass 2 checks Rp against pass
+ * 1's counts: PAMG_E_ARG, and nothing is written.  use_gmres != 0: PAMG_E_UNSUPPORTED (maxiter / precondition are GMRES's). */
+int pamg_approx_ideal_restriction_pass2(const int32_t *Rp, int Rp_size, int32_t *Rj, int Rj_size, double *Rx, int Rx_size,
+                                        const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *Ax, int Ax_size,
+                                        const int32_t *Cp, int Cp_size, const int32_t *Cj, int Cj_size, const double *Cx, int Cx_size,
+                                        const int32_t *Cpts, int Cpts_size, const int32_t *splitting, int splitting_size,
+                                        int32_t distance, int32_t use_gmres, int32_t maxiter, int32_t precondition);
+
 /* ------------------------------------------------------ Layer 2: resident engine (HBM) */
 /* Operator handle: uploads CSR/BSR arrays (HOST pointers) to HBM once and analyses them
  * (row-block plan for the LDS-streamed kernels; dependency-level schedules for the

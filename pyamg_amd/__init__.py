@@ -14,6 +14,6 @@ without a device raises (no CPU fallback).
 """
 from .hierarchy import HierarchySpec, LevelSpec, SmootherSpec, SparseOp, extract  # noqa: F401
 from .multilevel import DeviceMatrix, DeviceMultilevelSolver  # noqa: F401
-from . import amg_core, classical, relaxation  # noqa: F401
+from . import air, amg_core, classical, relaxation  # noqa: F401
 
 __version__ = "0.1.0"

@@ -124,6 +124,9 @@ def _declare(lib):
     f("pamg_rs_direct_interpolation_pass2", *interp2)
     f("pamg_rs_classical_interpolation_pass2", *interp2, _i)
     f("pamg_remove_strong_FF_connections", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i)
+    f("pamg_one_point_interpolation", *(_vp, _i) * 7)
+    f("pamg_approx_ideal_restriction_pass1", *(_vp, _i) * 5, _i)
+    f("pamg_approx_ideal_restriction_pass2", *(_vp, _i) * 11, _i, _i, _i, _i)
     f("pamg_fit_tentative_f64", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d)
     f("pamg_fit_tentative_f32", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float)
     f("pamg_matrix_create", P(_vp), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp)

@@ -761,7 +761,7 @@ _CLASSICAL_NAMES = ("classical_strength_of_connection", "direct_interpolation", 
 
 
 @contextlib.contextmanager
-def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False):
+def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -785,9 +785,20 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     ``<pyamg>.strength``, ``.classical.classical`` and ``.classical.interpolate``), ``direct_interpolation`` and ``classical_interpolation`` (in
     ``.classical.classical`` and ``.classical.interpolate``), ``PMIS`` and ``MIS`` (in ``.classical.split``).  The arrays are the reference's, bit
     for bit, and ``PMIS`` consumes the same random numbers; inputs the device path does not take go to the function that was patched out.
-    Off by default: the first measurements compare two hosts; a same-host run at scale decides a later default."""
+    Off by default: the first measurements compare two hosts; a same-host run at scale decides a later default.
+    ``air=True`` routes the setup of ``air_solver`` to ``pyamg_amd.air`` and ``pyamg_amd.classical``: ``one_point_interpolation`` and
+    ``local_air`` (in ``<pyamg>.classical.air`` and ``.classical.interpolate``), and ``classical_strength_of_connection`` and ``PMIS`` as
+    bound in ``.classical.air``.  Bit for bit again, on the same random draws; the default ``CF='RS'`` splitting is an order-dependent
+    serial sweep and stays with the reference.  With ``air=False`` nothing of ``<pyamg>.classical.air`` is touched."""
     import importlib
+    from . import air as _air
     from . import classical as _cls
+    air_table = (("classical.air", "one_point_interpolation", _air.one_point_interpolation),
+                 ("classical.interpolate", "one_point_interpolation", _air.one_point_interpolation),
+                 ("classical.air", "local_air", _air.local_air),
+                 ("classical.interpolate", "local_air", _air.local_air),
+                 ("classical.air", "classical_strength_of_connection", _cls.classical_strength_of_connection),
+                 ("classical.air", "PMIS", _cls.PMIS)) if air else ()
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
                           ("aggregation.aggregation", "richardson_prolongation_smoother", richardson_prolongation_smoother),
@@ -808,8 +819,9 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                           ("classical.classical", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.interpolate", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.split", "PMIS", _cls.PMIS),
-                          ("classical.split", "MIS", _cls.MIS)):
-        if not classical and name in _CLASSICAL_NAMES:
+                          ("classical.split", "MIS", _cls.MIS)) + air_table:
+        of_air = (mod, name, fn) in air_table
+        if not classical and name in _CLASSICAL_NAMES and not of_air:
             continue                            # (before the import: with classical=False nothing of <pyamg>.classical is touched)
         try:
             m = importlib.import_module(f"{pyamg.__name__}.{mod}")
@@ -828,7 +840,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                 setattr(m, name, _rho_or_reference(old))
             elif name == "schwarz_parameters":
                 setattr(m, name, _schwarz_parameters_or_reference(old))
-            elif name in ("standard_aggregation", "fit_candidates") or name in _CLASSICAL_NAMES:
+            elif name in ("standard_aggregation", "fit_candidates") or name in _CLASSICAL_NAMES or of_air:
                 setattr(m, name, _device_or_reference(fn, old))
             else:
                 setattr(m, name, fn)

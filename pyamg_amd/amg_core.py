@@ -18,7 +18,8 @@ __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_
            "gauss_seidel_nr", "jacobi_ne", "pinv_array", "standard_aggregation", "fit_candidates",
            "classical_strength_of_connection_abs", "classical_strength_of_connection_min", "maximal_independent_set_parallel", "pmis_splitting",
            "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2", "remove_strong_FF_connections",
-           "rs_classical_interpolation_pass1", "rs_classical_interpolation_pass2"]
+           "rs_classical_interpolation_pass1", "rs_classical_interpolation_pass2",
+           "one_point_interpolation", "approx_ideal_restriction_pass1", "approx_ideal_restriction_pass2"]
 
 
 def _sfx(Ax, *vals):
@@ -319,3 +320,28 @@ def rs_classical_interpolation_pass2(n_nodes, Ap, Aj, Ax, Sp, Sj, Sx, splitting,
     _f64(Ax, Sx, Px)
     capi.check(capi.lib().pamg_rs_classical_interpolation_pass2(int(n_nodes), *_pairs(Ap, Aj, Ax, Sp, Sj, Sx, splitting, Pp, Pj, Px),
                                                                int(bool(modified))), "rs_classical_interpolation_pass2")
+
+
+# ------------------------------------------------------------------ approximate ideal restriction (AIR) setup: csrc/pamg_air.hip
+def one_point_interpolation(Pp, Pj, Px, Cp, Cj, Cx, splitting):
+    """amg_core.one_point_interpolation (air.h:46-98).  Pp[-1] entries of Pj / Px are written; a C-row's value is 1.0 (the reference
+    writes its column only)."""
+    _idx(Pp, Pj, Cp, Cj, splitting)
+    _f64(Px, Cx)
+    capi.check(capi.lib().pamg_one_point_interpolation(*_pairs(Pp, Pj, Px, Cp, Cj, Cx, splitting)), "one_point_interpolation")
+
+
+def approx_ideal_restriction_pass1(Rp, Cp, Cj, Cpts, splitting, distance=2):
+    """amg_core.approx_ideal_restriction_pass1 (air.h:124-163)"""
+    _idx(Rp, Cp, Cj, Cpts, splitting)
+    capi.check(capi.lib().pamg_approx_ideal_restriction_pass1(*_pairs(Rp, Cp, Cj, Cpts, splitting), int(distance)), "approx_ideal_restriction_pass1")
+
+
+def approx_ideal_restriction_pass2(Rp, Rj, Rx, Ap, Aj, Ax, Cp, Cj, Cx, Cpts, splitting, distance=2, use_gmres=0, maxiter=10, precondition=1):
+    """amg_core.approx_ideal_restriction_pass2 (air.h:212-327) with the least-squares local solve; ``use_gmres`` raises
+    NotImplementedError.  Rx need not be zeroed."""
+    _idx(Rp, Rj, Ap, Aj, Cp, Cj, Cpts, splitting)
+    _f64(Rx, Ax, Cx)
+    capi.check(capi.lib().pamg_approx_ideal_restriction_pass2(*_pairs(Rp, Rj, Rx, Ap, Aj, Ax, Cp, Cj, Cx, Cpts, splitting), int(distance),
+                                                             int(bool(use_gmres)), int(maxiter), int(bool(precondition))),
+               "approx_ideal_restriction_pass2")

@@ -210,5 +210,22 @@ PYBIND11_MODULE(_amg_core_pybind, m)
         done(pamg_remove_strong_FF_connections(n_nodes, Sp.data(), len(Sp), Sj.data(), len(Sj), Sx.mutable_data(), len(Sx), splitting.data(),
                                                len(splitting)), "remove_strong_FF_connections");
     }, py::arg("n_nodes"), nc("Sp"), nc("Sj"), nc("Sx"), nc("splitting"));
+    // the approximate ideal restriction (AIR) setup, float64 (air_bind.cpp): csrc/pamg_air.hip
+    m.def("one_point_interpolation", [](Idx &Pp, Idx &Pj, D &Px, Idx &Cp, Idx &Cj, D &Cx, Idx &splitting) {
+        done(pamg_one_point_interpolation(Pp.mutable_data(), len(Pp), Pj.mutable_data(), len(Pj), Px.mutable_data(), len(Px), Cp.data(), len(Cp),
+                                          Cj.data(), len(Cj), Cx.data(), len(Cx), splitting.data(), len(splitting)), "one_point_interpolation");
+    }, nc("Pp"), nc("Pj"), nc("Px"), nc("Cp"), nc("Cj"), nc("Cx"), nc("splitting"));
+    m.def("approx_ideal_restriction_pass1", [](Idx &Rp, Idx &Cp, Idx &Cj, Idx &Cpts, Idx &splitting, int distance) {
+        done(pamg_approx_ideal_restriction_pass1(Rp.mutable_data(), len(Rp), Cp.data(), len(Cp), Cj.data(), len(Cj), Cpts.data(), len(Cpts),
+                                                 splitting.data(), len(splitting), distance), "approx_ideal_restriction_pass1");
+    }, nc("Rp"), nc("Cp"), nc("Cj"), nc("Cpts"), nc("splitting"), py::arg("distance") = 2);
+    m.def("approx_ideal_restriction_pass2", [](Idx &Rp, Idx &Rj, D &Rx, Idx &Ap, Idx &Aj, D &Ax, Idx &Cp, Idx &Cj, D &Cx, Idx &Cpts, Idx &splitting,
+                                                int distance, int use_gmres, int maxiter, int precondition) {
+        done(pamg_approx_ideal_restriction_pass2(Rp.data(), len(Rp), Rj.mutable_data(), len(Rj), Rx.mutable_data(), len(Rx), Ap.data(), len(Ap),
+                                                 Aj.data(), len(Aj), Ax.data(), len(Ax), Cp.data(), len(Cp), Cj.data(), len(Cj), Cx.data(), len(Cx),
+                                                 Cpts.data(), len(Cpts), splitting.data(), len(splitting), distance, use_gmres, maxiter, precondition),
+             "approx_ideal_restriction_pass2");
+    }, nc("Rp"), nc("Rj"), nc("Rx"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Cp"), nc("Cj"), nc("Cx"), nc("Cpts"), nc("splitting"),
+       py::arg("distance") = 2, py::arg("use_gmres") = 0, py::arg("maxiter") = 10, py::arg("precondition") = 1);
     m.def("version", [] { return std::string(pamg_version()); });
 }
