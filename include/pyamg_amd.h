@@ -380,6 +380,40 @@ int pamg_approx_ideal_restriction_pass2(const int32_t *Rp, int Rp_size, int32_t 
                                         const int32_t *Cpts, int Cpts_size, const int32_t *splitting, int splitting_size,
                                         int32_t distance, int32_t use_gmres, int32_t maxiter, int32_t precondition);
 
+/* The amg_core calls of the evolution strength measure (csrc/pamg_evolution.hip, the per-row arithmetic in csrc/pamg_evolution.h).
+ * float64, HOST arrays, amg_core's argument order; every result is the reference's, bit for bit.  Every pattern is checked before
+ * anything is written (PAMG_E_ARG): null pointers, negative sizes, a pointer that does not start at 0 or decreases, fewer than Sp[n]
+ * index or value entries, an index outside the matrix.
+ *
+ * amg_core::incomplete_mat_mult_csr, evolution_strength.h:586-712: Sx[p] = <A[i, :], B[:, Sj[p]]> on the stored pattern of S; A and S
+ * CSR, B CSC, all num_rows x num_rows with sorted indices.  Each entry is the two-pointer merge over the common indices, ascending,
+ * from 0.0; an entry without a common index is exactly 0.0. */
+int pamg_incomplete_mat_mult_csr_f64(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *Ax, int Ax_size,
+                                     const int32_t *Bp, int Bp_size, const int32_t *Bj, int Bj_size, const double *Bx, int Bx_size,
+                                     const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size, double *Sx, int Sx_size,
+                                     int32_t num_rows);
+/* amg_core::evolution_strength_helper, evolution_strength.h:329-550 (real T): x = B row-major [nrows * NullDim], y = DB candidate after
+ * candidate [NullDim * nrows], b = BDB row-major [nrows * BDBCols], BDBCols = NullDim (NullDim + 1) / 2.  Per row the (NullDim + 1)^2
+ * system is solved by the reference's one-sided Jacobi SVD; rows of any length.  1 <= NullDim <= 6; beyond: PAMG_E_UNSUPPORTED. */
+int pamg_evolution_strength_helper_f64(double *Sx, int Sx_size, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,
+                                       int32_t nrows, const double *x, int x_size, const double *y, int y_size, const double *b,
+                                       int b_size, int32_t BDBCols, int32_t NullDim, double tol);
+/* amg_core::apply_distance_filter, evolution_strength.h:140-172: per row the smallest off-diagonal entry (std::min: a NaN never replaces
+ * the running value; DBL_MAX for a row without one), then 1.0 on the diagonal and 0.0 for every entry >= epsilon times that minimum. */
+int pamg_apply_distance_filter_f64(int32_t n_row, double epsilon, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,
+                                   double *Sx, int Sx_size);
+/* amg_core::apply_absolute_distance_filter, evolution_strength.h:62-85: 1.0 on the diagonal, 0.0 for every other entry >= epsilon. */
+int pamg_apply_absolute_distance_filter_f64(int32_t n_row, double epsilon, const int32_t *Sp, int Sp_size, const int32_t *Sj,
+                                            int Sj_size, double *Sx, int Sx_size);
+/* amg_core::min_blocks, evolution_strength.h:220-245: Tx[i] = the smallest non-zero entry of block i (DBL_MAX for an all-zero block). */
+int pamg_min_blocks_f64(int32_t n_blocks, int32_t blocksize, const double *Sx, int Sx_size, double *Tx, int Tx_size);
+/* The one-candidate shortcut of evolution_strength_of_connection (strength.py:738-779) as one expression per stored entry (i, j) of
+ * S = Atilde, d its diagonal, b the candidate with its zeros made ones: t = (d_i / b_i) b_j, r = t / s_ij, the entry becomes |1 - r|,
+ * or 0.0 where |r| < 1e-4 or t s_ij < 0 -- each rounding where NumPy's elementwise steps put it.  (The reference composes this in
+ * Python; it has no amg_core twin.) */
+int pamg_evolution_strength_vector_f64(double *Sx, int Sx_size, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,
+                                       int32_t nrows, const double *d, int d_size, const double *b, int b_size);
+
 /* ------------------------------------------------------ Layer 2: resident engine (HBM) */
 /* Operator handle: uploads CSR/BSR arrays (HOST pointers) to HBM once and analyses them
  * (row-block plan for the LDS-streamed kernels; dependency-level schedules for the

@@ -761,7 +761,7 @@ _CLASSICAL_NAMES = ("classical_strength_of_connection", "direct_interpolation", 
 
 
 @contextlib.contextmanager
-def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False):
+def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False, evolution=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -789,7 +789,13 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     ``air=True`` routes the setup of ``air_solver`` to ``pyamg_amd.air`` and ``pyamg_amd.classical``: ``one_point_interpolation`` and
     ``local_air`` (in ``<pyamg>.classical.air`` and ``.classical.interpolate``), and ``classical_strength_of_connection`` and ``PMIS`` as
     bound in ``.classical.air``.  Bit for bit again, on the same random draws; the default ``CF='RS'`` splitting is an order-dependent
-    serial sweep and stays with the reference.  With ``air=False`` nothing of ``<pyamg>.classical.air`` is touched."""
+    serial sweep and stays with the reference.  With ``air=False`` nothing of ``<pyamg>.classical.air`` is touched.
+    ``evolution=True`` routes ``evolution_strength_of_connection`` to ``pyamg_amd.evolution`` in ``<pyamg>.strength``,
+    ``.aggregation.aggregation``, ``.aggregation.rootnode``, ``.aggregation.adaptive``, ``.classical.classical`` and ``.classical.air`` (the
+    deprecated ``ode_strength_of_connection`` resolves the patched name by itself).  Given the same spectral radius the arrays are the
+    reference's bit for bit; with the device Arnoldi's they agree to rounding (``pyamg_amd.evolution``).  Off by default for the reason
+    given for ``classical``: the measurement in DESIGN 3b decides a later default.  With ``evolution=False`` nothing changes, and neither
+    ``pyamg_amd.evolution`` nor anything under ``<pyamg>.classical`` is imported on its account."""
     import importlib
     from . import air as _air
     from . import classical as _cls
@@ -799,6 +805,12 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                  ("classical.interpolate", "local_air", _air.local_air),
                  ("classical.air", "classical_strength_of_connection", _cls.classical_strength_of_connection),
                  ("classical.air", "PMIS", _cls.PMIS)) if air else ()
+    evo_table = ()
+    if evolution:
+        from . import evolution as _evo
+        evo_table = tuple((mod, "evolution_strength_of_connection", _evo.evolution_strength_of_connection)
+                          for mod in ("strength", "aggregation.aggregation", "aggregation.rootnode", "aggregation.adaptive",
+                                      "classical.classical", "classical.air"))
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
                           ("aggregation.aggregation", "richardson_prolongation_smoother", richardson_prolongation_smoother),
@@ -819,7 +831,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                           ("classical.classical", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.interpolate", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.split", "PMIS", _cls.PMIS),
-                          ("classical.split", "MIS", _cls.MIS)) + air_table:
+                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table:
         of_air = (mod, name, fn) in air_table
         if not classical and name in _CLASSICAL_NAMES and not of_air:
             continue                            # (before the import: with classical=False nothing of <pyamg>.classical is touched)
@@ -840,7 +852,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                 setattr(m, name, _rho_or_reference(old))
             elif name == "schwarz_parameters":
                 setattr(m, name, _schwarz_parameters_or_reference(old))
-            elif name in ("standard_aggregation", "fit_candidates") or name in _CLASSICAL_NAMES or of_air:
+            elif name in ("standard_aggregation", "fit_candidates", "evolution_strength_of_connection") or name in _CLASSICAL_NAMES or of_air:
                 setattr(m, name, _device_or_reference(fn, old))
             else:
                 setattr(m, name, fn)

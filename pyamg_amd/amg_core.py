@@ -19,7 +19,9 @@ __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_
            "classical_strength_of_connection_abs", "classical_strength_of_connection_min", "maximal_independent_set_parallel", "pmis_splitting",
            "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2", "remove_strong_FF_connections",
            "rs_classical_interpolation_pass1", "rs_classical_interpolation_pass2",
-           "one_point_interpolation", "approx_ideal_restriction_pass1", "approx_ideal_restriction_pass2"]
+           "one_point_interpolation", "approx_ideal_restriction_pass1", "approx_ideal_restriction_pass2",
+           "incomplete_mat_mult_csr", "evolution_strength_helper", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
+           "evolution_strength_vector"]
 
 
 def _sfx(Ax, *vals):
@@ -345,3 +347,47 @@ def approx_ideal_restriction_pass2(Rp, Rj, Rx, Ap, Aj, Ax, Cp, Cj, Cx, Cpts, spl
     capi.check(capi.lib().pamg_approx_ideal_restriction_pass2(*_pairs(Rp, Rj, Rx, Ap, Aj, Ax, Cp, Cj, Cx, Cpts, splitting), int(distance),
                                                              int(bool(use_gmres)), int(maxiter), int(bool(precondition))),
                "approx_ideal_restriction_pass2")
+
+
+# ------------------------------------------------------------------ evolution strength of connection: csrc/pamg_evolution.hip
+def incomplete_mat_mult_csr(Ap, Aj, Ax, Bp, Bj, Bx, Sp, Sj, Sx, num_rows):
+    """amg_core.incomplete_mat_mult_csr (evolution_strength.h:586-712): Sx = (A @ B) on the stored pattern of S; A, S CSR, B CSC, sorted."""
+    _idx(Ap, Aj, Bp, Bj, Sp, Sj)
+    _f64(Ax, Bx, Sx)
+    capi.check(capi.lib().pamg_incomplete_mat_mult_csr_f64(*_pairs(Ap, Aj, Ax, Bp, Bj, Bx, Sp, Sj, Sx), int(num_rows)), "incomplete_mat_mult_csr")
+
+
+def evolution_strength_helper(Sx, Sp, Sj, nrows, x, y, b, BDBCols, NullDim, tol):
+    """amg_core.evolution_strength_helper (evolution_strength.h:329-550), real float64, 1 <= NullDim <= 6 (beyond: NotImplementedError)."""
+    _idx(Sp, Sj)
+    _f64(Sx, x, y, b)
+    capi.check(capi.lib().pamg_evolution_strength_helper_f64(*_pairs(Sx, Sp, Sj), int(nrows), *_pairs(x, y, b), int(BDBCols), int(NullDim), float(tol)),
+               "evolution_strength_helper")
+
+
+def apply_distance_filter(n_row, epsilon, Sp, Sj, Sx):
+    """amg_core.apply_distance_filter (evolution_strength.h:140-172)"""
+    _idx(Sp, Sj)
+    _f64(Sx)
+    capi.check(capi.lib().pamg_apply_distance_filter_f64(int(n_row), float(epsilon), *_pairs(Sp, Sj, Sx)), "apply_distance_filter")
+
+
+def apply_absolute_distance_filter(n_row, epsilon, Sp, Sj, Sx):
+    """amg_core.apply_absolute_distance_filter (evolution_strength.h:62-85)"""
+    _idx(Sp, Sj)
+    _f64(Sx)
+    capi.check(capi.lib().pamg_apply_absolute_distance_filter_f64(int(n_row), float(epsilon), *_pairs(Sp, Sj, Sx)), "apply_absolute_distance_filter")
+
+
+def min_blocks(n_blocks, blocksize, Sx, Tx):
+    """amg_core.min_blocks (evolution_strength.h:220-245)"""
+    _f64(Sx, Tx)
+    capi.check(capi.lib().pamg_min_blocks_f64(int(n_blocks), int(blocksize), *_pairs(Sx, Tx)), "min_blocks")
+
+
+def evolution_strength_vector(Sx, Sp, Sj, nrows, d, b):
+    """The one-candidate shortcut of evolution_strength_of_connection (strength.py:738-779), fused: Sx holds Atilde's values and receives
+    ``|1 - r|`` or 0.0 per stored entry; ``d`` is Atilde's diagonal, ``b`` the candidate with its zeros made ones."""
+    _idx(Sp, Sj)
+    _f64(Sx, d, b)
+    capi.check(capi.lib().pamg_evolution_strength_vector_f64(*_pairs(Sx, Sp, Sj), int(nrows), *_pairs(d, b)), "evolution_strength_vector")

@@ -227,5 +227,29 @@ PYBIND11_MODULE(_amg_core_pybind, m)
              "approx_ideal_restriction_pass2");
     }, nc("Rp"), nc("Rj"), nc("Rx"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Cp"), nc("Cj"), nc("Cx"), nc("Cpts"), nc("splitting"),
        py::arg("distance") = 2, py::arg("use_gmres") = 0, py::arg("maxiter") = 10, py::arg("precondition") = 1);
+    // the evolution strength measure, float64 (evolution_strength_bind.cpp): csrc/pamg_evolution.hip
+    m.def("incomplete_mat_mult_csr", [](Idx &Ap, Idx &Aj, D &Ax, Idx &Bp, Idx &Bj, D &Bx, Idx &Sp, Idx &Sj, D &Sx, int num_rows) {
+        done(pamg_incomplete_mat_mult_csr_f64(Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), Bp.data(), len(Bp), Bj.data(), len(Bj),
+                                              Bx.data(), len(Bx), Sp.data(), len(Sp), Sj.data(), len(Sj), Sx.mutable_data(), len(Sx), num_rows),
+             "incomplete_mat_mult_csr");
+    }, nc("Ap"), nc("Aj"), nc("Ax"), nc("Bp"), nc("Bj"), nc("Bx"), nc("Sp"), nc("Sj"), nc("Sx"), py::arg("num_rows"));
+    m.def("evolution_strength_helper", [](D &Sx, Idx &Sp, Idx &Sj, int nrows, D &x, D &y, D &b, int BDBCols, int NullDim, double tol) {
+        done(pamg_evolution_strength_helper_f64(Sx.mutable_data(), len(Sx), Sp.data(), len(Sp), Sj.data(), len(Sj), nrows, x.data(), len(x), y.data(),
+                                                len(y), b.data(), len(b), BDBCols, NullDim, tol), "evolution_strength_helper");
+    }, nc("Sx"), nc("Sp"), nc("Sj"), py::arg("nrows"), nc("x"), nc("y"), nc("b"), py::arg("BDBCols"), py::arg("NullDim"), py::arg("tol"));
+    m.def("apply_distance_filter", [](int n_row, double epsilon, Idx &Sp, Idx &Sj, D &Sx) {
+        done(pamg_apply_distance_filter_f64(n_row, epsilon, Sp.data(), len(Sp), Sj.data(), len(Sj), Sx.mutable_data(), len(Sx)), "apply_distance_filter");
+    }, py::arg("n_row"), py::arg("epsilon"), nc("Sp"), nc("Sj"), nc("Sx"));
+    m.def("apply_absolute_distance_filter", [](int n_row, double epsilon, Idx &Sp, Idx &Sj, D &Sx) {
+        done(pamg_apply_absolute_distance_filter_f64(n_row, epsilon, Sp.data(), len(Sp), Sj.data(), len(Sj), Sx.mutable_data(), len(Sx)),
+             "apply_absolute_distance_filter");
+    }, py::arg("n_row"), py::arg("epsilon"), nc("Sp"), nc("Sj"), nc("Sx"));
+    m.def("min_blocks", [](int n_blocks, int blocksize, D &Sx, D &Tx) {
+        done(pamg_min_blocks_f64(n_blocks, blocksize, Sx.data(), len(Sx), Tx.mutable_data(), len(Tx)), "min_blocks");
+    }, py::arg("n_blocks"), py::arg("blocksize"), nc("Sx"), nc("Tx"));
+    m.def("evolution_strength_vector", [](D &Sx, Idx &Sp, Idx &Sj, int nrows, D &d, D &b) {
+        done(pamg_evolution_strength_vector_f64(Sx.mutable_data(), len(Sx), Sp.data(), len(Sp), Sj.data(), len(Sj), nrows, d.data(), len(d), b.data(),
+                                                len(b)), "evolution_strength_vector");
+    }, nc("Sx"), nc("Sp"), nc("Sj"), py::arg("nrows"), nc("d"), nc("b"));
     m.def("version", [] { return std::string(pamg_version()); });
 }

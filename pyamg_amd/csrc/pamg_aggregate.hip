@@ -11,126 +11,13 @@
 #include <vector>
 
 #include "pamg_common.h"
+#include "pamg_jacobi_svd.h"
 
 using namespace pamg;
 
 namespace {
 
 constexpr int PN = 6;            // the reference switches to a LAPACK-based routine at n >= 7 (utils.py:682-687)
-
-template <typename T>
-struct JacobiSvd {
-    // column-major n x n factors, all in registers / scratch of one lane
-    T U[PN * PN], V[PN * PN], S[PN];
-    int n;
-
-    __device__ T coldot(int a, int b) const
-    {
-        T s = T(0);
-        for (int i = 0; i < n; ++i) s += U[a * n + i] * U[b * n + i];
-        return s;
-    }
-    __device__ T colnorm(int a) const { return sqrt(coldot(a, a)); }
-
-    // linalg.h:546-812 for a square real block held column-major in A
-    __device__ void run(const T *A)
-    {
-        const int nn = n * n;
-        if (n == 1) {                                    // :559-571
-            const T na = fabs(A[0]);
-            V[0] = T(1);
-            S[0] = na;
-            U[0] = (na == T(0)) ? T(1) : A[0] / na;
-            return;
-        }
-        const T eps = std::numeric_limits<T>::epsilon();
-        int count = 1, sweep = 0;
-        const int sweepmax = max(15 * n, 30);
-        const T tolerance = sqrt((T)n) * eps;
-        for (int i = 0; i < nn; ++i) V[i] = T(0);
-        for (int i = 0; i < nn; i += n + 1) V[i] = T(1);
-        for (int i = 0; i < nn; ++i) U[i] = A[i];
-        for (int j = 0; j < n; ++j) S[j] = eps * colnorm(j);                  // column error estimates, :598-603
-        while (count > 0 && sweep <= sweepmax) {
-            count = n * (n - 1) / 2;
-            for (int j = 0; j < n - 1; ++j) {
-                for (int k = j + 1; k < n; ++k) {
-                    const T a = colnorm(j), b = colnorm(k);
-                    const T d = coldot(j, k);
-                    const T nd = fabs(d);
-                    const T ea = S[j], eb = S[k];
-                    const bool sorted = a >= b;
-                    const bool orthog = nd <= tolerance * a * b;
-                    const bool noisya = a < ea, noisyb = b < eb;
-                    if (sorted && (orthog || noisya || noisyb)) {
-                        --count;
-                    } else if (!sorted || (nd == T(0) && a == b)) {
-                        // swap the columns with one sign flip, :651-686
-                        S[j] = eb;
-                        S[k] = ea;
-                        for (int i = 0; i < n; ++i) {
-                            const T uj = U[j * n + i], uk = U[k * n + i];
-                            U[j * n + i] = -uk;
-                            U[k * n + i] = uj;
-                        }
-                        for (int i = 0; i < n; ++i) {
-                            const T vj = V[j * n + i], vk = V[k * n + i];
-                            V[j * n + i] = -vk;
-                            V[k * n + i] = vj;
-                        }
-                    } else {
-                        // Jacobi rotation, :689-732
-                        const T tau = (b * b - a * a) / (T(2) * nd);
-                        const T sg = tau < T(0) ? T(-1) : T(1);
-                        // the reference's literals are doubles: with T = float these two expressions are evaluated in double
-                        // and rounded once (1.0 + tau*tau, 1.0 + t*t); with T = double nothing changes
-                        const T t = (T)((double)sg / ((double)fabs(tau) + sqrt(1.0 + (double)(tau * tau))));
-                        const T c = (T)(1.0 / sqrt(1.0 + (double)(t * t)));
-                        const T s = d * (t * c / nd);
-                        const T ms = -s;
-                        const T ns = fabs(s);
-                        S[j] = fabs(c) * ea + ns * eb;
-                        S[k] = ns * ea + fabs(c) * eb;
-                        for (int i = 0; i < n; ++i) {
-                            const T uj = U[j * n + i], uk = U[k * n + i];
-                            U[j * n + i] = uj * c + ms * uk;
-                            U[k * n + i] = s * uj + uk * c;
-                        }
-                        for (int i = 0; i < n; ++i) {
-                            const T vj = V[j * n + i], vk = V[k * n + i];
-                            V[j * n + i] = vj * c + ms * vk;
-                            V[k * n + i] = s * vj + vk * c;
-                        }
-                    }
-                }
-            }
-            ++sweep;
-        }
-        // singular values, :745-790
-        T sigma_tol = T(0);
-        int iszero = n;
-        for (int j = 0; j < n; ++j) {
-            const T cn = colnorm(j);
-            if (j == 0) {
-                const T alpha = T(50) / sqrt(sqrt(eps));
-                sigma_tol = alpha * cn * eps;
-            }
-            if (cn <= sigma_tol) {
-                --iszero;
-                S[j] = T(0);
-                for (int i = 0; i < n; ++i) U[j * n + i] = T(0);
-            } else {
-                S[j] = cn;
-                for (int i = 0; i < n; ++i) U[j * n + i] = U[j * n + i] / cn;
-            }
-        }
-        if (iszero == 0) {                                // the zero matrix: U = V = I, :792-805
-            for (int i = 0; i < nn; ++i) V[i] = T(0);
-            for (int i = 0; i < nn; i += n + 1) V[i] = T(1);
-            for (int i = 0; i < nn; i += n + 1) U[i] = T(1);
-        }
-    }
-};
 
 // linalg.h:930-1000.  transA: the blocks are row-major (Python arrays) -> transposed into column-major for the SVD.
 template <typename T>
@@ -139,7 +26,7 @@ __global__ __launch_bounds__(64) void pinv_array_kernel(T *AA, int64_t m, int n,
     const int64_t blk = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (blk >= m) return;
     T *a = AA + blk * n * n;
-    JacobiSvd<T> sv;
+    JacobiSvd<T, PN> sv;
     sv.n = n;
     T in[PN * PN], W[PN * PN];
     if (transA) { for (int r = 0; r < n; ++r) for (int c = 0; c < n; ++c) in[c * n + r] = a[r * n + c]; }
