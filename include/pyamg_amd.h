@@ -432,7 +432,7 @@ int pamg_matrix_destroy(pamg_matrix_t A);
  * info[7]=bwd GS levels */
 int pamg_matrix_info(pamg_matrix_t A, int64_t info[8]);
 /* tuning knobs (speed only: every setting computes the same bits).  key 0 = LDS entries per row
- * range, 1 = entries per lane in the staging phase (2; 1 and 4 were measured no better and retired in round 5), 2 = max rows per range (these
+ * range, 2 = max rows per range (these
  * re-plan the operator); 3 = flow_cap: an order-exact sweep whose schedule averages <= flow_cap/16
  * row ranges per dependency level runs as ONE persistent single-workgroup launch (default 32);
  * 5 = scheduler of the scalar order-exact sweeps: 0 automatic (narrow -> single workgroup, else the
@@ -441,7 +441,9 @@ int pamg_matrix_info(pamg_matrix_t A, int64_t info[8]);
  * with a barrier per level"; 6 = cap on the persistent grid (0 = automatic); 7 = granular sweep
  * inside one XCD's L2: 0 automatic (small operators), 1 always, 2 never; 8 = streaming flags of the
  * whole-operator kernels: bit 0 non-temporal loads of the operator stream, bit 1 XCD-aware
- * row-range order (9, LDS-staged x windows, was retired in round 5: 4-7 % slower than the direct gather);
+ * row-range order, bit 4 value codes staged by six chains per lane, bit 5 the value-code instantiation also on operators without
+ * value codes; a value with bit 2 or 3 (the retired ablations, which computed wrong results) is PAMG_E_ARG (1, entries per lane, was
+ * removed: only 2 was ever kept; 9, LDS-staged x windows, was retired in round 5: 4-7 % slower than the direct gather);
  * 5 also accepts 5 = TILED sweep (one persistent workgroup per contiguous chunk of rows; dependency chains
  * stay in LDS, only chunk-crossing edges use the global hand-off); 11 = record time stamps of the granular /
  * tiled sweep (diagnostics, pamg_matrix_gs_profile); 12 = tiles of the tiled sweep (0 = automatic),

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "pamg_common.h"
+#include "pamg_host_call.h"
 #include "pamg_jacobi_svd.h"
 
 using namespace pamg;
@@ -255,37 +256,29 @@ __global__ __launch_bounds__(BLK) void agg_final_kernel(int n, const int *mark, 
     }
 }
 
-int agg_grid(int64_t n, int cap = 4096) { return (int)std::min<int64_t>(cap, std::max<int64_t>(1, (n + BLK - 1) / BLK)); }
+int agg_grid(int64_t n, int cap = 4096) { return launch_grid(n, BLK, cap); }
 
 // device arrays Ap[n+1], Aj[nnz] -> device x[n], y[n]; *count
 int standard_aggregation_device(int n, const int *d_Ap, const int *d_Aj, int64_t nnz, int *d_x, int *d_y, int *count)
 {
     *count = 0;
     if (n == 0) return PAMG_OK;
-    int *Ns = nullptr, *nsize = nullptr, *cnt = nullptr, *pend = nullptr, *mark = nullptr, *rid = nullptr, *bsum = nullptr, *wl = nullptr;
-    unsigned *ctl = nullptr;                                     // [0] flags, [1] live vertices, [2] vertices done, [4..6] work-list sizes
+    Bufs d;
+    int *Ns, *nsize, *cnt, *pend, *mark, *rid, *bsum, *wl;
+    unsigned *ctl;                                               // [0] flags, [1] live vertices, [2] vertices done, [4..6] work-list sizes
     const int nb = (int)(((int64_t)n + (int64_t)BLK * SCAN_PER - 1) / ((int64_t)BLK * SCAN_PER));
-    int st = PAMG_OK;
-    auto cleanup = [&]() { hipFree(Ns); hipFree(nsize); hipFree(cnt); hipFree(pend); hipFree(mark); hipFree(rid); hipFree(bsum); hipFree(wl); hipFree(ctl); };
-#define AGG_CHECK(expr) do { st = (int)(expr); if (st) { cleanup(); return st; } } while (0)
-    AGG_CHECK(hipMalloc((void **)&Ns, sizeof(int) * ((size_t)nnz + (size_t)n + 8)));
-    AGG_CHECK(hipMalloc((void **)&nsize, sizeof(int) * (size_t)n));
-    AGG_CHECK(hipMalloc((void **)&cnt, sizeof(int) * (size_t)n));
-    AGG_CHECK(hipMalloc((void **)&pend, sizeof(int) * (size_t)n));
-    AGG_CHECK(hipMalloc((void **)&mark, sizeof(int) * (size_t)n));
-    AGG_CHECK(hipMalloc((void **)&rid, sizeof(int) * (size_t)n));
-    AGG_CHECK(hipMalloc((void **)&bsum, sizeof(int) * (size_t)(nb + 1)));
-    AGG_CHECK(hipMalloc((void **)&wl, sizeof(int) * 3 * (size_t)n));
-    AGG_CHECK(hipMalloc((void **)&ctl, 8 * sizeof(unsigned)));
-    AGG_CHECK(hipMemset(cnt, 0, sizeof(int) * (size_t)n));
-    AGG_CHECK(hipMemset(mark, 0, sizeof(int) * (size_t)n));
-    AGG_CHECK(hipMemset(ctl, 0, 8 * sizeof(unsigned)));
+    PAMG_TRY(d.get(&Ns, (size_t)nnz + (size_t)n + 8)); PAMG_TRY(d.get(&nsize, (size_t)n)); PAMG_TRY(d.get(&cnt, (size_t)n));
+    PAMG_TRY(d.get(&pend, (size_t)n)); PAMG_TRY(d.get(&mark, (size_t)n)); PAMG_TRY(d.get(&rid, (size_t)n));
+    PAMG_TRY(d.get(&bsum, (size_t)nb + 1)); PAMG_TRY(d.get(&wl, 3 * (size_t)n)); PAMG_TRY(d.get(&ctl, 8));
+    PAMG_HIP(hipMemset(cnt, 0, sizeof(int) * (size_t)n));
+    PAMG_HIP(hipMemset(mark, 0, sizeof(int) * (size_t)n));
+    PAMG_HIP(hipMemset(ctl, 0, 8 * sizeof(unsigned)));
     hipLaunchKernelGGL(agg_lists_kernel, dim3(agg_grid(n)), dim3(BLK), 0, 0, n, d_Ap, d_Aj, Ns, nsize, mark, ctl, ctl + 1);
     hipLaunchKernelGGL(agg_pend_kernel, dim3(agg_grid(n)), dim3(BLK), 0, 0, n, d_Ap, (const int *)Ns, (const int *)nsize, pend, wl, ctl + 4, ctl);
-    AGG_CHECK(hipGetLastError());
+    PAMG_HIP(hipGetLastError());
     unsigned h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    AGG_CHECK(hipMemcpy(h, ctl, sizeof(h), hipMemcpyDeviceToHost));
-    if (h[0] & 3u) { cleanup(); return PAMG_E_UNSUPPORTED; }     // not symmetric / duplicate entries: the token argument above does not hold
+    PAMG_HIP(hipMemcpy(h, ctl, sizeof(h), hipMemcpyDeviceToHost));
+    if (h[0] & 3u) return PAMG_E_UNSUPPORTED;    // not symmetric / duplicate entries: the token argument above does not hold
     const unsigned live = h[1];
     // rounds in batches (no host synchronisation inside a batch: every launch reads its list size from the device)
     int dev = 0, cus = 64;
@@ -302,33 +295,30 @@ int standard_aggregation_device(int n, const int *d_Ap, const int *d_Aj, int64_t
             hipLaunchKernelGGL(agg_round_kernel, dim3(grid), dim3(BLK), 0, 0, d_Ap, d_Aj, (const int *)Ns, (const int *)nsize, cnt, pend, mark,
                                (const int *)(wl + (size_t)a * n), (const unsigned *)(ctl + 4 + a), wl + (size_t)b * n, ctl + 4 + b, ctl + 4 + c, ctl + 2);
         }
-        AGG_CHECK(hipGetLastError());
+        PAMG_HIP(hipGetLastError());
         const unsigned before = done;
-        AGG_CHECK(hipMemcpy(&done, ctl + 2, sizeof(unsigned), hipMemcpyDeviceToHost));
+        PAMG_HIP(hipMemcpy(&done, ctl + 2, sizeof(unsigned), hipMemcpyDeviceToHost));
         if (done < live && (done == before || round > round_cap)) {                                      // no progress: cannot happen on a valid pattern
             unsigned w[8];
             hipMemcpy(w, ctl, sizeof(w), hipMemcpyDeviceToHost);
             fprintf(stderr, "[pamg aggregation] no progress: n %d nnz %lld round %d done %u of %u, list sizes %u %u %u, flags %u\n", n, (long long)nnz, round,
                     done, live, w[4], w[5], w[6], w[0]);
-            cleanup();
             return PAMG_E_STATE;
         }
     }
     hipLaunchKernelGGL(agg_pass2_kernel, dim3(agg_grid(n)), dim3(BLK), 0, 0, n, d_Ap, d_Aj, mark);
     hipLaunchKernelGGL(agg_count_kernel, dim3(nb), dim3(BLK), 0, 0, n, (const int *)mark, bsum);
-    AGG_CHECK(hipGetLastError());
+    PAMG_HIP(hipGetLastError());
     std::vector<int> hb((size_t)nb + 1, 0);
-    AGG_CHECK(hipMemcpy(hb.data(), bsum, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost));
+    PAMG_HIP(hipMemcpy(hb.data(), bsum, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost));
     int64_t acc = 0;
     for (int b = 0; b < nb; ++b) { const int c = hb[b]; hb[b] = (int)acc; acc += c; }
     *count = (int)acc;
-    AGG_CHECK(hipMemcpy(bsum, hb.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
+    PAMG_HIP(hipMemcpy(bsum, hb.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(agg_rank_kernel, dim3(nb), dim3(BLK), 0, 0, n, (const int *)mark, (const int *)bsum, rid, d_y);
     hipLaunchKernelGGL(agg_final_kernel, dim3(agg_grid(n)), dim3(BLK), 0, 0, n, (const int *)mark, (const int *)rid, d_x, ctl);
-    AGG_CHECK(hipGetLastError());
-    AGG_CHECK(hipMemcpy(h, ctl, sizeof(unsigned), hipMemcpyDeviceToHost));
-#undef AGG_CHECK
-    cleanup();
+    PAMG_HIP(hipGetLastError());
+    PAMG_HIP(hipMemcpy(h, ctl, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (h[0] & 4u) return PAMG_E_UNSUPPORTED;
     return PAMG_OK;
 }
@@ -405,20 +395,6 @@ int fit_launch(int n_col, int K1, int K2, const int *Ap, int *Ai, T *work, const
     return (int)hipGetLastError();
 }
 
-struct DevBufs {
-    std::vector<void *> p;
-    ~DevBufs() { for (void *q : p) hipFree(q); }
-    template <typename U> int get(U **out, size_t count)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(count * sizeof(U), 256));
-        if (e != hipSuccess) return (int)e;
-        p.push_back(q);
-        *out = (U *)q;
-        return PAMG_OK;
-    }
-};
-
 // amg_core.fit_candidates on HOST buffers (the reference's argument order, smoothed_aggregation_bind.cpp:134-170)
 template <typename T>
 int fit_candidates_host(int n_row, int n_col, int K1, int K2, const int32_t *Ap, int Ap_size, const int32_t *Ai, int Ai_size, T *Ax, int Ax_size,
@@ -431,17 +407,14 @@ int fit_candidates_host(int n_row, int n_col, int K1, int K2, const int32_t *Ap,
         return PAMG_E_ARG;
     for (int64_t k = 0; k < nnz; ++k) if (Ai[k] < 0 || Ai[k] >= n_row) return PAMG_E_ARG;
     if (n_col == 0) return PAMG_OK;
-    DevBufs d;
+    Bufs d;
     int *dAp, *dAi;
     T *dW, *dB, *dR;
-    PAMG_TRY(d.get(&dAp, (size_t)n_col + 1)); PAMG_TRY(d.get(&dAi, (size_t)nnz));
-    PAMG_TRY(d.get(&dW, (size_t)Ax_size)); PAMG_TRY(d.get(&dB, (size_t)B_size)); PAMG_TRY(d.get(&dR, (size_t)R_size));
-    PAMG_HIP(hipMemcpy(dAp, Ap, sizeof(int) * ((size_t)n_col + 1), hipMemcpyHostToDevice));
-    if (nnz) PAMG_HIP(hipMemcpy(dAi, Ai, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
-    if (B_size) PAMG_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)B_size, hipMemcpyHostToDevice));
+    PAMG_TRY(d.put(&dAp, Ap, (size_t)n_col + 1)); PAMG_TRY(d.put(&dAi, Ai, (size_t)nnz));
+    PAMG_TRY(d.get(&dW, (size_t)Ax_size)); PAMG_TRY(d.put(&dB, B, (size_t)B_size)); PAMG_TRY(d.get(&dR, (size_t)R_size));
     PAMG_TRY(fit_launch<T>(n_col, K1, K2, dAp, dAi, dW, dB, dR, tol, 0, nullptr, nullptr));
-    if (Ax_size) PAMG_HIP(hipMemcpy(Ax, dW, sizeof(T) * (size_t)Ax_size, hipMemcpyDeviceToHost));
-    PAMG_HIP(hipMemcpy(R, dR, sizeof(T) * (size_t)R_size, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(Ax, dW, (size_t)Ax_size));
+    PAMG_TRY(Bufs::fetch(R, dR, (size_t)R_size));
     return PAMG_OK;
 }
 
@@ -459,29 +432,26 @@ int fit_tentative_host(int n_fine, int n_coarse, int K1, int K2, const int32_t *
     }
     if (n_coarse == 0) return PAMG_OK;
     const size_t BS = (size_t)K1 * K2;
-    DevBufs d;
+    Bufs d;
     int *dTp, *dTj, *dCp, *dCi, *dCur;
     T *dW, *dB, *dR, *dQ;
-    PAMG_TRY(d.get(&dTp, (size_t)n_fine + 1)); PAMG_TRY(d.get(&dTj, (size_t)std::max<int64_t>(nnz, 1)));
+    PAMG_TRY(d.put(&dTp, Tp, (size_t)n_fine + 1)); PAMG_TRY(d.put(&dTj, Tj, (size_t)nnz));
     PAMG_TRY(d.get(&dCp, (size_t)n_coarse + 1)); PAMG_TRY(d.get(&dCi, (size_t)std::max<int64_t>(nnz, 1))); PAMG_TRY(d.get(&dCur, (size_t)n_coarse));
     PAMG_TRY(d.get(&dW, (size_t)nnz * BS)); PAMG_TRY(d.get(&dQ, (size_t)nnz * BS));
-    PAMG_TRY(d.get(&dB, (size_t)n_fine * BS)); PAMG_TRY(d.get(&dR, (size_t)n_coarse * K2 * K2));
-    PAMG_HIP(hipMemcpy(dTp, Tp, sizeof(int) * ((size_t)n_fine + 1), hipMemcpyHostToDevice));
-    if (nnz) PAMG_HIP(hipMemcpy(dTj, Tj, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
-    if (n_fine) PAMG_HIP(hipMemcpy(dB, B, sizeof(T) * (size_t)n_fine * BS, hipMemcpyHostToDevice));
+    PAMG_TRY(d.put(&dB, B, (size_t)n_fine * BS)); PAMG_TRY(d.get(&dR, (size_t)n_coarse * K2 * K2));
     PAMG_HIP(hipMemset(dCur, 0, sizeof(int) * (size_t)n_coarse));
     if (n_fine) hipLaunchKernelGGL(agglist_count_kernel, dim3(agg_grid(n_fine)), dim3(BLK), 0, 0, n_fine, (const int *)dTp, (const int *)dTj, dCur);
     PAMG_HIP(hipGetLastError());
     std::vector<int> cp((size_t)n_coarse + 1, 0);
-    PAMG_HIP(hipMemcpy(cp.data() + 1, dCur, sizeof(int) * (size_t)n_coarse, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(cp.data() + 1, dCur, (size_t)n_coarse));
     for (int a = 0; a < n_coarse; ++a) cp[(size_t)a + 1] += cp[(size_t)a];
     PAMG_HIP(hipMemcpy(dCp, cp.data(), sizeof(int) * ((size_t)n_coarse + 1), hipMemcpyHostToDevice));
     PAMG_HIP(hipMemset(dCur, 0, sizeof(int) * (size_t)n_coarse));
     if (n_fine) hipLaunchKernelGGL(agglist_fill_kernel, dim3(agg_grid(n_fine)), dim3(BLK), 0, 0, n_fine, (const int *)dTp, (const int *)dTj, (const int *)dCp, dCur, dCi);
     PAMG_HIP(hipGetLastError());
     PAMG_TRY(fit_launch<T>(n_coarse, K1, K2, dCp, dCi, dW, dB, dR, tol, 1, dQ, dTp));          // outpos[node] = Tp[node]: its only entry
-    if (nnz) PAMG_HIP(hipMemcpy(Qx, dQ, sizeof(T) * (size_t)nnz * BS, hipMemcpyDeviceToHost));
-    PAMG_HIP(hipMemcpy(R, dR, sizeof(T) * (size_t)n_coarse * K2 * K2, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(Qx, dQ, (size_t)nnz * BS));
+    PAMG_TRY(Bufs::fetch(R, dR, (size_t)n_coarse * K2 * K2));
     return PAMG_OK;
 }
 
@@ -501,16 +471,14 @@ int pamg_standard_aggregation(int32_t n_row, const int32_t *Ap, int Ap_size, con
     for (int64_t p = 0; p < nnz; ++p) if (Aj[p] < 0 || Aj[p] >= n_row) return PAMG_E_ARG;
     *naggs = 0;
     if (n_row == 0) return PAMG_OK;
-    DevBufs d;
+    Bufs d;
     int *dAp, *dAj, *dx, *dy;
-    PAMG_TRY(d.get(&dAp, (size_t)n_row + 1)); PAMG_TRY(d.get(&dAj, (size_t)std::max<int64_t>(nnz, 1)));
+    PAMG_TRY(d.put(&dAp, Ap, (size_t)n_row + 1)); PAMG_TRY(d.put(&dAj, Aj, (size_t)nnz));
     PAMG_TRY(d.get(&dx, (size_t)n_row)); PAMG_TRY(d.get(&dy, (size_t)n_row));
-    PAMG_HIP(hipMemcpy(dAp, Ap, sizeof(int) * ((size_t)n_row + 1), hipMemcpyHostToDevice));
-    if (nnz) PAMG_HIP(hipMemcpy(dAj, Aj, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
     int count = 0;
     PAMG_TRY(standard_aggregation_device(n_row, dAp, dAj, nnz, dx, dy, &count));
-    PAMG_HIP(hipMemcpy(x, dx, sizeof(int) * (size_t)n_row, hipMemcpyDeviceToHost));
-    if (count) PAMG_HIP(hipMemcpy(y, dy, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(x, dx, (size_t)n_row));
+    PAMG_TRY(Bufs::fetch(y, dy, (size_t)count));
     *naggs = count;
     return PAMG_OK;
 }
@@ -526,13 +494,13 @@ int pamg_csr_standard_aggregation(pamg_csr_t C, int32_t *x, int32_t *y, int32_t 
     *naggs = 0;
     if (n == 0) return PAMG_OK;
     if (!x || !y) return PAMG_E_ARG;
-    DevBufs d;
+    Bufs d;
     int *dx, *dy;
     PAMG_TRY(d.get(&dx, (size_t)n)); PAMG_TRY(d.get(&dy, (size_t)n));
     int count = 0;
     PAMG_TRY(standard_aggregation_device(n, a.p, a.j, a.nnz, dx, dy, &count));
-    PAMG_HIP(hipMemcpy(x, dx, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    if (count) PAMG_HIP(hipMemcpy(y, dy, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(x, dx, (size_t)n));
+    PAMG_TRY(Bufs::fetch(y, dy, (size_t)count));
     *naggs = count;
     return PAMG_OK;
 }
@@ -614,21 +582,18 @@ int transpose_host(int n_brow, int n_bcol, int R, int C, const int32_t *Ap, cons
     for (int j = 0; j <= n_bcol; ++j) Bp[j] = 0;
     if (nblk == 0) return PAMG_OK;
     const size_t RC = (size_t)R * C;
-    DevBufs d;
+    Bufs d;
     int *dAp, *dAj, *dBp, *dCur, *dSrc, *dBi;
     T *dAx, *dBx;
-    PAMG_TRY(d.get(&dAp, (size_t)n_brow + 1)); PAMG_TRY(d.get(&dAj, (size_t)nblk)); PAMG_TRY(d.get(&dBp, (size_t)n_bcol + 1));
+    PAMG_TRY(d.put(&dAp, Ap, (size_t)n_brow + 1)); PAMG_TRY(d.put(&dAj, Aj, (size_t)nblk)); PAMG_TRY(d.get(&dBp, (size_t)n_bcol + 1));
     PAMG_TRY(d.get(&dCur, (size_t)n_bcol + 1)); PAMG_TRY(d.get(&dSrc, (size_t)nblk)); PAMG_TRY(d.get(&dBi, (size_t)nblk));
-    PAMG_TRY(d.get(&dAx, (size_t)nblk * RC)); PAMG_TRY(d.get(&dBx, (size_t)nblk * RC));
-    PAMG_HIP(hipMemcpy(dAp, Ap, sizeof(int) * ((size_t)n_brow + 1), hipMemcpyHostToDevice));
-    PAMG_HIP(hipMemcpy(dAj, Aj, sizeof(int) * (size_t)nblk, hipMemcpyHostToDevice));
-    PAMG_HIP(hipMemcpy(dAx, Ax, sizeof(T) * (size_t)nblk * RC, hipMemcpyHostToDevice));
+    PAMG_TRY(d.put(&dAx, Ax, (size_t)nblk * RC)); PAMG_TRY(d.get(&dBx, (size_t)nblk * RC));
     PAMG_HIP(hipMemset(dCur, 0, sizeof(int) * ((size_t)n_bcol + 1)));
     const int grid = agg_grid(nblk, 8192);
     hipLaunchKernelGGL(tr_count_kernel, dim3(grid), dim3(BLK), 0, 0, nblk, (const int *)dAj, dCur);
     PAMG_HIP(hipGetLastError());
     std::vector<int> cnt((size_t)n_bcol + 1, 0);
-    PAMG_HIP(hipMemcpy(cnt.data(), dCur, sizeof(int) * (size_t)n_bcol, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(cnt.data(), dCur, (size_t)n_bcol));
     int mx = 0;
     int64_t acc = 0;
     for (int j = 0; j < n_bcol; ++j) { const int c = cnt[(size_t)j]; mx = std::max(mx, c); Bp[j] = (int)acc; acc += c; }
@@ -640,8 +605,8 @@ int transpose_host(int n_brow, int n_bcol, int R, int C, const int32_t *Ap, cons
     hipLaunchKernelGGL(tr_sort_kernel, dim3(agg_grid(n_bcol)), dim3(BLK), 0, 0, n_bcol, n_brow, (const int *)dAp, (const int *)dBp, dSrc, dBi);
     hipLaunchKernelGGL((tr_blocks_kernel<T>), dim3(agg_grid((int64_t)nblk * RC, 8192)), dim3(BLK), 0, 0, nblk, R, C, (const int *)dSrc, (const T *)dAx, dBx);
     PAMG_HIP(hipGetLastError());
-    PAMG_HIP(hipMemcpy(Bi, dBi, sizeof(int) * (size_t)nblk, hipMemcpyDeviceToHost));
-    PAMG_HIP(hipMemcpy(Bx, dBx, sizeof(T) * (size_t)nblk * RC, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(Bi, dBi, (size_t)nblk));
+    PAMG_TRY(Bufs::fetch(Bx, dBx, (size_t)nblk * RC));
     return PAMG_OK;
 }
 

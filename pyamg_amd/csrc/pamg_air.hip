@@ -14,6 +14,7 @@
 // depend on the workgroup only (the largest N of its systems).
 #include "pamg_common.h"
 #include "pamg_air.h"
+#include "pamg_host_call.h"
 #include "pamg_stream_plan.h"
 
 #include <climits>
@@ -25,48 +26,7 @@ namespace {
 constexpr int AIR_BLK = 64;                 // one wave
 constexpr int SLOT = air::MAX_STAGED + 1;   // ints per lane of the counting kernel (odd: the lanes' slots start on different banks)
 
-int agrid(int64_t n, int per_block, int cap = 8192) { return (int)std::min<int64_t>(cap, std::max<int64_t>(1, (n + per_block - 1) / per_block)); }
-
-// device buffers of one call, released when it returns
-struct Bufs {
-    std::vector<void *> p;
-    ~Bufs() { for (void *q : p) hipFree(q); }
-    template <typename T>
-    int get(T **out, size_t n)
-    {
-        void *q = nullptr;
-        PAMG_HIP(hipMalloc(&q, std::max<size_t>(sizeof(T) * n, 256)));
-        p.push_back(q);
-        *out = (T *)q;
-        return PAMG_OK;
-    }
-    template <typename T>
-    int put(T **out, const T *host, size_t n)
-    {
-        PAMG_TRY(get(out, n));
-        if (n) PAMG_HIP(hipMemcpy(*out, host, sizeof(T) * n, hipMemcpyHostToDevice));
-        return PAMG_OK;
-    }
-};
-
-int have_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return PAMG_E_NODEVICE;
-    return PAMG_OK;
-}
-
-// the index arrays of a CSR pattern of n rows and n columns: sizes, monotone pointer, columns in range
-int check_pattern(int n, const int *Ap, int Ap_size, const int *Aj, int Aj_size, int64_t *nnz_out)
-{
-    if (n < 0 || !Ap || Ap_size < n + 1 || Ap[0] != 0) return PAMG_E_ARG;
-    for (int i = 0; i < n; ++i) if (Ap[i + 1] < Ap[i]) return PAMG_E_ARG;
-    const int64_t nnz = Ap[n];
-    if (nnz > Aj_size || (nnz && !Aj)) return PAMG_E_ARG;
-    for (int64_t p = 0; p < nnz; ++p) if (Aj[p] < 0 || Aj[p] >= n) return PAMG_E_ARG;
-    *nnz_out = nnz;
-    return PAMG_OK;
-}
+int agrid(int64_t n, int per_block, int cap = 8192) { return launch_grid(n, per_block, cap); }
 
 // counts -> pointer on the host; PAMG_E_UNSUPPORTED beyond int32
 int scan_host(int n, const int *cnt, int *ptr)
@@ -197,7 +157,7 @@ int neighbourhood_counts(int n, int nc, const int *Cp, const int *Cj, const int 
     PAMG_TRY(d.get(&dcnt, (size_t)nc));
     hipLaunchKernelGGL(air_count_kernel, dim3(agrid(nc, AIR_BLK)), dim3(AIR_BLK), 0, 0, nc, dCp, dCj, dCpts, dsp, distance, dcnt);
     PAMG_HIP(hipGetLastError());
-    PAMG_HIP(hipMemcpy(cnt.data(), dcnt, sizeof(int) * (size_t)nc, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(cnt.data(), dcnt, (size_t)nc));
     std::vector<int> big;
     for (int r = 0; r < nc; ++r) if (cnt[(size_t)r] < 0) big.push_back(r);
     plan_parallel((int64_t)big.size(), [&](int64_t lo, int64_t hi, int) {
@@ -227,7 +187,7 @@ int pamg_one_point_interpolation(int32_t *Pp, int Pp_size, int32_t *Pj, int Pj_s
     const int n = Pp_size - 1;
     int64_t nnz = 0;
     if (!Pp) return PAMG_E_ARG;
-    PAMG_TRY(check_pattern(n, Cp, Cp_size, Cj, Cj_size, &nnz));
+    PAMG_TRY(check_pattern(n, n, Cp, Cp_size, Cj, Cj_size, &nnz));
     if (nnz > Cx_size || (nnz && !Cx) || splitting_size < n || (n && !splitting)) return PAMG_E_ARG;
     Pp[0] = 0;
     if (n == 0) return PAMG_OK;
@@ -243,7 +203,7 @@ int pamg_one_point_interpolation(int32_t *Pp, int Pp_size, int32_t *Pj, int Pj_s
     hipLaunchKernelGGL((one_point_kernel<false>), dim3(grid), dim3(BLK), 0, 0, n, dCp, dCj, dCx, dsp, dmap, dcnt, (const int *)nullptr, (int *)nullptr,
                        (double *)nullptr);
     PAMG_HIP(hipGetLastError());
-    PAMG_HIP(hipMemcpy(cnt.data(), dcnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(cnt.data(), dcnt, (size_t)n));
     std::vector<int> ptr((size_t)n + 1);
     PAMG_TRY(scan_host(n, cnt.data(), ptr.data()));
     const int total = ptr[(size_t)n];
@@ -251,10 +211,9 @@ int pamg_one_point_interpolation(int32_t *Pp, int Pp_size, int32_t *Pj, int Pj_s
     PAMG_TRY(d.put(&dPp, (const int *)ptr.data(), (size_t)n + 1)); PAMG_TRY(d.get(&dPj, (size_t)total)); PAMG_TRY(d.get(&dPx, (size_t)total));
     hipLaunchKernelGGL((one_point_kernel<true>), dim3(grid), dim3(BLK), 0, 0, n, dCp, dCj, dCx, dsp, dmap, (int *)nullptr, (const int *)dPp, dPj, dPx);
     PAMG_HIP(hipGetLastError());
-    if (total) {
-        PAMG_HIP(hipMemcpy(Pj, dPj, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost));
-        PAMG_HIP(hipMemcpy(Px, dPx, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost));
-    } else PAMG_HIP(hipDeviceSynchronize());
+    PAMG_TRY(Bufs::fetch(Pj, dPj, (size_t)total));
+    PAMG_TRY(Bufs::fetch(Px, dPx, (size_t)total));
+    if (!total) PAMG_HIP(hipDeviceSynchronize());
     for (int i = 0; i <= n; ++i) Pp[i] = ptr[(size_t)i];
     return PAMG_OK;
 }
@@ -264,7 +223,7 @@ int pamg_approx_ideal_restriction_pass1(int32_t *Rp, int Rp_size, const int32_t 
 {
     const int n = Cp_size - 1, nc = Cpts_size;
     int64_t nnz = 0;
-    PAMG_TRY(check_pattern(n, Cp, Cp_size, Cj, Cj_size, &nnz));
+    PAMG_TRY(check_pattern(n, n, Cp, Cp_size, Cj, Cj_size, &nnz));
     PAMG_TRY(check_cf(n, Cpts, Cpts_size, splitting, splitting_size));
     if (!Rp || Rp_size < nc + 1) return PAMG_E_ARG;
     Rp[0] = 0;
@@ -290,8 +249,8 @@ int pamg_approx_ideal_restriction_pass2(const int32_t *Rp, int Rp_size, int32_t 
     if (use_gmres != 0) return PAMG_E_UNSUPPORTED;
     const int n = Ap_size - 1, nc = Cpts_size;
     int64_t nnzA = 0, nnzC = 0;
-    PAMG_TRY(check_pattern(n, Ap, Ap_size, Aj, Aj_size, &nnzA));
-    PAMG_TRY(check_pattern(n, Cp, Cp_size, Cj, Cj_size, &nnzC));
+    PAMG_TRY(check_pattern(n, n, Ap, Ap_size, Aj, Aj_size, &nnzA));
+    PAMG_TRY(check_pattern(n, n, Cp, Cp_size, Cj, Cj_size, &nnzC));
     PAMG_TRY(check_cf(n, Cpts, Cpts_size, splitting, splitting_size));
     if (nnzA > Ax_size || (nnzA && !Ax) || !Rp || Rp_size < nc + 1 || Rp[0] != 0) return PAMG_E_ARG;
     if (nc == 0) return PAMG_OK;
@@ -350,10 +309,8 @@ int pamg_approx_ideal_restriction_pass2(const int32_t *Rp, int Rp_size, int32_t 
     unsigned bad = 0;
     PAMG_HIP(hipMemcpy(&bad, dflag, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (bad) return PAMG_E_STATE;
-    if (nnzR) {
-        PAMG_HIP(hipMemcpy(Rj, dRj, sizeof(int) * (size_t)nnzR, hipMemcpyDeviceToHost));
-        PAMG_HIP(hipMemcpy(Rx, dRx, sizeof(double) * (size_t)nnzR, hipMemcpyDeviceToHost));
-    }
+    PAMG_TRY(Bufs::fetch(Rj, dRj, (size_t)nnzR));
+    PAMG_TRY(Bufs::fetch(Rx, dRx, (size_t)nnzR));
     for (size_t t = 0; t < big.size(); ++t) {
         const int r = big[t], N = cnt[(size_t)r], r0 = Rp[r];
         for (int i = 0; i < N; ++i) { Rj[r0 + i] = bigNf[t][(size_t)i]; Rx[r0 + i] = bigx[t][(size_t)i]; }

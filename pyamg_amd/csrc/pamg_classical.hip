@@ -15,6 +15,7 @@
 //              row that loops, with the kinds and inner denominators in global scratch instead of LDS
 #include "pamg_common.h"
 #include "pamg_classical.h"
+#include "pamg_host_call.h"
 
 #include <climits>
 
@@ -24,48 +25,7 @@ namespace {
 
 constexpr int MIS_BATCH = 8;                // rounds between two read-backs of the activity flags
 
-int cgrid(int64_t n, int cap = 8192) { return (int)std::min<int64_t>(cap, std::max<int64_t>(1, (n + BLK - 1) / BLK)); }
-
-// device buffers of one call, released when it returns
-struct Bufs {
-    std::vector<void *> p;
-    ~Bufs() { for (void *q : p) hipFree(q); }
-    template <typename T>
-    int get(T **out, size_t n)
-    {
-        void *q = nullptr;
-        PAMG_HIP(hipMalloc(&q, std::max<size_t>(sizeof(T) * n, 256)));
-        p.push_back(q);
-        *out = (T *)q;
-        return PAMG_OK;
-    }
-    template <typename T>
-    int put(T **out, const T *host, size_t n)
-    {
-        PAMG_TRY(get(out, n));
-        if (n) PAMG_HIP(hipMemcpy(*out, host, sizeof(T) * n, hipMemcpyHostToDevice));
-        return PAMG_OK;
-    }
-};
-
-int have_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return PAMG_E_NODEVICE;
-    return PAMG_OK;
-}
-
-// the index arrays of a square CSR pattern of n rows: sizes, monotone pointer, columns in range
-int check_pattern(int n, const int *Ap, int Ap_size, const int *Aj, int Aj_size, int64_t *nnz_out)
-{
-    if (n < 0 || !Ap || Ap_size < n + 1 || Ap[0] != 0) return PAMG_E_ARG;
-    for (int i = 0; i < n; ++i) if (Ap[i + 1] < Ap[i]) return PAMG_E_ARG;
-    const int64_t nnz = Ap[n];
-    if (nnz > Aj_size || (nnz && !Aj)) return PAMG_E_ARG;
-    for (int64_t p = 0; p < nnz; ++p) if (Aj[p] < 0 || Aj[p] >= n) return PAMG_E_ARG;
-    *nnz_out = nnz;
-    return PAMG_OK;
-}
+int cgrid(int64_t n) { return launch_grid(n, BLK, 8192); }
 
 // out[i] = in[0] + ... + in[i-1], out[n] = the total; one workgroup, a chunk per lane
 __global__ __launch_bounds__(BLK) void excl_scan_kernel(int n, const int *__restrict__ in, int *__restrict__ out, unsigned *__restrict__ overflow)
@@ -119,7 +79,7 @@ int strength(int n, double theta, const int *Ap, int Ap_size, const int *Aj, int
              int *Sj, int Sj_size, double *Sx, int Sx_size)
 {
     int64_t nnz = 0;
-    PAMG_TRY(check_pattern(n, Ap, Ap_size, Aj, Aj_size, &nnz));
+    PAMG_TRY(check_pattern(n, n, Ap, Ap_size, Aj, Aj_size, &nnz));
     if (nnz > Ax_size || (nnz && !Ax) || !Sp || Sp_size < n + 1) return PAMG_E_ARG;
     Sp[0] = 0;
     if (n == 0) return PAMG_OK;
@@ -140,11 +100,9 @@ int strength(int n, double theta, const int *Ap, int Ap_size, const int *Aj, int
     hipLaunchKernelGGL((strength_kernel<MIN, true>), dim3(cgrid(n)), dim3(BLK), 0, 0, n, theta, dAp, dAj, dAx, (int *)nullptr, (const int *)dSp,
                        dSj, dSx);
     PAMG_HIP(hipGetLastError());
-    PAMG_HIP(hipMemcpy(Sp, dSp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost));
-    if (total) {
-        PAMG_HIP(hipMemcpy(Sj, dSj, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost));
-        PAMG_HIP(hipMemcpy(Sx, dSx, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost));
-    }
+    PAMG_TRY(Bufs::fetch(Sp, dSp, (size_t)n + 1));
+    PAMG_TRY(Bufs::fetch(Sj, dSj, (size_t)total));
+    PAMG_TRY(Bufs::fetch(Sx, dSx, (size_t)total));
     return PAMG_OK;
 }
 
@@ -197,7 +155,7 @@ int mis_rounds(int n, const int *Gp, const int *Gj, const int *Tp, const int *Tj
         }
         PAMG_HIP(hipGetLastError());
         unsigned h[MIS_BATCH];
-        PAMG_HIP(hipMemcpy(h, d_flags, sizeof(unsigned) * MIS_BATCH, hipMemcpyDeviceToHost));
+        PAMG_TRY(Bufs::fetch(h, d_flags, MIS_BATCH));
         for (int r = 0; r < batch; ++r) {
             ++rounds;
             if (!h[r]) { done = true; break; }              // the rounds after it in this batch changed nothing
@@ -354,7 +312,7 @@ struct InterpArgs {
 int interp_pass1(int n, const int *Sp, int Sp_size, const int *Sj, int Sj_size, const int *splitting, int splitting_size, int *Pp, int Pp_size)
 {
     int64_t nnz = 0;
-    PAMG_TRY(check_pattern(n, Sp, Sp_size, Sj, Sj_size, &nnz));
+    PAMG_TRY(check_pattern(n, n, Sp, Sp_size, Sj, Sj_size, &nnz));
     if (!Pp || Pp_size < n + 1 || splitting_size < n || (n && !splitting)) return PAMG_E_ARG;
     Pp[0] = 0;
     if (n == 0) return PAMG_OK;
@@ -368,7 +326,7 @@ int interp_pass1(int n, const int *Sp, int Sp_size, const int *Sj, int Sj_size, 
     PAMG_HIP(hipGetLastError());
     int total = 0;
     PAMG_TRY(scan_counts(n, dcnt, dPp, dflag, &total));
-    PAMG_HIP(hipMemcpy(Pp, dPp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(Pp, dPp, (size_t)n + 1));
     return PAMG_OK;
 }
 
@@ -377,8 +335,8 @@ int interp_pass2(const InterpArgs &a, int modified)
 {
     const int n = a.n;
     int64_t nnzA = 0, nnzS = 0;
-    PAMG_TRY(check_pattern(n, a.Ap, a.Ap_size, a.Aj, a.Aj_size, &nnzA));
-    PAMG_TRY(check_pattern(n, a.Sp, a.Sp_size, a.Sj, a.Sj_size, &nnzS));
+    PAMG_TRY(check_pattern(n, n, a.Ap, a.Ap_size, a.Aj, a.Aj_size, &nnzA));
+    PAMG_TRY(check_pattern(n, n, a.Sp, a.Sp_size, a.Sj, a.Sj_size, &nnzS));
     if (nnzA > a.Ax_size || (nnzA && !a.Ax) || nnzS > a.Sx_size || (nnzS && !a.Sx)) return PAMG_E_ARG;
     if (a.splitting_size < n || (n && !a.splitting) || !a.Pp || a.Pp_size < n + 1) return PAMG_E_ARG;
     if (n == 0) return PAMG_OK;
@@ -428,10 +386,9 @@ int interp_pass2(const InterpArgs &a, int modified)
 #undef PAMG_CLS_LAUNCH
         PAMG_HIP(hipGetLastError());
     }
-    if (nnzP) {
-        PAMG_HIP(hipMemcpy(a.Pj, dPj, sizeof(int) * (size_t)nnzP, hipMemcpyDeviceToHost));
-        PAMG_HIP(hipMemcpy(a.Px, dPx, sizeof(double) * (size_t)nnzP, hipMemcpyDeviceToHost));
-    } else PAMG_HIP(hipDeviceSynchronize());
+    PAMG_TRY(Bufs::fetch(a.Pj, dPj, (size_t)nnzP));
+    PAMG_TRY(Bufs::fetch(a.Px, dPx, (size_t)nnzP));
+    if (!nnzP) PAMG_HIP(hipDeviceSynchronize());
     return PAMG_OK;
 }
 
@@ -455,7 +412,7 @@ int pamg_maximal_independent_set(int32_t num_rows, const int32_t *Ap, int Ap_siz
 {
     const int n = num_rows;
     int64_t nnz = 0;
-    PAMG_TRY(check_pattern(n, Ap, Ap_size, Aj, Aj_size, &nnz));
+    PAMG_TRY(check_pattern(n, n, Ap, Ap_size, Aj, Aj_size, &nnz));
     if (x_size < n || y_size < n || (n && (!x || !y)) || active == C || active == F) return PAMG_E_ARG;
     if (max_iters != -1) return PAMG_E_UNSUPPORTED;         // a bounded number of the reference's in-place sweeps depends on the sweep order
     if (n_mis) *n_mis = 0;
@@ -477,7 +434,7 @@ int pamg_maximal_independent_set(int32_t num_rows, const int32_t *Ap, int Ap_siz
     int fin = 0, nr = 0;
     PAMG_TRY(mis_rounds(n, dGp, dGj, nullptr, nullptr, dy, dx, active, C, F, dflags, &fin, &nr));
     std::vector<int> out((size_t)n);
-    PAMG_HIP(hipMemcpy(out.data(), dx[fin], sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(out.data(), dx[fin], (size_t)n));
     int count = 0;
     for (int i = 0; i < n; ++i) { count += x[i] == active && out[(size_t)i] == C; x[i] = out[(size_t)i]; }
     if (n_mis) *n_mis = count;
@@ -490,7 +447,7 @@ int pamg_pmis_splitting(int32_t n_nodes, const int32_t *Sp, int Sp_size, const i
 {
     const int n = n_nodes;
     int64_t nnz = 0;
-    PAMG_TRY(check_pattern(n, Sp, Sp_size, Sj, Sj_size, &nnz));
+    PAMG_TRY(check_pattern(n, n, Sp, Sp_size, Sj, Sj_size, &nnz));
     if (rnd_size < n || splitting_size < n || (n && (!rnd || !splitting))) return PAMG_E_ARG;
     if (rounds) *rounds = 0;
     if (n == 0) return PAMG_OK;
@@ -516,7 +473,7 @@ int pamg_pmis_splitting(int32_t n_nodes, const int32_t *Sp, int Sp_size, const i
     PAMG_TRY(mis_rounds(n, dSp, dSj, dTp, dTj, dy, dx, -1, cls::C_NODE, cls::F_NODE, dflags, &fin, &nr));
     hipLaunchKernelGGL(pmis_dirichlet_kernel, dim3(cgrid(n)), dim3(BLK), 0, 0, n, dSp, dSj, ddeg, dx[fin]);
     PAMG_HIP(hipGetLastError());
-    PAMG_HIP(hipMemcpy(splitting, dx[fin], sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(splitting, dx[fin], (size_t)n));
     if (rounds) *rounds = nr;
     return PAMG_OK;
 }
@@ -554,7 +511,7 @@ int pamg_remove_strong_FF_connections(int32_t n_nodes, const int32_t *Sp, int Sp
 {
     const int n = n_nodes;
     int64_t nnz = 0;
-    PAMG_TRY(check_pattern(n, Sp, Sp_size, Sj, Sj_size, &nnz));
+    PAMG_TRY(check_pattern(n, n, Sp, Sp_size, Sj, Sj_size, &nnz));
     if (nnz > Sx_size || (nnz && !Sx) || splitting_size < n || (n && !splitting)) return PAMG_E_ARG;
     if (n == 0 || nnz == 0) return PAMG_OK;
     PAMG_TRY(have_device());
@@ -565,7 +522,7 @@ int pamg_remove_strong_FF_connections(int32_t n_nodes, const int32_t *Sp, int Sp
     PAMG_TRY(d.put(&dsp, splitting, (size_t)n));
     hipLaunchKernelGGL(remove_ff_kernel, dim3(cgrid(n)), dim3(BLK), 0, 0, n, dSp, dSj, dSx, dsp);
     PAMG_HIP(hipGetLastError());
-    PAMG_HIP(hipMemcpy(Sx, dSx, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(Sx, dSx, (size_t)nnz));
     return PAMG_OK;
 }
 

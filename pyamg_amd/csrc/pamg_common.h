@@ -75,7 +75,8 @@ struct StreamArgs {
     T omega;
     int cap;             // products staged in LDS per workgroup
     int nblk;            // row ranges of this launch
-    int flags;           // bit 0: non-temporal operator stream, bit 1: XCD-aware range order, bits 2/3: ablations
+    int flags;           // bit 0: non-temporal operator stream, bit 1: XCD-aware range order, bit 4: value codes staged by six chains per lane,
+                         // bit 5: the value-code instantiation also without value codes (pamg_matrix.hip: launch_epi).  Every setting computes the same bits
     int nidle;           // granular sweep: elements of xs that idle lanes may read (>= 1)
     const unsigned short *Aj16;   // whole-operator kernels: column ids as 16-bit window codes (window << 14 | offset) or nullptr
     const int4 *wbase;            //   per row range: the first column of its (up to four) windows
@@ -176,7 +177,7 @@ struct pamg_matrix_s {
     std::vector<int> h_Ap, h_Aj;
     std::vector<int> h_bAp, h_bAj;
     // plan for the streamed kernels
-    int cap = 1536, npl = 2, max_rows = 1024;
+    int cap = 1536, max_rows = 1024;
     int flow_cap = 32;               // single-workgroup persistent sweep when a schedule averages <= flow_cap/16 row ranges per level
     unsigned short *d_Aj16 = nullptr; // column ids of the scalar view as 16-bit window codes (csr_stream_kernel reads 2 instead of 4 bytes per entry)
     int4 *d_wbase = nullptr;         //   window bases per row range; both null when some range needs more than four 16 K-column windows

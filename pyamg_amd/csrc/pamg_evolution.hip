@@ -16,6 +16,7 @@
 // Plain launches only; no lane of any kernel waits for another.
 #include "pamg_common.h"
 #include "pamg_evolution.h"
+#include "pamg_host_call.h"
 
 #include <climits>
 
@@ -26,49 +27,7 @@ namespace {
 constexpr int GW = 16;                      // lanes per row of the entry-parallel kernels
 constexpr int HBLK = 64;                    // the helper: one wave per workgroup, so that a long solve holds back 63 rows and no more
 
-int egrid(int64_t n, int per_block, int cap = 16384) { return (int)std::min<int64_t>(cap, std::max<int64_t>(1, (n + per_block - 1) / per_block)); }
-
-// device buffers of one call, released when it returns
-struct Bufs {
-    std::vector<void *> p;
-    ~Bufs() { for (void *q : p) hipFree(q); }
-    template <typename T>
-    int get(T **out, size_t n)
-    {
-        void *q = nullptr;
-        PAMG_HIP(hipMalloc(&q, std::max<size_t>(sizeof(T) * n, 256)));
-        p.push_back(q);
-        *out = (T *)q;
-        return PAMG_OK;
-    }
-    template <typename T>
-    int put(T **out, const T *host, size_t n)
-    {
-        PAMG_TRY(get(out, n));
-        if (n) PAMG_HIP(hipMemcpy(*out, host, sizeof(T) * n, hipMemcpyHostToDevice));
-        return PAMG_OK;
-    }
-};
-
-int have_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return PAMG_E_NODEVICE;
-    return PAMG_OK;
-}
-
-// a compressed pattern of n rows (or columns) whose indices lie in [0, ncol): sizes, the pointer starting at 0 and monotone, indices in
-// range, room for Ap[n] values
-int check_pattern(int n, int ncol, const int *Ap, int Ap_size, const int *Aj, int Aj_size, const double *Ax, int Ax_size, int64_t *nnz_out)
-{
-    if (n < 0 || !Ap || Ap_size < n + 1 || Aj_size < 0 || Ax_size < 0 || Ap[0] != 0) return PAMG_E_ARG;
-    for (int i = 0; i < n; ++i) if (Ap[i + 1] < Ap[i]) return PAMG_E_ARG;
-    const int64_t nnz = Ap[n];
-    if (nnz > Aj_size || nnz > Ax_size || (nnz && (!Aj || !Ax))) return PAMG_E_ARG;
-    for (int64_t p = 0; p < nnz; ++p) if (Aj[p] < 0 || Aj[p] >= ncol) return PAMG_E_ARG;
-    *nnz_out = nnz;
-    return PAMG_OK;
-}
+int egrid(int64_t n, int per_block) { return launch_grid(n, per_block, 16384); }
 
 // ------------------------------------------------------------------------------------------------ kernels
 __global__ __launch_bounds__(BLK) void imm_kernel(int n, const int *__restrict__ Ap, const int *__restrict__ Aj, const double *__restrict__ Ax,
@@ -127,8 +86,8 @@ int on_values(double *Sx, int64_t nnz, Bufs &d, Launch &&launch)
     PAMG_TRY(d.put(&dSx, (const double *)Sx, (size_t)nnz));
     launch(dSx);
     PAMG_HIP(hipGetLastError());
-    if (nnz) PAMG_HIP(hipMemcpy(Sx, dSx, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost));
-    else PAMG_HIP(hipDeviceSynchronize());
+    PAMG_TRY(Bufs::fetch(Sx, dSx, (size_t)nnz));
+    if (!nnz) PAMG_HIP(hipDeviceSynchronize());
     return PAMG_OK;
 }
 
@@ -136,7 +95,7 @@ template <bool RELATIVE>
 int distance_filter(int n_row, double epsilon, const int *Sp, int Sp_size, const int *Sj, int Sj_size, double *Sx, int Sx_size)
 {
     int64_t nnz = 0;
-    PAMG_TRY(check_pattern(n_row, INT_MAX, Sp, Sp_size, Sj, Sj_size, Sx, Sx_size, &nnz));
+    PAMG_TRY(check_pattern(n_row, INT_MAX, Sp, Sp_size, Sj, Sj_size, &nnz, true, Sx, Sx_size));
     if (n_row == 0 || nnz == 0) return PAMG_OK;
     PAMG_TRY(have_device());
     Bufs d;
@@ -157,9 +116,9 @@ int pamg_incomplete_mat_mult_csr_f64(const int32_t *Ap, int Ap_size, const int32
 {
     const int n = num_rows;
     int64_t nnzA = 0, nnzB = 0, nnzS = 0;
-    PAMG_TRY(check_pattern(n, n, Ap, Ap_size, Aj, Aj_size, Ax, Ax_size, &nnzA));
-    PAMG_TRY(check_pattern(n, n, Bp, Bp_size, Bj, Bj_size, Bx, Bx_size, &nnzB));
-    PAMG_TRY(check_pattern(n, n, Sp, Sp_size, Sj, Sj_size, Sx, Sx_size, &nnzS));
+    PAMG_TRY(check_pattern(n, n, Ap, Ap_size, Aj, Aj_size, &nnzA, true, Ax, Ax_size));
+    PAMG_TRY(check_pattern(n, n, Bp, Bp_size, Bj, Bj_size, &nnzB, true, Bx, Bx_size));
+    PAMG_TRY(check_pattern(n, n, Sp, Sp_size, Sj, Sj_size, &nnzS, true, Sx, Sx_size));
     if (n == 0 || nnzS == 0) return PAMG_OK;
     PAMG_TRY(have_device());
     Bufs d;
@@ -170,7 +129,7 @@ int pamg_incomplete_mat_mult_csr_f64(const int32_t *Ap, int Ap_size, const int32
     PAMG_TRY(d.put(&dSp, Sp, (size_t)n + 1)); PAMG_TRY(d.put(&dSj, Sj, (size_t)nnzS)); PAMG_TRY(d.get(&dSx, (size_t)nnzS));
     hipLaunchKernelGGL(imm_kernel, dim3(egrid(n, BLK / GW)), dim3(BLK), 0, 0, n, dAp, dAj, dAx, dBp, dBj, dBx, dSp, dSj, dSx);
     PAMG_HIP(hipGetLastError());
-    PAMG_HIP(hipMemcpy(Sx, dSx, sizeof(double) * (size_t)nnzS, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(Sx, dSx, (size_t)nnzS));
     return PAMG_OK;
 }
 
@@ -179,7 +138,7 @@ int pamg_evolution_strength_helper_f64(double *Sx, int Sx_size, const int32_t *S
                                        int32_t BDBCols, int32_t NullDim, double tol)
 {
     int64_t nnz = 0;
-    PAMG_TRY(check_pattern(nrows, nrows, Sp, Sp_size, Sj, Sj_size, Sx, Sx_size, &nnz));
+    PAMG_TRY(check_pattern(nrows, nrows, Sp, Sp_size, Sj, Sj_size, &nnz, true, Sx, Sx_size));
     if (NullDim < 1 || !x || !y || !b) return PAMG_E_ARG;
     if (NullDim > evo::MAX_NULLDIM) return PAMG_E_UNSUPPORTED;
     if (BDBCols != NullDim * (NullDim + 1) / 2) return PAMG_E_ARG;
@@ -228,7 +187,7 @@ int pamg_min_blocks_f64(int32_t n_blocks, int32_t blocksize, const double *Sx, i
     PAMG_TRY(d.put(&dSx, Sx, (size_t)total)); PAMG_TRY(d.get(&dTx, (size_t)n_blocks));
     hipLaunchKernelGGL(min_blocks_kernel, dim3(egrid(n_blocks, BLK)), dim3(BLK), 0, 0, n_blocks, blocksize, dSx, dTx);
     PAMG_HIP(hipGetLastError());
-    PAMG_HIP(hipMemcpy(Tx, dTx, sizeof(double) * (size_t)n_blocks, hipMemcpyDeviceToHost));
+    PAMG_TRY(Bufs::fetch(Tx, dTx, (size_t)n_blocks));
     return PAMG_OK;
 }
 
@@ -236,7 +195,7 @@ int pamg_evolution_strength_vector_f64(double *Sx, int Sx_size, const int32_t *S
                                        const double *d, int d_size, const double *b, int b_size)
 {
     int64_t nnz = 0;
-    PAMG_TRY(check_pattern(nrows, nrows, Sp, Sp_size, Sj, Sj_size, Sx, Sx_size, &nnz));
+    PAMG_TRY(check_pattern(nrows, nrows, Sp, Sp_size, Sj, Sj_size, &nnz, true, Sx, Sx_size));
     if (!d || !b || d_size < nrows || b_size < nrows) return PAMG_E_ARG;
     if (nrows == 0 || nnz == 0) return PAMG_OK;
     PAMG_TRY(have_device());

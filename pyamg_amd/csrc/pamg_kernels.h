@@ -117,9 +117,6 @@ __device__ __forceinline__ T spin_value(const T *xs, int j, unsigned *err)
     return v;
 }
 
-#ifdef PAMG_FAKE_RUNTABLE
-__shared__ double pamg_fake_xl[1024];
-#endif
 // gather of one x value in the three flavours of the kernel family:
 //   plain (COH = 0): ordinary cached load;  COH = 1: L1-bypassing load (block sweeps with a barrier per level);
 //   COH = 2 (granular sweep): early entries spin on the hand-off buffer, the others read x.
@@ -197,18 +194,14 @@ __device__ __forceinline__ void stage_pairs16(const StreamArgs<T> &a, int p0, in
         int2 cc;
         cc.x = (w0 == 0 ? wb.x : w0 == 1 ? wb.y : w0 == 2 ? wb.z : wb.w) + (int)(c0 & 0x3FFFu);
         cc.y = (w1 == 0 ? wb.x : w1 == 1 ? wb.y : w1 == 2 ? wb.z : wb.w) + (int)(c1 & 0x3FFFu);
-        const bool ok0 = q >= p0, ok1 = q + 1 < p1;
-        T x0, x1;
-        if (a.flags & 4) {                        // ablation: operator stream only, no gather
-#ifdef PAMG_FAKE_RUNTABLE            /* experiment only (wrong results): the operands from an LDS stage of x, as a run-table kernel would read them */
-            x0 = (T)pamg_fake_xl[cc.x & 1023]; x1 = (T)pamg_fake_xl[cc.y & 1023];
-#else
-            x0 = T(cc.x); x1 = T(cc.y);
-#endif
-        } else {
-            x0 = ok0 ? gather_x<COH>(a, cc.x) : T(0);
-            x1 = ok1 ? gather_x<COH>(a, cc.y) : T(0);
-        }
+        // both predicates also test the decoded columns (window base + offset: never negative), so that BOTH decodes stand ahead of the two
+        // gathers and the gathers issue back to back.  With predicates on q alone the compiler sinks each decode into its gather's block (window
+        // bases re-materialised per entry, the second gather behind the first decode): + 0.3 - 0.8 % on the 256^3 residual
+        // (profiles/r15_csr_stream_cleanup_ab.txt)
+        const bool in = (cc.x | cc.y) >= 0;
+        const bool ok0 = q >= p0 && in, ok1 = q + 1 < p1 && in;
+        const T x0 = ok0 ? gather_x<COH>(a, cc.x) : T(0);
+        const T x1 = ok1 ? gather_x<COH>(a, cc.y) : T(0);
         T2 pr;
         pr.x = vv.x * x0;
         pr.y = vv.y * x1;
@@ -238,17 +231,8 @@ __device__ __forceinline__ void stage_pairs32(const StreamArgs<T> &a, int p0, in
             vv = *reinterpret_cast<const T2 *>(a.Ax + q);
         }
         const bool ok0 = q >= p0, ok1 = q + 1 < p1;
-        T x0, x1;
-        if (a.flags & 4) {                            // ablation: operator stream only, no gather
-#ifdef PAMG_FAKE_RUNTABLE            /* experiment only (wrong results): the operands from an LDS stage of x, as a run-table kernel would read them */
-            x0 = (T)pamg_fake_xl[cc.x & 1023]; x1 = (T)pamg_fake_xl[cc.y & 1023];
-#else
-            x0 = T(cc.x); x1 = T(cc.y);
-#endif
-        } else {
-            x0 = ok0 ? gather_x<COH>(a, cc.x) : T(0);
-            x1 = ok1 ? gather_x<COH>(a, cc.y) : T(0);
-        }
+        const T x0 = ok0 ? gather_x<COH>(a, cc.x) : T(0);
+        const T x1 = ok1 ? gather_x<COH>(a, cc.y) : T(0);
         T2 pr;
         pr.x = (DIAGF && (cc.x & DIAG_BIT)) ? T(0) : vv.x * x0;
         pr.y = (DIAGF && (cc.y & DIAG_BIT)) ? T(0) : vv.y * x1;
@@ -262,138 +246,83 @@ __device__ __forceinline__ void stage_pairs32(const StreamArgs<T> &a, int p0, in
 }
 
 // ---- phase 1: stage products (and column ids) of entries [p0,p1) into LDS slots [p-base]
-template <typename T, bool NEEDC, int NPL, int COH = 0, bool DIAGF = false>
+template <typename T, bool NEEDC, int COH = 0, bool DIAGF = false>
 __device__ __forceinline__ void stage_products(const StreamArgs<T> &a, int p0, int p1, int base,
                                                T *prod, int *cols, const T *vd = nullptr)
 {
     const int tid = threadIdx.x;
-    if constexpr (NPL == 1) {
-        int p = p0 + tid;
-        for (; p + 3 * BLK < p1; p += 4 * BLK) {      // 4 independent load chains in flight
-            const int c0 = a.Aj[p], c1 = a.Aj[p + BLK], c2 = a.Aj[p + 2 * BLK], c3 = a.Aj[p + 3 * BLK];
-            const T v0 = a.Ax[p], v1 = a.Ax[p + BLK], v2 = a.Ax[p + 2 * BLK], v3 = a.Ax[p + 3 * BLK];
-            const T x0 = gather_x<COH>(a, c0), x1 = gather_x<COH>(a, c1), x2 = gather_x<COH>(a, c2),
-                    x3 = gather_x<COH>(a, c3);
-            prod[p - base] = (DIAGF && (c0 & DIAG_BIT)) ? T(0) : v0 * x0;
-            prod[p - base + BLK] = (DIAGF && (c1 & DIAG_BIT)) ? T(0) : v1 * x1;
-            prod[p - base + 2 * BLK] = (DIAGF && (c2 & DIAG_BIT)) ? T(0) : v2 * x2;
-            prod[p - base + 3 * BLK] = (DIAGF && (c3 & DIAG_BIT)) ? T(0) : v3 * x3;
-            if constexpr (NEEDC) {
-                cols[p - base] = c0 & COL_MASK;
-                cols[p - base + BLK] = c1 & COL_MASK;
-                cols[p - base + 2 * BLK] = c2 & COL_MASK;
-                cols[p - base + 3 * BLK] = c3 & COL_MASK;
-            }
-        }
-        for (; p < p1; p += BLK) {
-            const int c0 = a.Aj[p];
-            const T v0 = a.Ax[p];
-            prod[p - base] = (DIAGF && (c0 & DIAG_BIT)) ? T(0) : v0 * gather_x<COH>(a, c0);
-            if constexpr (NEEDC) cols[p - base] = c0 & COL_MASK;
-        }
-    } else if constexpr (NPL == 4) {
-        // four consecutive entries per lane: one 16-byte index load, two 16-byte value loads.
-        // base is a multiple of 4, arrays are padded, out-of-range slots are masked.
-        using T2 = typename Vec2<T>::type;
-        for (int q = base + 4 * tid; q < p1; q += 4 * BLK) {
-            const int4 cc = *reinterpret_cast<const int4 *>(a.Aj + q);
-            const T2 va = *reinterpret_cast<const T2 *>(a.Ax + q);
-            const T2 vb = *reinterpret_cast<const T2 *>(a.Ax + q + 2);
-            const int c[4] = {cc.x, cc.y, cc.z, cc.w};
-            const T v[4] = {va.x, va.y, vb.x, vb.y};
-            T pr[4];
+    // two consecutive entries per lane: 8-byte index loads, 16-byte value loads, 16-byte
+    // LDS stores.  base is even, so every pair is naturally aligned; the operator's
+    // arrays are padded so the pair straddling p1 stays inside the allocation.
+    using T2 = typename Vec2<T>::type;
+    const bool nt = (a.flags & 1) != 0;               // stream the operator past the caches
+    if (a.Aj16) {
+        // 16-bit column stream: every column of this row range lies in one of (up to) four windows of 16 K columns;
+        // an entry stores window << 14 | offset.  Two bytes less per entry on the operator stream, same arithmetic.
+        const int4 wb = a.wb;
+        if (vd) {
+            if (a.flags & 16) { stage_val8<T, NEEDC, COH, 6>(a, p0, p1, base, prod, cols, vd); return; }
+            // four consecutive entries per lane and step (8 + 4 bytes of operator stream for them), TWO steps in flight:
+            // with 3 bytes per entry the kernel is bound by its dependent round trips (codes -> gather), so the codes of
+            // both steps are requested before the first gather.  base is a multiple of 4 here.
+            for (int q = base + 4 * tid; q < p1; q += 8 * BLK) {
+                const int q2 = q + 4 * BLK;
+                const bool two = q2 < p1;
+                const int qb = two ? q2 : q;
+                const uint2 cwa = *reinterpret_cast<const uint2 *>(a.Aj16 + q);
+                const unsigned vca = *reinterpret_cast<const unsigned *>(a.Ax8 + q);
+                const uint2 cwb = *reinterpret_cast<const uint2 *>(a.Aj16 + qb);
+                const unsigned vcb = *reinterpret_cast<const unsigned *>(a.Ax8 + qb);
+                const unsigned c[8] = {cwa.x & 0xFFFFu, cwa.x >> 16, cwa.y & 0xFFFFu, cwa.y >> 16,
+                                       cwb.x & 0xFFFFu, cwb.x >> 16, cwb.y & 0xFFFFu, cwb.y >> 16};
+                int cc[8];
+                T xv[8];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool ok = (q + j >= p0) && (q + j < p1);
-                T xv;
-                if (a.flags & 4) xv = T(c[j]);
-                else xv = ok ? gather_x<COH>(a, c[j]) : T(0);
-                pr[j] = (DIAGF && (c[j] & DIAG_BIT)) ? T(0) : v[j] * xv;
-            }
-            T2 o0, o1;
-            o0.x = pr[0]; o0.y = pr[1]; o1.x = pr[2]; o1.y = pr[3];
-            *reinterpret_cast<T2 *>(prod + (q - base)) = o0;
-            *reinterpret_cast<T2 *>(prod + (q - base) + 2) = o1;
-            if constexpr (NEEDC) {
-                int4 cm;
-                cm.x = c[0] & COL_MASK; cm.y = c[1] & COL_MASK; cm.z = c[2] & COL_MASK; cm.w = c[3] & COL_MASK;
-                *reinterpret_cast<int4 *>(cols + (q - base)) = cm;
-            }
-        }
-    } else {
-        // two consecutive entries per lane: 8-byte index loads, 16-byte value loads, 16-byte
-        // LDS stores.  base is even, so every pair is naturally aligned; the operator's
-        // arrays are padded so the pair straddling p1 stays inside the allocation.
-        using T2 = typename Vec2<T>::type;
-        const bool nt = (a.flags & 1) != 0;               // stream the operator past the caches
-        if (a.Aj16) {
-            // 16-bit column stream: every column of this row range lies in one of (up to) four windows of 16 K columns;
-            // an entry stores window << 14 | offset.  Two bytes less per entry on the operator stream, same arithmetic.
-            const int4 wb = a.wb;
-            if (vd) {
-                if (a.flags & 16) { stage_val8<T, NEEDC, COH, 6>(a, p0, p1, base, prod, cols, vd); return; }
-                // four consecutive entries per lane and step (8 + 4 bytes of operator stream for them), TWO steps in flight:
-                // with 3 bytes per entry the kernel is bound by its dependent round trips (codes -> gather), so the codes of
-                // both steps are requested before the first gather.  base is a multiple of 4 here.
-                for (int q = base + 4 * tid; q < p1; q += 8 * BLK) {
-                    const int q2 = q + 4 * BLK;
-                    const bool two = q2 < p1;
-                    const int qb = two ? q2 : q;
-                    const uint2 cwa = *reinterpret_cast<const uint2 *>(a.Aj16 + q);
-                    const unsigned vca = *reinterpret_cast<const unsigned *>(a.Ax8 + q);
-                    const uint2 cwb = *reinterpret_cast<const uint2 *>(a.Aj16 + qb);
-                    const unsigned vcb = *reinterpret_cast<const unsigned *>(a.Ax8 + qb);
-                    const unsigned c[8] = {cwa.x & 0xFFFFu, cwa.x >> 16, cwa.y & 0xFFFFu, cwa.y >> 16,
-                                           cwb.x & 0xFFFFu, cwb.x >> 16, cwb.y & 0xFFFFu, cwb.y >> 16};
-                    int cc[8];
-                    T xv[8];
+                for (int j = 0; j < 8; ++j) {
+                    const unsigned w = c[j] >> 14;
+                    cc[j] = (w == 0 ? wb.x : w == 1 ? wb.y : w == 2 ? wb.z : wb.w) + (int)(c[j] & 0x3FFFu);
+                }
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const unsigned w = c[j] >> 14;
-                        cc[j] = (w == 0 ? wb.x : w == 1 ? wb.y : w == 2 ? wb.z : wb.w) + (int)(c[j] & 0x3FFFu);
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        // unconditional (no branch around the load): an entry outside the range reads the first column of
-                        // the window; its product lands in a slot nobody sums (or is not stored at all)
-                        const int e = (j < 4 ? q : qb) + (j & 3);
-                        const bool ok = (e >= p0) && (e < p1);
-                        xv[j] = gather_x<COH>(a, ok ? cc[j] : wb.x);
-                    }
-                    T2 o0, o1;
-                    o0.x = vd[vca & 0xFFu] * xv[0]; o0.y = vd[(vca >> 8) & 0xFFu] * xv[1];
-                    o1.x = vd[(vca >> 16) & 0xFFu] * xv[2]; o1.y = vd[vca >> 24] * xv[3];
-                    *reinterpret_cast<T2 *>(prod + (q - base)) = o0;
-                    *reinterpret_cast<T2 *>(prod + (q - base) + 2) = o1;
+                for (int j = 0; j < 8; ++j) {
+                    // unconditional (no branch around the load): an entry outside the range reads the first column of
+                    // the window; its product lands in a slot nobody sums (or is not stored at all)
+                    const int e = (j < 4 ? q : qb) + (j & 3);
+                    const bool ok = (e >= p0) && (e < p1);
+                    xv[j] = gather_x<COH>(a, ok ? cc[j] : wb.x);
+                }
+                T2 o0, o1;
+                o0.x = vd[vca & 0xFFu] * xv[0]; o0.y = vd[(vca >> 8) & 0xFFu] * xv[1];
+                o1.x = vd[(vca >> 16) & 0xFFu] * xv[2]; o1.y = vd[vca >> 24] * xv[3];
+                *reinterpret_cast<T2 *>(prod + (q - base)) = o0;
+                *reinterpret_cast<T2 *>(prod + (q - base) + 2) = o1;
+                if constexpr (NEEDC) {
+                    int4 cm;
+                    cm.x = cc[0]; cm.y = cc[1]; cm.z = cc[2]; cm.w = cc[3];
+                    *reinterpret_cast<int4 *>(cols + (q - base)) = cm;
+                }
+                if (two) {
+                    o0.x = vd[vcb & 0xFFu] * xv[4]; o0.y = vd[(vcb >> 8) & 0xFFu] * xv[5];
+                    o1.x = vd[(vcb >> 16) & 0xFFu] * xv[6]; o1.y = vd[vcb >> 24] * xv[7];
+                    *reinterpret_cast<T2 *>(prod + (q2 - base)) = o0;
+                    *reinterpret_cast<T2 *>(prod + (q2 - base) + 2) = o1;
                     if constexpr (NEEDC) {
                         int4 cm;
-                        cm.x = cc[0]; cm.y = cc[1]; cm.z = cc[2]; cm.w = cc[3];
-                        *reinterpret_cast<int4 *>(cols + (q - base)) = cm;
-                    }
-                    if (two) {
-                        o0.x = vd[vcb & 0xFFu] * xv[4]; o0.y = vd[(vcb >> 8) & 0xFFu] * xv[5];
-                        o1.x = vd[(vcb >> 16) & 0xFFu] * xv[6]; o1.y = vd[vcb >> 24] * xv[7];
-                        *reinterpret_cast<T2 *>(prod + (q2 - base)) = o0;
-                        *reinterpret_cast<T2 *>(prod + (q2 - base) + 2) = o1;
-                        if constexpr (NEEDC) {
-                            int4 cm;
-                            cm.x = cc[4]; cm.y = cc[5]; cm.z = cc[6]; cm.w = cc[7];
-                            *reinterpret_cast<int4 *>(cols + (q2 - base)) = cm;
-                        }
+                        cm.x = cc[4]; cm.y = cc[5]; cm.z = cc[6]; cm.w = cc[7];
+                        *reinterpret_cast<int4 *>(cols + (q2 - base)) = cm;
                     }
                 }
-                return;
             }
-            // the nontemporal choice is made OUTSIDE the loop (round 6): with the run-time test inside the unrolled body (round 5) the loads sat
-            // under a uniform branch and the fine-level residual went 0.332 -> 0.361 ms -- loads under a branch make the compiler wait
-            // conservatively ("three things the compiler taught us" (a))
-            if (nt) stage_pairs16<T, NEEDC, COH, true>(a, p0, p1, base, prod, cols, wb);
-            else stage_pairs16<T, NEEDC, COH, false>(a, p0, p1, base, prod, cols, wb);
             return;
         }
-        if (nt) stage_pairs32<T, NEEDC, COH, DIAGF, true>(a, p0, p1, base, prod, cols);
-        else stage_pairs32<T, NEEDC, COH, DIAGF, false>(a, p0, p1, base, prod, cols);
+        // the nontemporal choice is made OUTSIDE the loop (round 6): with the run-time test inside the unrolled body (round 5) the loads sat
+        // under a uniform branch and the fine-level residual went 0.332 -> 0.361 ms -- loads under a branch make the compiler wait
+        // conservatively ("three things the compiler taught us" (a))
+        if (nt) stage_pairs16<T, NEEDC, COH, true>(a, p0, p1, base, prod, cols, wb);
+        else stage_pairs16<T, NEEDC, COH, false>(a, p0, p1, base, prod, cols, wb);
+        return;
     }
+    if (nt) stage_pairs32<T, NEEDC, COH, DIAGF, true>(a, p0, p1, base, prod, cols);
+    else stage_pairs32<T, NEEDC, COH, DIAGF, false>(a, p0, p1, base, prod, cols);
 }
 
 // ---- phase 2 pieces
@@ -574,21 +503,21 @@ __device__ __forceinline__ void row_finish(const StreamArgs<T> &a, const RowPre<
 // form).  Round 6, one session (profiles/r06_ab_csr_stream.txt): the run-time tests for value codes in the staged kernel cost the fine-level residual
 // of the 256^3 stencil 0.3355 -> 0.3145 ms (0.699 -> 0.745 of the HBM peak by SURVEY 8(d)), 2000^2 0.0649 -> 0.0574 -- what rounds 3 - 5 had lost since
 // round 2's 0.313 (together with the nontemporal test inside the unrolled staging loop: 0.3475 -> 0.3307).
-template <typename T, int EPI, int NPL, int COH, bool VC = true>
+template <typename T, int EPI, int COH, bool VC = true>
 __device__ __forceinline__ void stream_block(const StreamArgs<T> &a, const int4 meta, unsigned char *smem_raw,
                                              double &sq)
 {
     constexpr bool NEEDC = EpiTraits<EPI>::need_cols;
     const int cap = a.cap;
     // slots per LDS array: the window + the alignment slack below the first entry + the row phase's batch over-read
-    const int slots = cap + ((VC && NPL == 2 && COH == 0 && a.Ax8) ? 16 : 8);
+    const int slots = cap + ((VC && COH == 0 && a.Ax8) ? 16 : 8);
     T *prod = reinterpret_cast<T *>(smem_raw);
     int *cols = reinterpret_cast<int *>(smem_raw + sizeof(T) * (size_t)slots);
     const int tid = threadIdx.x;
     const int r0 = meta.x, r1 = meta.y, p0 = meta.z, p1 = meta.w;
     const T *vd = nullptr;
-    int amask = (NPL == 4) ? ~3 : (NPL == 2) ? ~1 : ~0;
-    if constexpr (VC && NPL == 2 && COH == 0) {
+    int amask = ~1;                                       // two entries per lane: the first staged slot is even
+    if constexpr (VC && COH == 0) {
         if (a.Ax8) {
             // value dictionary -> LDS (behind the products and column ids); read after the barrier below
             T *d = reinterpret_cast<T *>(smem_raw + ((sizeof(T) * (size_t)slots + (NEEDC ? sizeof(int) * (size_t)slots : 0) + 15) & ~(size_t)15));
@@ -602,21 +531,9 @@ __device__ __forceinline__ void stream_block(const StreamArgs<T> &a, const int4 
         int r = r0 + tid;
         RowPre<T> q;
         if (r < r1) q = row_prefetch<T, EPI, COH>(a, r);
-#ifdef PAMG_FAKE_RUNTABLE
-        if constexpr (COH == 0) {
-            // 1 024 values of x (what the ~140 column runs of a range of an SA-level operator hold) by coalesced loads, then the barrier a run-table kernel needs
-            const int c0 = (int)(((unsigned)blockIdx.x * 1024u) & ((1u << 20) - 1u));      // (with flag 4 only, on operators with >= 2^20 + 1024 columns: the SA levels of 256^3)
-            if (a.flags & 4) { for (int i = tid; i < 1024; i += BLK) pamg_fake_xl[i] = (double)a.x[c0 + i]; }     // (ablation flag 4 selects the experiment)
-            __syncthreads();
-        }
-#endif
         if (vd) __syncthreads();
-        stage_products<T, NEEDC, NPL, COH, EpiTraits<EPI>::diag_flag>(a, p0, p1, base, prod, cols, vd);
+        stage_products<T, NEEDC, COH, EpiTraits<EPI>::diag_flag>(a, p0, p1, base, prod, cols, vd);
         __syncthreads();
-        if (a.flags & 8) {                                // ablation: no row phase
-            if (tid == 0) a.y[r0] = prod[0];
-            return;
-        }
         while (r < r1) {
             T s = row_init<T, EPI>(q);
             row_accumulate<T, EPI>(s, prod, cols, q.lo - base, q.hi - base, q.row);
@@ -633,7 +550,7 @@ __device__ __forceinline__ void stream_block(const StreamArgs<T> &a, const int4 
             const int c1 = min(c0 + cap, p1);
             const int base = c0 & amask;
             __syncthreads();
-            stage_products<T, NEEDC, NPL, COH, EpiTraits<EPI>::diag_flag>(a, c0, c1, base, prod, cols, vd);
+            stage_products<T, NEEDC, COH, EpiTraits<EPI>::diag_flag>(a, c0, c1, base, prod, cols, vd);
             __syncthreads();
             if (tid == 0) row_accumulate<T, EPI>(s, prod, cols, c0 - base, c1 - base, q.row);
         }
@@ -641,7 +558,7 @@ __device__ __forceinline__ void stream_block(const StreamArgs<T> &a, const int4 
     }
 }
 
-template <typename T, int EPI, int NPL, bool VC = true>
+template <typename T, int EPI, bool VC = true>
 __global__ __launch_bounds__(BLK) void csr_stream_kernel(const StreamArgs<T> a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -659,12 +576,12 @@ __global__ __launch_bounds__(BLK) void csr_stream_kernel(const StreamArgs<T> a)
     // launch index picks the range out of a list; everything per range (plan, window bases, partial) keeps its place
     if (live && a.blkmap) blk = a.blkmap[blk];
     if (live) {
-        if (NPL == 2 && a.Aj16) {
+        if (a.Aj16) {
             StreamArgs<T> aw = a;
             aw.wb = a.wbase[blk];
-            stream_block<T, EPI, NPL, 0, VC>(aw, a.blkmeta[blk], smem_raw, sq);
+            stream_block<T, EPI, 0, VC>(aw, a.blkmeta[blk], smem_raw, sq);
         } else {
-            stream_block<T, EPI, NPL, 0, VC>(a, a.blkmeta[blk], smem_raw, sq);
+            stream_block<T, EPI, 0, VC>(a, a.blkmeta[blk], smem_raw, sq);
         }
     }
     if constexpr (EPI == EPI_SUMSQ) {
@@ -1165,7 +1082,7 @@ __device__ __forceinline__ void range_finish(const StreamArgs<T> &a, const Range
 // single-workgroup persistent sweep: ranges taken one after the other, separated by
 // __syncthreads(), ordinary cached x accesses (same CU); the static operands of range k+1 are
 // fetched while range k is being reduced.
-template <typename T, int EPI, int NPL>
+template <typename T, int EPI>
 __global__ __launch_bounds__(BLK) void gs_flow1_kernel(const FlowArgs<T> g)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1185,7 +1102,7 @@ __global__ __launch_bounds__(BLK) void gs_flow1_kernel(const FlowArgs<T> g)
             range_finish<T, EPI, 0>(a, cur, smem_raw);
         } else {
             if (blk + 1 < nb) range_prefetch<T, EPI, 0>(a, blk + 1, nxt);
-            stream_block<T, EPI, NPL, 0>(a, a.blkmeta[blk], smem_raw, sq);
+            stream_block<T, EPI, 0>(a, a.blkmeta[blk], smem_raw, sq);
         }
         __syncthreads();
         cur = nxt;
@@ -1348,7 +1265,7 @@ __device__ __forceinline__ void gran_step(const GranArgs<T> &g, RangePre<T> &cur
         if (g.prof && tid == 0) t3 = wall_clock64();
         range_finish<T, EPI, C>(a, cur, smem_raw);
     } else {
-        stream_block<T, EPI, 2, C>(a, a.blkmeta[blk], smem_raw, sq);
+        stream_block<T, EPI, C>(a, a.blkmeta[blk], smem_raw, sq);
     }
     if (g.prof && tid == 0) {
         t4 = wall_clock64();

@@ -66,23 +66,22 @@ int val8_lds(const pamg_matrix_s *A, int epi)
 }
 
 template <typename T, int EPI>
-int launch_epi(int npl, int grid, int lds, hipStream_t s, const StreamArgs<T> &a)
+int launch_epi(int grid, int lds, hipStream_t s, const StreamArgs<T> &a)
 {
     if (grid <= 0) return PAMG_OK;
-    // two entries per lane and staging step (one and four were measured no better and retired in round 5: tune key 1)
-    (void)npl;
+    // two entries per lane and staging step (one and four were measured no better, DESIGN 3, and are gone)
     // flag bit 5: an operator WITHOUT value codes through the instantiation that carries their paths.  Same arithmetic, another instruction
     // schedule: on the SA-level operators of the 256^3 hierarchy (one session, profiles/r06_microbench_sa_ops_vc_ab.txt) A1's residual runs 0.198 ms
     // there and 0.219 in the lean instantiation, R0 0.214 / 0.227 -- but P0 0.187 / 0.162 and the fine-level stencil 0.3355 / 0.3145: the autotune times both
     if (a.Ax8 || (a.flags & 32)) {
         if (lds > 48 * 1024)
-            PAMG_HIP(hipFuncSetAttribute((const void *)csr_stream_kernel<T, EPI, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        hipLaunchKernelGGL((csr_stream_kernel<T, EPI, 2, true>), dim3(grid), dim3(BLK), lds, s, a);
+            PAMG_HIP(hipFuncSetAttribute((const void *)csr_stream_kernel<T, EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        hipLaunchKernelGGL((csr_stream_kernel<T, EPI, true>), dim3(grid), dim3(BLK), lds, s, a);
     } else {
         // no value codes on this operator: the instantiation without their run-time tests (pamg_kernels.h: stream_block)
         if (lds > 48 * 1024)
-            PAMG_HIP(hipFuncSetAttribute((const void *)csr_stream_kernel<T, EPI, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        hipLaunchKernelGGL((csr_stream_kernel<T, EPI, 2, false>), dim3(grid), dim3(BLK), lds, s, a);
+            PAMG_HIP(hipFuncSetAttribute((const void *)csr_stream_kernel<T, EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        hipLaunchKernelGGL((csr_stream_kernel<T, EPI, false>), dim3(grid), dim3(BLK), lds, s, a);
     }
     return (int)hipGetLastError();
 }
@@ -190,22 +189,22 @@ int launch_rowgather(int epi, int grid, int cap, int nvd, hipStream_t s, const S
 }
 
 template <typename T>
-int launch_any(int epi, int npl, int grid, int lds, hipStream_t s, const StreamArgs<T> &a)
+int launch_any(int epi, int grid, int lds, hipStream_t s, const StreamArgs<T> &a)
 {
     switch (epi) {
-        case EPI_SET: return launch_epi<T, EPI_SET>(npl, grid, lds, s, a);
-        case EPI_ACC: return launch_epi<T, EPI_ACC>(npl, grid, lds, s, a);
-        case EPI_RESID: return launch_epi<T, EPI_RESID>(npl, grid, lds, s, a);
-        case EPI_AXPBY: return launch_epi<T, EPI_AXPBY>(npl, grid, lds, s, a);
-        case EPI_ACC_AXPBY: return launch_epi<T, EPI_ACC_AXPBY>(npl, grid, lds, s, a);
-        case EPI_SUMSQ: return launch_epi<T, EPI_SUMSQ>(npl, grid, lds, s, a);
-        case EPI_ACCSEQ: return launch_epi<T, EPI_ACCSEQ>(npl, grid, lds, s, a);
-        case EPI_JACOBI: return launch_epi<T, EPI_JACOBI>(npl, grid, lds, s, a);
-        case EPI_JACOBI_B: return launch_epi<T, EPI_JACOBI_B>(npl, grid, lds, s, a);
-        case EPI_GS: return launch_epi<T, EPI_GS>(npl, grid, lds, s, a);
-        case EPI_GS_B: return launch_epi<T, EPI_GS_B>(npl, grid, lds, s, a);
-        case EPI_SOR: return launch_epi<T, EPI_SOR>(npl, grid, lds, s, a);
-        case EPI_JACOBI_IDX: return launch_epi<T, EPI_JACOBI_IDX>(npl, grid, lds, s, a);
+        case EPI_SET: return launch_epi<T, EPI_SET>(grid, lds, s, a);
+        case EPI_ACC: return launch_epi<T, EPI_ACC>(grid, lds, s, a);
+        case EPI_RESID: return launch_epi<T, EPI_RESID>(grid, lds, s, a);
+        case EPI_AXPBY: return launch_epi<T, EPI_AXPBY>(grid, lds, s, a);
+        case EPI_ACC_AXPBY: return launch_epi<T, EPI_ACC_AXPBY>(grid, lds, s, a);
+        case EPI_SUMSQ: return launch_epi<T, EPI_SUMSQ>(grid, lds, s, a);
+        case EPI_ACCSEQ: return launch_epi<T, EPI_ACCSEQ>(grid, lds, s, a);
+        case EPI_JACOBI: return launch_epi<T, EPI_JACOBI>(grid, lds, s, a);
+        case EPI_JACOBI_B: return launch_epi<T, EPI_JACOBI_B>(grid, lds, s, a);
+        case EPI_GS: return launch_epi<T, EPI_GS>(grid, lds, s, a);
+        case EPI_GS_B: return launch_epi<T, EPI_GS_B>(grid, lds, s, a);
+        case EPI_SOR: return launch_epi<T, EPI_SOR>(grid, lds, s, a);
+        case EPI_JACOBI_IDX: return launch_epi<T, EPI_JACOBI_IDX>(grid, lds, s, a);
     }
     return PAMG_E_ARG;
 }
@@ -234,7 +233,7 @@ int plan_idx16(pamg_matrix_s *A, const std::vector<int4> &blk)
     PhaseTimer pt_("plan_idx16", A->nnz);
     if (A->d_Aj16) { hipFree(A->d_Aj16); A->d_Aj16 = nullptr; }
     if (A->d_wbase) { hipFree(A->d_wbase); A->d_wbase = nullptr; }
-    if (A->npl != 2 || A->nnz == 0 || A->d_rowid) return PAMG_OK;
+    if (A->nnz == 0 || A->d_rowid) return PAMG_OK;
     const int nb = (int)blk.size();
     std::vector<int4> wb((size_t)nb);
     std::vector<unsigned short> code((size_t)A->nnz + 16, 0);
@@ -556,7 +555,7 @@ int build_level_part(pamg_matrix_s *A, GsSchedule *g)
     };
     int gcap = A->gs_cap > 0 ? A->gs_cap : (A->cap_from_val8 ? 1536 : A->cap);
     plan(gcap);
-    if (A->gs_cap == 0 && (A->gs_mode == 0 || A->gs_mode == 2) && gcap > 512 && A->npl == 2) {
+    if (A->gs_cap == 0 && (A->gs_mode == 0 || A->gs_mode == 2) && gcap > 512) {
         // Where this schedule will run as the multi-XCD granular sweep (neither narrow enough for one workgroup nor small
         // enough for the one-XCD form) on SA-like rows, finer ranges win: a range waits for the slowest of its early
         // entries, so 512-entry ranges (~16 rows of 31) track the dependency graph more closely than 1536-entry ones
@@ -956,7 +955,7 @@ int stream_launch_part(pamg_matrix_s *A, int part, int epi, const void *x, const
     if (part) {
         const int n = A->npart[part - 1];
         if (n == 0) return PAMG_OK;
-        const bool idx16 = A->use_idx16 && A->d_Aj16 && A->npl == 2;
+        const bool idx16 = A->use_idx16 && A->d_Aj16;
         const bool val8 = idx16 && A->use_val8 && A->d_Ax8;
         const int lds = lds_bytes(A->dtype, epi, A->cap) + (val8 ? val8_lds(A, epi) : 0) + A->lds_pad;
         const bool rowg = val8 && A->use_rowg && A->max_row_len <= A->cap;
@@ -974,7 +973,7 @@ int stream_launch_part(pamg_matrix_s *A, int part, int epi, const void *x, const
             }
             if (rowp) { const int st = launch_rowpat<double>(epi, n, A, s, a); if (st != 1) return st; }
             if (rowg) { const int st = launch_rowgather<double>(epi, n, A->cap, A->nvdict, s, a); if (st != 1) return st; }
-            return launch_any<double>(epi, A->npl, n, lds, s, a);
+            return launch_any<double>(epi, n, lds, s, a);
         }
         StreamArgs<float> a = base_args<float>(A, x, b, y, c, omega, partial);
         a.flags = A->stream_flags & ~2;
@@ -988,11 +987,11 @@ int stream_launch_part(pamg_matrix_s *A, int part, int epi, const void *x, const
         }
         if (rowp) { const int st = launch_rowpat<float>(epi, n, A, s, a); if (st != 1) return st; }
         if (rowg) { const int st = launch_rowgather<float>(epi, n, A->cap, A->nvdict, s, a); if (st != 1) return st; }
-        return launch_any<float>(epi, A->npl, n, lds, s, a);
+        return launch_any<float>(epi, n, lds, s, a);
     }
     int lds = lds_bytes(A->dtype, epi, A->cap) + A->lds_pad;        // lds_pad (tune key 36): unused LDS that caps the workgroups per CU of the staged kernel
     const int grid = (A->stream_flags & 2) ? 8 * ((A->nblk + 7) / 8) : A->nblk;
-    const bool idx16 = A->use_idx16 && A->d_Aj16 && A->npl == 2;
+    const bool idx16 = A->use_idx16 && A->d_Aj16;
     const bool val8 = idx16 && A->use_val8 && A->d_Ax8;
     if (val8) lds += val8_lds(A, epi);
     const bool rowg = val8 && A->use_rowg && A->max_row_len <= A->cap;
@@ -1004,7 +1003,7 @@ int stream_launch_part(pamg_matrix_s *A, int part, int epi, const void *x, const
         if (rowp && (A->use_rowpat == 1 || A->use_rowpat == 4)) { const int st = launch_rowmask<double>(epi, A, s, a); if (st != 1) return st; }
         if (rowp) { const int st = launch_rowpat<double>(epi, grid, A, s, a); if (st != 1) return st; }
         if (rowg) { const int st = launch_rowgather<double>(epi, grid, A->cap, A->nvdict, s, a); if (st != 1) return st; }
-        return launch_any<double>(epi, A->npl, grid, lds, s, a);
+        return launch_any<double>(epi, grid, lds, s, a);
     }
     StreamArgs<float> a = base_args<float>(A, x, b, y, c, omega, partial);
     a.flags = A->stream_flags;
@@ -1012,7 +1011,7 @@ int stream_launch_part(pamg_matrix_s *A, int part, int epi, const void *x, const
     if (rowp && (A->use_rowpat == 1 || A->use_rowpat == 4)) { const int st = launch_rowmask<float>(epi, A, s, a); if (st != 1) return st; }
     if (rowp) { const int st = launch_rowpat<float>(epi, grid, A, s, a); if (st != 1) return st; }
     if (rowg) { const int st = launch_rowgather<float>(epi, grid, A->cap, A->nvdict, s, a); if (st != 1) return st; }
-    return launch_any<float>(epi, A->npl, grid, lds, s, a);
+    return launch_any<float>(epi, grid, lds, s, a);
 }
 
 // grid ceiling of the granular sweep: its workgroups must be co-resident; (occupancy - 1, at most
@@ -1044,10 +1043,9 @@ static int gran2_launch(int epi, int grid, int lds, hipStream_t s, const GranArg
 }
 
 template <typename T, int EPI>
-static int flow1_launch(int npl, int lds, hipStream_t s, const FlowArgs<T> &f)
+static int flow1_launch(int lds, hipStream_t s, const FlowArgs<T> &f)
 {
-    (void)npl;
-    hipLaunchKernelGGL((gs_flow1_kernel<T, EPI, 2>), dim3(1), dim3(BLK), lds, s, f);
+    hipLaunchKernelGGL((gs_flow1_kernel<T, EPI>), dim3(1), dim3(BLK), lds, s, f);
     return (int)hipGetLastError();
 }
 
@@ -1309,7 +1307,7 @@ static int gs_sweep_scalar_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, 
     const bool can_persist = lds <= 48 * 1024 && g->nlevels > 1 && A->gs_mode != 1;
     const bool narrow = (int64_t)g->nblk_total * 16 <= (int64_t)g->nlevels * A->flow_cap;
     const bool single = can_persist && (A->gs_mode == 3 || ((A->gs_mode == 0 || A->gs_mode == 5) && narrow));
-    const bool granular = can_persist && !single && A->npl == 2 && g->d_xs;
+    const bool granular = can_persist && !single && g->d_xs;
     if (single) {
         FlowArgs<T> f;
         f.s = a;
@@ -1318,9 +1316,9 @@ static int gs_sweep_scalar_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, 
         f.nlevels = g->nlevels;
         f.sync = g->d_sync;
         switch (epi) {
-            case EPI_GS: return flow1_launch<T, EPI_GS>(A->npl, lds, s, f);
-            case EPI_GS_B: return flow1_launch<T, EPI_GS_B>(A->npl, lds, s, f);
-            case EPI_SOR: return flow1_launch<T, EPI_SOR>(A->npl, lds, s, f);
+            case EPI_GS: return flow1_launch<T, EPI_GS>(lds, s, f);
+            case EPI_GS_B: return flow1_launch<T, EPI_GS_B>(lds, s, f);
+            case EPI_SOR: return flow1_launch<T, EPI_SOR>(lds, s, f);
             default: return PAMG_E_ARG;
         }
     }
@@ -1367,7 +1365,7 @@ static int gs_sweep_scalar_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, 
     for (int l = 0; l < g->nlevels; ++l) {
         a.blkmeta = g->d_blkmeta + g->level_blk[l];
         a.nblk = g->level_blk[l + 1] - g->level_blk[l];
-        PAMG_TRY(launch_any<T>(epi, A->npl, a.nblk, lds, s, a));
+        PAMG_TRY(launch_any<T>(epi, a.nblk, lds, s, a));
     }
     return PAMG_OK;
 }
@@ -1829,7 +1827,7 @@ int matrix_row_subset(pamg_matrix_s *A, const int32_t *rows, int nrows, pamg_mat
     rid.resize((size_t)nrows + 8, 0);
     if (!st) st = upload(&B->d_rowid, rid.data(), rid.size(), &B->bytes);
     B->h_Aj.resize((size_t)B->nnz);
-    B->cap = 1536; B->npl = 2; B->max_rows = 1024;
+    B->cap = 1536; B->max_rows = 1024;
     if (!st) st = replan(B);
     if (st) { pamg_matrix_destroy(B); return st; }
     *out = B;
@@ -2053,7 +2051,7 @@ int pamg_matrix_create(pamg_matrix_t *out, int dtype, int flavour, int n_brow, i
     }
     // default plan (measured best on 256^3 Poisson): 1536 staged entries = 12 KB (SpMV) / 18 KB
     // (smoothers, with column ids) of LDS per workgroup -> 8 workgroups = 32 waves per CU
-    A->cap = 1536; A->npl = 2; A->max_rows = 1024;
+    A->cap = 1536; A->max_rows = 1024;
     // with 8-bit value codes the whole-operator kernels stage four entries per lane in two steps that are in flight
     // together: 2048 entries fill both (measured on the 256^3 stencil: 0.242 ms against 0.262 with 1536); the level
     // schedules of the order-exact sweeps keep 1536
@@ -2123,14 +2121,14 @@ int pamg_matrix_info(pamg_matrix_t A, int64_t info[8])
 int pamg_matrix_value_codes(pamg_matrix_t A, int *n_values)
 {
     if (!A || !n_values) return PAMG_E_ARG;
-    *n_values = (A->d_Ax8 && A->use_val8 && A->use_idx16 && A->d_Aj16 && A->npl == 2) ? A->nvdict : 0;
+    *n_values = (A->d_Ax8 && A->use_val8 && A->use_idx16 && A->d_Aj16) ? A->nvdict : 0;
     return PAMG_OK;
 }
 
 int pamg_matrix_row_patterns(pamg_matrix_t A, int *n_patterns)
 {
     if (!A || !n_patterns) return PAMG_E_ARG;
-    *n_patterns = (A->d_pid && A->use_rowpat && A->d_Ax8 && A->use_val8 && A->use_idx16 && A->d_Aj16 && A->npl == 2) ? A->npat : 0;
+    *n_patterns = (A->d_pid && A->use_rowpat && A->d_Ax8 && A->use_val8 && A->use_idx16 && A->d_Aj16) ? A->npat : 0;
     return PAMG_OK;
 }
 
@@ -2161,13 +2159,12 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
     if (A->borrowed > 0) return PAMG_E_STATE;
     switch (key) {
         case 0: if (value < 64 || value > 12288) return PAMG_E_ARG; A->cap = value & ~3; A->cap_from_val8 = 0; break;
-        case 1: if (value != 2) return PAMG_E_ARG; A->npl = 2; return PAMG_OK;      // 1 and 4 entries per lane: measured no better, retired in round 5
         case 2: if (value < 1) return PAMG_E_ARG; A->max_rows = value; break;
         case 3: if (value < 0 || value > 256) return PAMG_E_ARG; A->flow_cap = value; return PAMG_OK;
         case 5: if (value < 0 || value > 5) return PAMG_E_ARG; A->gs_mode = value; return PAMG_OK;
         case 6: if (value < 0) return PAMG_E_ARG; A->gran_cap = value; return PAMG_OK;
         case 7: if (value < 0 || value > 2) return PAMG_E_ARG; A->gran_xcd = value; matrix_drop_point_twin(A); return PAMG_OK;
-        case 8: if (value < 0 || value > 63) return PAMG_E_ARG; A->stream_flags = value; return PAMG_OK;
+        case 8: if (value < 0 || value > 63 || (value & 12)) return PAMG_E_ARG; A->stream_flags = value; return PAMG_OK;      // bits 2, 3: retired (ablations that computed wrong results)
         case 11: A->gs_prof = value != 0; return PAMG_OK;
         case 12: if (value < 0) return PAMG_E_ARG; A->tile_G = value; break;
         case 13: if (value != 0 && (value < 64 || value > 8192 || (value & (value - 1)))) return PAMG_E_ARG; A->tile_W = value; break;
@@ -2235,7 +2232,7 @@ int pamg_matrix_autotune(pamg_matrix_t A, int allow_cap)
 {
     if (!A) return PAMG_E_ARG;
     if (A->borrowed > 0) return PAMG_E_STATE;
-    if (A->nnz < 4000000 || A->npl != 2) return PAMG_OK;
+    if (A->nnz < 4000000) return PAMG_OK;
     const size_t ts = tsize(A->dtype);
     void *x = nullptr, *y = nullptr;
     PAMG_HIP(hipMalloc(&x, (size_t)(A->ncols + 8) * ts));

@@ -12,6 +12,7 @@
 //            shuffles are never under a divergent branch), a finished group idles.  The arithmetic is pamg_dense_pinv.h.
 #include "pamg_common.h"
 #include "pamg_dense_pinv.h"
+#include "pamg_host_call.h"
 
 using namespace pamg;
 
@@ -255,11 +256,6 @@ int launch_all(bool invert, const int *lists, int nsub, const unsigned long long
     return PAMG_OK;
 }
 
-struct Scratch {
-    void *p = nullptr;
-    ~Scratch() { if (p) hipFree(p); }
-};
-
 }  // namespace
 
 namespace pamg {
@@ -273,14 +269,15 @@ int schwarz_blocks_device(int dtype, pamg_matrix_s *A, int nsub, const int *d_Sp
     if (A->dtype != dtype) return PAMG_E_ARG;
     if (!A->d_Ap || !A->d_Aj || !A->d_Ax) return PAMG_E_UNSUPPORTED;
     if (info) info[0] = info[1] = info[2] = info[3] = 0;
-    Scratch tp64, lists, cw;
-    PAMG_HIP(hipMalloc(&tp64.p, sizeof(long long) * ((size_t)nsub + 1)));
-    PAMG_HIP(hipMalloc(&lists.p, sizeof(int) * std::max<size_t>(1, (size_t)dpinv::NCLASS * nsub)));
-    PAMG_HIP(hipMalloc(&cw.p, sizeof(unsigned long long) * CW_WORDS));
+    Bufs d;
+    long long *tp64;
+    int *lists;
+    unsigned long long *cw;
+    PAMG_TRY(d.get(&tp64, (size_t)nsub + 1)); PAMG_TRY(d.get(&lists, (size_t)dpinv::NCLASS * nsub)); PAMG_TRY(d.get(&cw, (size_t)CW_WORDS));
     unsigned long long h_cw[CW_WORDS];
-    hipLaunchKernelGGL(schwarz_plan_kernel, dim3(1), dim3(PLAN_T), 0, s, nsub, d_Sp, (long long *)tp64.p, (int *)lists.p, (unsigned long long *)cw.p);
+    hipLaunchKernelGGL(schwarz_plan_kernel, dim3(1), dim3(PLAN_T), 0, s, nsub, d_Sp, tp64, lists, cw);
     PAMG_HIP(hipGetLastError());
-    PAMG_HIP(hipMemcpyAsync(h_cw, cw.p, sizeof(h_cw), hipMemcpyDeviceToHost, s));
+    PAMG_HIP(hipMemcpyAsync(h_cw, cw, sizeof(h_cw), hipMemcpyDeviceToHost, s));
     PAMG_HIP(hipStreamSynchronize(s));
     if (info) { info[0] = (int64_t)h_cw[CW_TOTAL]; info[1] = (int64_t)h_cw[CW_MAXM]; }
     if (h_cw[CW_BAD]) return PAMG_E_ARG;
@@ -289,7 +286,7 @@ int schwarz_blocks_device(int dtype, pamg_matrix_s *A, int nsub, const int *d_Sp
     const size_t ts = tsize(dtype);
     if (!tp_given) {
         if ((int64_t)h_cw[CW_TOTAL] > Tx_capacity) return PAMG_E_ARG;
-        hipLaunchKernelGGL(schwarz_tp_narrow_kernel, dim3((unsigned)(nsub / 256 + 1)), dim3(256), 0, s, nsub + 1, (const long long *)tp64.p, d_Tp);
+        hipLaunchKernelGGL(schwarz_tp_narrow_kernel, dim3((unsigned)(nsub / 256 + 1)), dim3(256), 0, s, nsub + 1, (const long long *)tp64, d_Tp);
         PAMG_HIP(hipGetLastError());
         if (h_cw[CW_TOTAL]) PAMG_HIP(hipMemsetAsync(d_Tx, 0, ts * (size_t)h_cw[CW_TOTAL], s));
     } else if (Tx_capacity) {
@@ -298,10 +295,10 @@ int schwarz_blocks_device(int dtype, pamg_matrix_s *A, int nsub, const int *d_Sp
     if (h_cw[CW_TOTAL] == 0) return PAMG_OK;
     if (!d_Sj || !d_Tx) return PAMG_E_ARG;
     for (int pass = 0; pass < (invert ? 2 : 1); ++pass) {
-        if (dtype == PAMG_F64) PAMG_TRY(launch_all<double>(pass == 1, (const int *)lists.p, nsub, h_cw, d_Sp, d_Sj, d_Tp, A, (double *)d_Tx, rank_tol, (unsigned long long *)cw.p, s));
-        else PAMG_TRY(launch_all<float>(pass == 1, (const int *)lists.p, nsub, h_cw, d_Sp, d_Sj, d_Tp, A, (float *)d_Tx, rank_tol, (unsigned long long *)cw.p, s));
+        if (dtype == PAMG_F64) PAMG_TRY(launch_all<double>(pass == 1, lists, nsub, h_cw, d_Sp, d_Sj, d_Tp, A, (double *)d_Tx, rank_tol, cw, s));
+        else PAMG_TRY(launch_all<float>(pass == 1, lists, nsub, h_cw, d_Sp, d_Sj, d_Tp, A, (float *)d_Tx, rank_tol, cw, s));
     }
-    PAMG_HIP(hipMemcpyAsync(h_cw, cw.p, sizeof(h_cw), hipMemcpyDeviceToHost, s));
+    PAMG_HIP(hipMemcpyAsync(h_cw, cw, sizeof(h_cw), hipMemcpyDeviceToHost, s));
     PAMG_HIP(hipStreamSynchronize(s));
     if (info) { info[2] = (int64_t)h_cw[CW_SWEEPS]; info[3] = (int64_t)h_cw[CW_TRUNC]; }
     if (h_cw[CW_BAD]) return PAMG_E_ARG;
@@ -328,21 +325,17 @@ int pamg_schwarz_blocks(int dtype, pamg_matrix_t A, int nsub, const int32_t *Sp,
     const size_t nS = (size_t)Sp[nsub];
     if (nS && !Sj) return PAMG_E_ARG;
     if (Tx_capacity && !Tx) return PAMG_E_ARG;
-    Scratch dSp, dSj, dTp, dTx;
+    Bufs d;
+    int *dSp, *dSj, *dTp;
+    char *dTx;                                  // Tx_capacity values of dtype
     const size_t ts = tsize(dtype);
-    PAMG_HIP(hipMalloc(&dSp.p, sizeof(int) * ((size_t)nsub + 1)));
-    PAMG_HIP(hipMalloc(&dSj.p, sizeof(int) * std::max<size_t>(nS, 1)));
-    PAMG_HIP(hipMalloc(&dTp.p, sizeof(int) * ((size_t)nsub + 1)));
-    PAMG_HIP(hipMalloc(&dTx.p, ts * std::max<size_t>((size_t)Tx_capacity, 1)));
-    PAMG_HIP(hipMemcpy(dSp.p, Sp, sizeof(int) * ((size_t)nsub + 1), hipMemcpyHostToDevice));
-    if (nS) PAMG_HIP(hipMemcpy(dSj.p, Sj, sizeof(int) * nS, hipMemcpyHostToDevice));
+    PAMG_TRY(d.put(&dSp, Sp, (size_t)nsub + 1)); PAMG_TRY(d.put(&dSj, Sj, nS));
+    PAMG_TRY(d.get(&dTp, (size_t)nsub + 1)); PAMG_TRY(d.get(&dTx, ts * (size_t)Tx_capacity));
     int64_t loc[4];
     int64_t *inf = info ? info : loc;
-    PAMG_TRY(schwarz_blocks_device(dtype, A, nsub, (const int *)dSp.p, (const int *)dSj.p, (int *)dTp.p, dTx.p, Tx_capacity, rank_tol, invert,
-                                   false, nullptr, inf));
-    PAMG_HIP(hipMemcpy(Tp, dTp.p, sizeof(int) * ((size_t)nsub + 1), hipMemcpyDeviceToHost));
-    if (inf[0]) PAMG_HIP(hipMemcpy(Tx, dTx.p, ts * (size_t)inf[0], hipMemcpyDeviceToHost));
-    return PAMG_OK;
+    PAMG_TRY(schwarz_blocks_device(dtype, A, nsub, dSp, dSj, dTp, dTx, Tx_capacity, rank_tol, invert, false, nullptr, inf));
+    PAMG_TRY(Bufs::fetch(Tp, dTp, (size_t)nsub + 1));
+    return Bufs::fetch((char *)Tx, dTx, ts * (size_t)inf[0]);
 }
 
 }  // extern "C"

@@ -25,14 +25,13 @@ def _dev(*arrs):
 
 
 @pytest.mark.parametrize("tag", ["pois", "irr"])
-@pytest.mark.parametrize("npl", [2])
 @pytest.mark.parametrize("cap", [64, 2048])
-def test_spmv_family_bit_exact(kernels_npz, tag, npl, cap):
+def test_spmv_family_bit_exact(kernels_npz, tag, cap):
     z = kernels_npz
     A = _csr(z, tag)
     x, b = z[f"{tag}.x"], z[f"{tag}.b"]
     dA = DeviceMatrix(sparse_op(A))
-    dA.tune(lds_entries=cap, nnz_per_lane=npl)
+    dA.tune(lds_entries=cap)
     dx, db = _dev(x, b)
     dy = capi.DeviceArray(A.shape[0], np.float64)
     dA.spmv(capi.SPMV_SET, dx, dy)
@@ -54,13 +53,13 @@ def test_spmv_family_bit_exact(kernels_npz, tag, npl, cap):
 
 
 @pytest.mark.parametrize("tag", ["pois", "irr"])
-@pytest.mark.parametrize("npl,cap", [(2, 64), (2, 2048)])
-def test_relaxation_bit_exact_vs_reference_outputs(kernels_npz, tag, npl, cap):
+@pytest.mark.parametrize("cap", [64, 2048])
+def test_relaxation_bit_exact_vs_reference_outputs(kernels_npz, tag, cap):
     z = kernels_npz
     A = _csr(z, tag)
     x, b = z[f"{tag}.x"], z[f"{tag}.b"]
     dA = DeviceMatrix(sparse_op(A))
-    dA.tune(lds_entries=cap, nnz_per_lane=npl)
+    dA.tune(lds_entries=cap)
     (db,) = _dev(b)
     work = capi.DeviceArray(3 * A.shape[0], np.float64)
     for sweep in ("forward", "backward", "symmetric"):
@@ -81,7 +80,7 @@ def test_relaxation_bit_exact_vs_reference_outputs(kernels_npz, tag, npl, cap):
     assert np.array_equal(dx.download(), z[f"{tag}.poly0"])
     # BSR(1,1) flavour: arithmetic order of amg_core::bsr_jacobi / bsr_gauss_seidel
     dB = DeviceMatrix(sparse_op(A.tobsr(blocksize=(1, 1))))
-    dB.tune(lds_entries=cap, nnz_per_lane=npl)
+    dB.tune(lds_entries=cap)
     (dx,) = _dev(x)
     dB.jacobi(dx, db, work, 0.8, iterations=2)
     assert np.array_equal(dx.download(), z[f"{tag}.bsr1.jacobi"])
@@ -201,23 +200,23 @@ def test_edge_cases_and_long_rows(dtype):
     M.sort_indices()
     op = sparse_op(M)
     x = rng.rand(n).astype(dtype); b = rng.rand(n).astype(dtype)
-    for npl, cap in [(2, 64), (2, 128), (2, 2048)]:
+    for cap in [64, 128, 2048]:
         dM = DeviceMatrix(op)
-        dM.tune(lds_entries=cap, nnz_per_lane=npl)
+        dM.tune(lds_entries=cap)
         dx, db = _dev(x, b)
         dy = capi.DeviceArray(n, dtype)
         dM.spmv(capi.SPMV_SET, dx, dy)
-        assert np.array_equal(dy.download(), orc.matvec(op, x)), (npl, cap)
+        assert np.array_equal(dy.download(), orc.matvec(op, x)), cap
         c = x.copy()
         orc.relax_gauss_seidel(op, c, b, 1, "symmetric")
         dM.gauss_seidel(dx, db, sweep="symmetric")
-        assert np.array_equal(dx.download(), c), (npl, cap)
+        assert np.array_equal(dx.download(), c), cap
         c = x.copy()
         orc.relax_jacobi(op, c, b, 2, 0.5)
         (dx,) = _dev(x)
         work = capi.DeviceArray(n, dtype)
         dM.jacobi(dx, db, work, 0.5, iterations=2)
-        assert np.array_equal(dx.download(), c), (npl, cap)
+        assert np.array_equal(dx.download(), c), cap
     # n = 1 and an all-zero operator
     one = sparse_op(sp.csr_array(np.array([[2.0]], dtype=dtype)))
     dO = DeviceMatrix(one)
@@ -235,6 +234,64 @@ def test_edge_cases_and_long_rows(dtype):
     E0 = sparse_op(sp.csr_array((0, 0), dtype=dtype))
     dE = DeviceMatrix(E0)
     assert dE.info()["rows"] == 0
+
+
+def test_stream_flags_compute_the_same_bits_and_retired_values_are_refused(kernels_npz):
+    """Tune key 8: bits 0 (nontemporal stream), 1 (XCD-aware range order) and 5 (value-code instantiation) are speed only -- y = A x, the
+    residual and a Jacobi step are the oracle's bits under every combination; a value with the retired bits 2 / 3 is PAMG_E_ARG and leaves
+    the operator as it was; key 1 (entries per lane) is gone.  lds_entries = 64: many row ranges (the XCD-order grid rounded to 8 with
+    dead workgroups, rows longer than the window); 2048: one range.  The five-point operators carry value codes: they also run with the
+    row-gather and row-pattern forms off, i.e. through the staged kernel's value-code paths."""
+    from oracle import oracle as orc
+    z = kernels_npz
+    T = sp.diags_array([-np.ones(39), 2.0 * np.ones(40), -np.ones(39)], offsets=[-1, 0, 1])
+    five = sp.csr_array(sp.kron(sp.eye_array(40), T) + sp.kron(T, sp.eye_array(40)))
+    five.sort_indices()
+    rng = np.random.RandomState(5)
+    cases = [(_csr(z, tag), z[f"{tag}.x"], z[f"{tag}.b"], [{}]) for tag in ("pois", "irr")]
+    for dtype in (np.float64, np.float32):
+        cases.append((five.astype(dtype), rng.rand(1600).astype(dtype), rng.rand(1600).astype(dtype), [{}, {"rowgather": 0, "rowpat": 0}]))
+    lib = capi.lib()
+    for A, x, b, forms in cases:
+        op = sparse_op(A)
+        n, dtype = A.shape[0], A.dtype
+        Ax = orc.matvec(op, x)
+        xj = x.copy()
+        orc.relax_jacobi(op, xj, b, 1, 0.8)
+        ref = (Ax, b - Ax, xj)
+        for form in forms:
+            for cap in (64, 2048):
+                dA = DeviceMatrix(op)
+                dA.tune(lds_entries=cap, **form)
+                db, = _dev(b)
+                work = capi.DeviceArray(3 * n, dtype)
+
+                def run():
+                    (dx,) = _dev(x)
+                    dy = capi.DeviceArray(n, dtype)
+                    dA.spmv(capi.SPMV_SET, dx, dy)
+                    y = dy.download()
+                    dA.spmv(capi.SPMV_RESID, dx, dy, b=db)
+                    r = dy.download()
+                    dA.jacobi(dx, db, work, 0.8, iterations=1)
+                    return y, r, dx.download()
+
+                dA.tune(stream_flags=0)
+                base = run()
+                for got, want in zip(base, ref):
+                    assert np.array_equal(got, want), (dtype, form, cap)
+                for fl in (4, 8, 12, 5, 63):
+                    with pytest.raises(capi.PamgError) as e:
+                        dA.tune(stream_flags=fl)
+                    assert e.value.status == capi.E_ARG, fl
+                    for got, want in zip(run(), base):
+                        assert np.array_equal(got, want), (dtype, form, cap, fl)
+                for fl in (1, 2, 3, 32, 33, 34, 35):
+                    dA.tune(stream_flags=fl)
+                    for got, want0, want in zip(run(), base, ref):
+                        assert np.array_equal(got, want0) and np.array_equal(got, want), (dtype, form, cap, fl)
+                assert lib.pamg_matrix_tune(dA.handle, 1, 2) == lib.pamg_matrix_tune(dA.handle, 1000, 2) == capi.E_ARG     # an unknown key
+                dA.free()
 
 
 def test_relaxation_module_contract():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the general CSR kernel (csr_stream_kernel<double, RESID, npl2>) between library builds inside ONE session (boxes of the pool differ
+"""A/B of the general CSR kernel (csr_stream_kernel<double, RESID>) between library builds inside ONE session (boxes of the pool differ
 by up to 7 %): every build runs in its own process (PAMG_LIB), rounds interleaved, best and median of each.
 
     python tools/ab_csr_stream.py libA.so libB.so [...]   (paths relative to the repo root; 'head' = pyamg_amd/libpyamg_amd.so)

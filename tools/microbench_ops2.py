@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Lane mappings of the staged kernel on the operators of a real SA hierarchy (A1, P0, R0 of 256^3): two consecutive entries
-per lane (default) against one (lanes on consecutive entries), a few LDS windows.  Not product code."""
+"""The staged kernel on the operators of a real SA hierarchy (A1, P0, R0 of 256^3) over a few LDS windows.  Not product code."""
 import json, sys, time
 from pathlib import Path
 import numpy as np
@@ -33,14 +32,13 @@ for li, L in enumerate(spec.levels[:2]):
         dx = capi.DeviceArray.from_host(rng.rand(op.shape[1])); dy = capi.DeviceArray(op.shape[0], np.float64)
         rec = {}
         ref = None
-        for npl in (2,):
-            for cap in (1536, 1024, 768, 2048):
-                dM.tune(lds_entries=cap, nnz_per_lane=npl, stream_flags=0)
-                ms = timeit(lambda: dM.spmv(capi.SPMV_SET, dx, dy), 10)
-                got = dy.download()
-                if ref is None:
-                    ref = got
-                rec[f"npl{npl}/cap{cap}"] = [round(ms, 4), bool(np.array_equal(ref, got))]
+        for cap in (1536, 1024, 768, 2048):
+            dM.tune(lds_entries=cap, stream_flags=0)
+            ms = timeit(lambda: dM.spmv(capi.SPMV_SET, dx, dy), 10)
+            got = dy.download()
+            if ref is None:
+                ref = got
+            rec[f"cap{cap}"] = [round(ms, 4), bool(np.array_equal(ref, got))]
         print(f"L{li}.{nm} {op.shape} nnz={op.nnz} nnz/row={op.nnz/op.shape[0]:.1f}  ms: {rec}", flush=True)
         out[f"L{li}.{nm}"] = rec
         dM.free(); dx.free(); dy.free()

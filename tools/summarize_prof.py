@@ -24,9 +24,9 @@ EPI = ["SET", "ACC", "RESID", "AXPBY", "ACC_AXPBY", "SUMSQ", "ACCSEQ", "JACOBI",
 
 
 def short(name):
-    m = re.search(r"csr_stream_kernel<(\w+), *(\d+), *(\d+)(?:, *(\w+))?>", name)
+    m = re.search(r"csr_stream_kernel<(\w+), *(\d+)(?:, *[\w()]+)*>", name)
     if m:
-        return f"csr_stream<{m.group(1)},{EPI[int(m.group(2))]},npl{m.group(3)}>"
+        return f"csr_stream<{m.group(1)},{EPI[int(m.group(2))]}>"
     m = re.search(r"csr_(rowgather|rowpat)_kernel<(\w+), *(\d+)>", name)
     if m:
         return f"csr_{m.group(1)}<{m.group(2)},{EPI[int(m.group(3))]}>"
@@ -68,7 +68,7 @@ def short(name):
 
 def family(k):
     if k.startswith("csr_"):
-        m = re.search(r",(\w+?)(,npl\d|,kz\d|,nu\d)?>", k)
+        m = re.search(r",(\w+?)(,kz\d|,nu\d)?>", k)
         return "csr", (m.group(1) if m else None)
     if k.startswith("gs_lanem"):
         return ("gs_lanem_zero" if ",zero>" in k else "gs_lanem_corr" if ",corr>" in k else "gs_lanem"), None
