@@ -17,10 +17,10 @@
 // (amg_core::bsr_gauss_seidel), for float operators and for block sizes other than 2, 3, 4, 6.
 #include "pamg_common.h"
 #include "pamg_blane_plan.h"
+#include "pamg_wave.h"
+#include "pamg_sweep_host.h"
 
 namespace pamg {
-
-constexpr unsigned long long BL_SENTINEL = 0x7FF8DEADBEEF5A5Aull;     // the pattern of the exact sweeps (pamg_kernels.h)
 
 struct BlaneSched {
     int L = 0, K = 0, RPW = 0, bs = 0, nlevels = 0;
@@ -59,47 +59,6 @@ struct BlaneDyn {
     double xv[K][BS];
     long long t0;
 };
-
-template <int CTRL>
-__device__ __forceinline__ double bl_dpp(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);       // (no `old` operand: every lane has a source, the compiler needs no copy)
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-// lane ^ 16 and lane ^ 32 without the LDS path: v_permlane16_swap / v_permlane32_swap (CDNA4) exchange the odd 16-lane rows (the upper half) of
-// one copy with the even rows (the lower half) of the other -- afterwards one copy holds the even-row (lower-half) values everywhere, the other the
-// odd-row (upper-half) values, and their sum is the XOR-butterfly step (the same two addends in both partner lanes).  ds_swizzle / ds_bpermute cost
-// ~100 cycles of latency each and a wait per value: 0.6 us of the 0.64 us between the last operand and the publish with six sums and 64 lanes.
-__device__ __forceinline__ double bl_xor16_sum(double v)
-{
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-__device__ __forceinline__ double bl_xor32_sum(double v)
-{
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-// the butterfly of the scalar lane form (pamg_lane.hip: seg_allreduce): the same partners in the same order
-template <int L>
-__device__ __forceinline__ double bl_allreduce(double v)
-{
-    v = v + bl_dpp<0xB1>(v);
-    v = v + bl_dpp<0x4E>(v);
-    if constexpr (L >= 8) v = v + bl_dpp<0x141>(v);
-    if constexpr (L >= 16) v = v + bl_dpp<0x140>(v);
-    if constexpr (L >= 32) v = bl_xor16_sum(v);
-    if constexpr (L >= 64) v = bl_xor32_sum(v);
-    return v;
-}
-
-__device__ __forceinline__ bool bl_missing(double v) { return (unsigned long long)__double_as_longlong(v) == BL_SENTINEL; }
 
 template <int BS, int L, int K>
 __device__ __forceinline__ void blane_load(const BlaneArgs &a, int g, BlaneSet<BS, K> &S)
@@ -154,7 +113,7 @@ __device__ __forceinline__ void blane_finish(const BlaneArgs &a, const BlaneSet<
         if ((S.c[k] & LANE_EARLY) && !(S.c[k] & LANE_NONE)) {
             bool miss = false;
 #pragma unroll
-            for (int e = 0; e < BS; ++e) miss = miss || bl_missing(D.xv[k][e]);
+            for (int e = 0; e < BS; ++e) miss = miss || Sentinel<double>::missing(D.xv[k][e]);
             if (miss) pend |= 1u << k;
         }
     unsigned spins = 0;
@@ -164,7 +123,7 @@ __device__ __forceinline__ void blane_finish(const BlaneArgs &a, const BlaneSet<
         const double *gp = a.xs + (size_t)S.gate * BS + (BS - 1);
         while (true) {
             const double gv = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!bl_missing(gv)) break;
+            if (!Sentinel<double>::missing(gv)) break;
             __builtin_amdgcn_s_sleep(2);
             if ((++spins & 1023u) == 0 && (spins > (1u << 21) || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) break;
         }
@@ -184,7 +143,7 @@ __device__ __forceinline__ void blane_finish(const BlaneArgs &a, const BlaneSet<
             if ((pend >> k) & 1u) {
                 bool miss = false;
 #pragma unroll
-                for (int e = 0; e < BS; ++e) { D.xv[k][e] = t[k][e]; miss = miss || bl_missing(t[k][e]); }
+                for (int e = 0; e < BS; ++e) { D.xv[k][e] = t[k][e]; miss = miss || Sentinel<double>::missing(t[k][e]); }
                 if (!miss) pend &= ~(1u << k);
             }
         if ((++spins & 1023u) == 0) {
@@ -209,7 +168,7 @@ __device__ __forceinline__ void blane_finish(const BlaneArgs &a, const BlaneSet<
         }
     }
 #pragma unroll
-    for (int r = 0; r < BS; ++r) acc[r] = bl_allreduce<L>(acc[r]);
+    for (int r = 0; r < BS; ++r) acc[r] = seg_allreduce<L>(acc[r]);
     // lane q < bs of the block row: component q of Dinv_i (b_i - sum)   (relaxation.h:1283-1292)
     double nv = 0.0;
 #pragma unroll
@@ -220,11 +179,7 @@ __device__ __forceinline__ void blane_finish(const BlaneArgs &a, const BlaneSet<
         else __hip_atomic_store(a.xs + o, nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         a.y[o] = nv;
     }
-    if (a.prof && lane == 0) {
-        long long *o = a.prof + (size_t)g * 4;
-        o[0] = D.t0; o[1] = t1; o[2] = wall_clock64();
-        o[3] = (long long)((__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) | (blockIdx.x << 4));
-    }
+    if (a.prof && lane == 0) profile_stamp(a.prof + (size_t)g * 4, D.t0, t1);
 }
 
 constexpr int BLANE_WPB = BLK / 64;
@@ -236,7 +191,6 @@ constexpr int BLANE_WPB = BLK / 64;
 template <int BS, int L, int K, int MODE>
 __global__ __launch_bounds__(BLK) void bsr_lane_kernel(const BlaneArgs a)
 {
-    const int lane = threadIdx.x & 63;
     const int wib = threadIdx.x >> 6;
     const int idle = (int)((((unsigned)blockIdx.x * BLANE_WPB + (unsigned)wib) * 16u) % (unsigned)a.nidle);
     BlaneSet<BS, K> P;
@@ -249,49 +203,24 @@ __global__ __launch_bounds__(BLK) void bsr_lane_kernel(const BlaneArgs a)
             blane_finish<BS, L, K, MODE>(a, P, D, g, idle);
         }
     } else {
-        __shared__ int sh_home;
-        if (threadIdx.x == 0) {
-            const unsigned me = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) + 1u;     // HW_REG_XCC_ID[3:0] + 1
-            unsigned home = 0u;
-            __hip_atomic_compare_exchange_strong(a.ticket + 1, &home, me, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            sh_home = (home == 0u || home == me) ? 1 : 0;
-        }
-        __syncthreads();
-        if (!sh_home) return;
-        // tickets: lane 0 draws, the wave reads lane 0's register; taken in increasing order by running waves: complete for any placement.
+        if (!claim_home_xcd(a.ticket + 1)) return;
+        // tickets are taken in increasing order by running waves: complete for any placement.
         // The next ticket is drawn while the current group waits (the atomic returns long before the group's operands do).
         unsigned tk = 0;
-        if (lane == 0) tk = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int g = (int)__builtin_amdgcn_readfirstlane(tk);
+        draw_ticket(a.ticket, tk);
+        int g = ticket_number(tk);
         while (g < a.ngroups) {
             blane_load<BS, L, K>(a, g, P);
             blane_issue<BS, L, K>(a, P, D, idle);
-            if (lane == 0) tk = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            draw_ticket(a.ticket, tk);
             blane_finish<BS, L, K, MODE>(a, P, D, g, idle);
-            g = (int)__builtin_amdgcn_readfirstlane(tk);
+            g = ticket_number(tk);
         }
     }
 }
 
-__global__ __launch_bounds__(BLK) void blane_fill_sentinel_kernel(double *xs, int64_t n)
-{
-    unsigned long long *p = reinterpret_cast<unsigned long long *>(xs);
-    for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLK) p[i] = BL_SENTINEL;
-}
-
 // ------------------------------------------------------------------ host side
 namespace {
-
-template <typename U>
-int blane_upload(U **dst, const void *src, size_t bytes, size_t *total)
-{
-    *dst = nullptr;
-    const size_t alloc = std::max<size_t>(bytes, 256) + 256;
-    PAMG_HIP(hipMalloc((void **)dst, alloc));
-    if (bytes && src) PAMG_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    if (total) *total += alloc;
-    return PAMG_OK;
-}
 
 // two blocks per lane only for whole-wave block rows
 template <int BS, int MODE>
@@ -369,26 +298,16 @@ int build_blane_part(pamg_matrix_s *A, GsSchedule *g)
     if (!t) return PAMG_E_ALLOC;
     t->L = P.L; t->K = P.K; t->RPW = P.RPW; t->bs = P.bs; t->nlevels = P.nlevels; t->ngroups = P.ngroups; t->nslots = P.nslots;
     t->max_level_groups = P.max_level_groups; t->n_early = P.n_early; t->n_old = P.n_old;
-    int st = blane_upload(&t->d_cols, P.cols.data(), P.cols.size() * sizeof(int), &t->bytes);
-    if (!st) st = blane_upload(&t->d_rid, P.rid.data(), P.rid.size() * sizeof(int), &t->bytes);
-    if (!st) st = blane_upload(&t->d_gate, P.gate.data(), P.gate.size() * sizeof(int), &t->bytes);
-    if (!st) st = blane_upload(&t->d_vals, P.vals.data(), P.vals.size(), &t->bytes);
-    if (!st) st = blane_upload(&t->d_zero, nullptr, 256, &t->bytes);
+    int st = device_upload(&t->d_cols, P.cols.data(), P.cols.size() * sizeof(int), &t->bytes);
+    if (!st) st = device_upload(&t->d_rid, P.rid.data(), P.rid.size() * sizeof(int), &t->bytes);
+    if (!st) st = device_upload(&t->d_gate, P.gate.data(), P.gate.size() * sizeof(int), &t->bytes);
+    if (!st) st = device_upload(&t->d_vals, P.vals.data(), P.vals.size(), &t->bytes);
+    if (!st) st = device_upload(&t->d_zero, nullptr, 256, &t->bytes);
     if (!st) st = (int)hipMemset(t->d_zero, 0, 256);
     if (st) { free_blane_part(t); return st; }
     g->blane = t;
     g->bytes += t->bytes;
     return PAMG_OK;
-}
-
-static int blane_grid_cap(BlaneSched *t, const void *k)
-{
-    if (t->cap > 0 && t->cap_kernel == k) return t->cap;
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess) nb = 2;
-    nb = std::max(1, std::min(nb - 1, 8));                     // the query can over-report by one per CU (MI355X_MICROARCH.md)
-    t->cap = nb; t->cap_kernel = k;
-    return nb;
 }
 
 int blane_launch(pamg_matrix_s *A, GsSchedule *g, const void *Dinv, void *x, const void *b, hipStream_t s)
@@ -409,20 +328,16 @@ int blane_launch(pamg_matrix_s *A, GsSchedule *g, const void *Dinv, void *x, con
         PAMG_HIP(hipMemcpyAsync(g->d_xold, x, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
         a.x = (const double *)g->d_xold;
     }
-    if (A->gs_prof && !t->d_prof) {
-        PAMG_HIP(hipMalloc((void **)&t->d_prof, (size_t)t->ngroups * 4 * sizeof(long long)));
-        PAMG_HIP(hipMemset(t->d_prof, 0, (size_t)t->ngroups * 4 * sizeof(long long)));
-    }
+    if (A->gs_prof) PAMG_TRY(ensure_profile(&t->d_prof, t->ngroups));
     a.prof = A->gs_prof ? t->d_prof : nullptr;
     const int fgrid = (int)std::min<int64_t>(4096, (n + BLK - 1) / BLK);
-    hipLaunchKernelGGL(blane_fill_sentinel_kernel, dim3(fgrid), dim3(BLK), 0, s, (double *)g->d_xs, n);
+    hipLaunchKernelGGL((fill_sentinel_kernel<double>), dim3(fgrid), dim3(BLK), 0, s, (double *)g->d_xs, n);
     PAMG_HIP(hipGetLastError());
     const bool xcd = blane_one_xcd(A, g);
     const void *k = blane_kernel(A->R, t->L, t->K, xcd ? 1 : 0);
     if (!k) return PAMG_E_ARG;
-    static thread_local int cus = 0;
-    if (!cus) cus = device_cus_lane();
-    const int cap = blane_grid_cap(t, k);
+    const int cus = device_cus();
+    const int cap = resident_cap(t->cap, t->cap_kernel, k);
     const int per_level = (int)((t->ngroups + t->nlevels - 1) / std::max(1, t->nlevels));
     // Look-ahead (a wave that runs ahead waits in its poll loop -- on its gate -- with its blocks in registers): three dependency levels where a
     // wave holds several block rows, six with one block row per wave (its blocks are the longer fetch: 18 KB per 6 x 6 row) -- the elasticity
@@ -434,16 +349,7 @@ int blane_launch(pamg_matrix_s *A, GsSchedule *g, const void *Dinv, void *x, con
     if (A->lane_G > 0) G = std::min(A->lane_G, cap * cus);
     G = (int)std::max<int64_t>(1, std::min<int64_t>(G, (t->ngroups + BLANE_WPB - 1) / BLANE_WPB));
     void *args[] = {(void *)&a};
-    if (xcd) {
-        PAMG_HIP(hipMemsetAsync(g->d_sync + 20, 0, 2 * sizeof(unsigned), s));
-        const int Gx = std::max(1, std::min(G, (cus / 8) * cap));
-        t->last_grid = 8 * Gx;
-        PAMG_HIP(hipLaunchKernel(k, dim3(8 * Gx), dim3(BLK), args, 0, s));
-        return PAMG_OK;
-    }
-    t->last_grid = G;
-    PAMG_HIP(hipLaunchKernel(k, dim3(G), dim3(BLK), args, 0, s));
-    return PAMG_OK;
+    return launch_persistent(k, args, G, xcd, g->d_sync + 20, cus, cap, &t->last_grid, s);
 }
 
 // info[0..7] = lanes per block row, blocks per lane, groups, block slots, early blocks, workgroups of the last launch, widest level (groups), bytes
@@ -461,9 +367,7 @@ int blane_profile(const GsSchedule *g, long long *out, int64_t cap, int64_t *n)
 {
     *n = 0;
     if (!g || !g->blane || !g->blane->d_prof) return PAMG_OK;
-    *n = g->blane->ngroups;
-    if (out && cap >= *n) PAMG_HIP(hipMemcpy(out, g->blane->d_prof, (size_t)*n * 4 * sizeof(long long), hipMemcpyDeviceToHost));
-    return PAMG_OK;
+    return read_profile(g->blane->d_prof, g->blane->ngroups, out, cap, n);
 }
 
 }  // namespace pamg

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "pamg_common.h"
+#include "pamg_wave.h"
 
 using namespace pamg;
 
@@ -612,7 +613,7 @@ __global__ __launch_bounds__(256) void bw_read_kernel(const double2 *__restrict_
 template <int U>
 __global__ __launch_bounds__(256) void bw_read_xcd_kernel(const double2 *__restrict__ a, double *__restrict__ c, int64_t n2, int home_wgs)
 {
-    if ((__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) != 0) return;                 // HW_REG_XCC_ID
+    if (xcc_id() != 0) return;
     const int64_t w = blockIdx.x >> 3;                                                   // (round-robin placement: every eighth workgroup is here)
     double s = 0.0;
     for (int64_t base = w * (256 * U) + threadIdx.x; base < n2; base += (int64_t)home_wgs * (256 * U)) {

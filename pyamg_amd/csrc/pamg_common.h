@@ -372,7 +372,6 @@ size_t blane_part_bytes(const GsSchedule *g);
 int blane_launch(pamg_matrix_s *A, GsSchedule *g, const void *Dinv, void *x, const void *b, hipStream_t s);
 int blane_info(const GsSchedule *g, int64_t *info);
 int blane_profile(const GsSchedule *g, long long *out, int64_t cap, int64_t *n);
-int device_cus_lane();
 // pamg_lane.hip: the lane-parallel fast-order sweep
 bool lane_eligible(const pamg_matrix_s *A, const GsSchedule *g);
 int build_lane_part(pamg_matrix_s *A, GsSchedule *g);

@@ -15,6 +15,7 @@
 #pragma once
 #include "pamg_common.h"
 #include "pamg_rowmask_map.h"
+#include "pamg_wave.h"
 
 namespace pamg {
 
@@ -84,20 +85,6 @@ constexpr int EARLY_BIT = (int)0x80000000u;
 // sweeps needs no column ids in LDS and no compare per entry.
 constexpr int DIAG_BIT = 0x40000000;
 constexpr int COL_MASK = 0x3FFFFFFF;
-
-// Sentinel bit patterns of the hand-off buffer xs (a quiet NaN with a payload no arithmetic
-// produces): xs[j] == sentinel  <=>  row j has not published its new value in this sweep yet.
-template <typename T> struct Sentinel;
-template <> struct Sentinel<double> {
-    using bits_t = unsigned long long;
-    static constexpr bits_t value = 0x7FF8DEADBEEF5A5Aull;
-    static __device__ __forceinline__ bits_t bits(double v) { return (bits_t)__double_as_longlong(v); }
-};
-template <> struct Sentinel<float> {
-    using bits_t = unsigned int;
-    static constexpr bits_t value = 0x7FC5BEEFu;
-    static __device__ __forceinline__ bits_t bits(float v) { return __float_as_uint(v); }
-};
 
 // wait for row j's published value: the 8-byte (4-byte) datum IS the flag -- one write-through
 // store by the producer, relaxed agent-scope polling here (MI355X_MICROARCH.md, hand-off "R2")
@@ -1271,7 +1258,7 @@ __device__ __forceinline__ void gran_step(const GranArgs<T> &g, RangePre<T> &cur
         t4 = wall_clock64();
         long long *o = g.prof + (size_t)blk * 8;
         o[0] = t0; o[1] = t0; o[2] = t2; o[3] = t3; o[4] = t4;
-        o[5] = (long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF);
+        o[5] = (long long)xcc_id();
         o[6] = (long long)blockIdx.x;
     }
 }
@@ -1328,10 +1315,7 @@ __global__ __launch_bounds__(BLK) void gs_gran2_kernel(const GranArgs<T> g)
     int blk = (int)blockIdx.x;
     if constexpr (XCD) {
         if (tid == 0) {
-            const unsigned me = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) + 1u;     // HW_REG_XCC_ID[3:0] + 1
-            unsigned home = 0u;
-            __hip_atomic_compare_exchange_strong(g.ticket + 1, &home, me, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const bool mine = home == 0u || home == me;      // home holds the previous value
+            const bool mine = home_xcd_vote(g.ticket + 1);
             sh_next = mine ? (int)__hip_atomic_fetch_add(g.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g.nblk;
         }
         __syncthreads();
@@ -1350,15 +1334,6 @@ __global__ __launch_bounds__(BLK) void gs_gran2_kernel(const GranArgs<T> g)
         gran_step<T, EPI, C>(g, Q, blk, smem_raw, sq);
         blk = gran_next<T, EPI, XCD>(g, blk, P, meta_nxt, &sh_next);
     }
-}
-
-template <typename T>
-__global__ __launch_bounds__(BLK) void fill_sentinel_kernel(T *xs, int64_t n)
-{
-    using B = typename Sentinel<T>::bits_t;
-    B *p = reinterpret_cast<B *>(xs);
-    for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLK)
-        p[i] = Sentinel<T>::value;
 }
 
 // ------------------------------------------------------------------ BLAS-1 and friends

@@ -20,6 +20,8 @@
 // normal-equation hierarchy (10 cycles each, tests and bench legs, ~10^9 slot hand-offs per run) would show and never have.
 #include "pamg_common.h"
 #include "pamg_kz_plan.h"
+#include "pamg_wave.h"
+#include "pamg_sweep_host.h"
 
 namespace pamg {
 
@@ -34,7 +36,8 @@ struct KzLaneSched {
     kz_i4 *d_slots = nullptr;          // [ncols] {value lo, value hi, version, 0}
     unsigned *d_err = nullptr;
     int last_grid = 0;
-    int occ_cap = 0;                   // workgroups per CU the sweep may count on (occupancy query, asked once)
+    int cap = 0;                       // workgroups per CU the sweep may count on (occupancy query, asked once per kernel)
+    const void *cap_kernel = nullptr;
     size_t bytes = 0;
 };
 
@@ -113,42 +116,6 @@ __device__ __forceinline__ void kz_store(kz_i4 *p, kz_i4 q)
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 0" :: "v"(p), "v"(q) : "memory");
 }
 
-template <int CTRL>
-__device__ __forceinline__ double kz_dpp(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);       // (no `old` operand: every lane has a source, the compiler needs no copy)
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-// lane ^ 16 / lane ^ 32 by v_permlane16_swap / v_permlane32_swap (pamg_lane.hip: swap_sum): no LDS path
-template <bool HALF>
-__device__ __forceinline__ double kz_swap_sum(double v)
-{
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    if constexpr (HALF) {
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-    } else {
-        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-    }
-}
-// the butterfly of the Gauss-Seidel lane form (pamg_lane.hip: seg_allreduce), same steps in the same order
-template <int L>
-__device__ __forceinline__ double kz_allreduce(double v)
-{
-    if constexpr (L >= 2) v = v + kz_dpp<0xB1>(v);
-    if constexpr (L >= 4) v = v + kz_dpp<0x4E>(v);
-    if constexpr (L >= 8) v = v + kz_dpp<0x141>(v);
-    if constexpr (L >= 16) v = v + kz_dpp<0x140>(v);
-    if constexpr (L >= 32) v = kz_swap_sum<false>(v);
-    if constexpr (L >= 64) v = kz_swap_sum<true>(v);
-    return v;
-}
-
 template <bool NR, int L, int K>
 __device__ __forceinline__ void kz_group(const KzArgs &a, const KzSet<K> &S, int idle)
 {
@@ -191,7 +158,7 @@ __device__ __forceinline__ void kz_group(const KzArgs &a, const KzSet<K> &S, int
         const double pr = S.a[k] * xv[k];
         s = s + ((S.j[k] & KZL_NONE) ? 0.0 : pr);
     }
-    s = kz_allreduce<L>(s);
+    s = seg_allreduce<L>(s);
     double d;
     if constexpr (NR) d = s * (dinv * a.omega);                       // relaxation.h:963-966
     else d = (bi - s) * dinv * a.omega;                               // relaxation.h:897
@@ -233,17 +200,6 @@ __global__ __launch_bounds__(BLK) void kz_lane_kernel(const KzArgs a)
 
 // ------------------------------------------------------------------ host side
 namespace {
-
-template <typename U>
-int kz_upload(U **dst, const void *src, size_t bytes, size_t *total)
-{
-    *dst = nullptr;
-    const size_t alloc = std::max<size_t>(bytes, 256) + 256;
-    PAMG_HIP(hipMalloc((void **)dst, alloc));
-    if (bytes && src) PAMG_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    if (total) *total += alloc;
-    return PAMG_OK;
-}
 
 template <bool NR, int L>
 const void *kz_kernel_k(int K)
@@ -295,26 +251,18 @@ int build_kz_lane_part(pamg_matrix_s *Lm, LineSchedule *g)
     KzLaneSched *t = new (std::nothrow) KzLaneSched();
     if (!t) return PAMG_E_ALLOC;
     t->L = P.L; t->K = P.K; t->RPW = P.RPW; t->ngroups = P.ngroups; t->nslots = P.nslots; t->nlevels = P.nlevels; t->max_level_groups = P.max_level_groups;
-    int st = kz_upload(&t->d_idx, P.idx.data(), P.idx.size() * sizeof(int), &t->bytes);
-    if (!st) st = kz_upload(&t->d_ver, P.ver.data(), P.ver.size() * sizeof(int), &t->bytes);
-    if (!st) st = kz_upload(&t->d_line, P.line.data(), P.line.size() * sizeof(int), &t->bytes);
-    if (!st) st = kz_upload(&t->d_vals, P.vals.data(), P.vals.size(), &t->bytes);
-    if (!st) st = kz_upload(&t->d_slots, nullptr, (size_t)(Lm->ncols + 16) * sizeof(kz_i4), &t->bytes);
-    if (!st) st = kz_upload(&t->d_err, nullptr, 64, &t->bytes);
+    int st = device_upload(&t->d_idx, P.idx.data(), P.idx.size() * sizeof(int), &t->bytes);
+    if (!st) st = device_upload(&t->d_ver, P.ver.data(), P.ver.size() * sizeof(int), &t->bytes);
+    if (!st) st = device_upload(&t->d_line, P.line.data(), P.line.size() * sizeof(int), &t->bytes);
+    if (!st) st = device_upload(&t->d_vals, P.vals.data(), P.vals.size(), &t->bytes);
+    if (!st) st = device_upload(&t->d_slots, nullptr, (size_t)(Lm->ncols + 16) * sizeof(kz_i4), &t->bytes);
+    if (!st) st = device_upload(&t->d_err, nullptr, 64, &t->bytes);
     if (!st) st = (int)hipMemset(t->d_err, 0, 64);
     if (st) { free_kz_lane_part(t); return st; }
     g->kzl = t;
     g->bytes += t->bytes;
     Lm->bytes += t->bytes;
     return PAMG_OK;
-}
-
-static int kz_cus()
-{
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 64;
-    return p.multiProcessorCount;
 }
 
 int kz_lane_launch(pamg_matrix_s *Lm, LineSchedule *g, bool nr, void *v, const void *b, const void *Dinv, double omega, void *xout, hipStream_t s)
@@ -332,16 +280,9 @@ int kz_lane_launch(pamg_matrix_s *Lm, LineSchedule *g, bool nr, void *v, const v
     PAMG_HIP(hipGetLastError());
     const void *k = nr ? kz_kernel<true>(t->L, t->K) : kz_kernel<false>(t->L, t->K);
     if (!k) return PAMG_E_ARG;
-    static thread_local int cus = 0;
-    if (!cus) cus = kz_cus();
-    // a few dependency levels of look-ahead; every workgroup must be resident: at most 2 per CU, and never more than the occupancy query
-    // allows minus one (asked once per schedule, as the lane / line / block sweeps do)
-    if (t->occ_cap == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess || nb < 1) nb = 1;
-        t->occ_cap = std::max(1, std::min(nb > 1 ? nb - 1 : 1, 2));
-    }
-    const int percu = t->occ_cap;
+    const int cus = device_cus();
+    // a few dependency levels of look-ahead; every workgroup must be resident: at most 2 per CU
+    const int percu = resident_cap(t->cap, t->cap_kernel, k, 2);
     const int per_level = (int)((t->ngroups + t->nlevels - 1) / std::max(1, t->nlevels));
     const int64_t want_waves = std::max<int64_t>(64, (int64_t)4 * per_level);
     int G = (int)std::min<int64_t>((want_waves + KZ_WPB - 1) / KZ_WPB, (int64_t)percu * cus);

@@ -28,30 +28,10 @@
 #include "pamg_lane_plan.h"
 #include "pamg_lanem_plan.h"
 #include "pamg_tile_plan.h"
+#include "pamg_wave.h"
+#include "pamg_sweep_host.h"
 
 namespace pamg {
-
-// Sentinel bit patterns of the hand-off buffer (the ones of the exact sweeps, pamg_kernels.h): xs[j] == sentinel  <=>  row j
-// has not published its new value in this sweep yet.
-template <typename T> struct Sentinel;
-template <> struct Sentinel<double> {
-    using bits_t = unsigned long long;
-    static constexpr bits_t value = 0x7FF8DEADBEEF5A5Aull;
-    static __device__ __forceinline__ bits_t bits(double v) { return (bits_t)__double_as_longlong(v); }
-};
-template <> struct Sentinel<float> {
-    using bits_t = unsigned int;
-    static constexpr bits_t value = 0x7FC5BEEFu;
-    static __device__ __forceinline__ bits_t bits(float v) { return __float_as_uint(v); }
-};
-
-template <typename T>
-__global__ __launch_bounds__(BLK) void lane_fill_sentinel_kernel(T *xs, int64_t n)
-{
-    using B = typename Sentinel<T>::bits_t;
-    B *p = reinterpret_cast<B *>(xs);
-    for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLK) p[i] = Sentinel<T>::value;
-}
 
 // per slot row (group g, row r of the group): original row | NODIAG, the group's gate operand, 1 / a_ii -- ONE 16-byte request
 struct alignas(16) LaneRec { int rid; int gate; int rd_lo; int rd_hi; };
@@ -96,63 +76,6 @@ struct LaneSet {
     T rd;
     int gate;
 };
-
-// ---- sum over the L lanes that share a row; every lane ends up with the total (bit for bit the same total: an XOR butterfly
-//      adds the same two values in both lanes of a pair at every step)
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);       // (no `old` operand: every lane has a source, the compiler needs no copy)
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-// lane ^ 16 and lane ^ 32 without the LDS path (round 5; ds_swizzle + ds_bpermute before): v_permlane16_swap / v_permlane32_swap (CDNA4) exchange
-// the odd 16-lane rows (the upper half) of one copy with the even rows (the lower half) of the other; afterwards one copy holds the even-row
-// (lower-half) values everywhere, the other the odd-row (upper-half) ones, and their sum is the butterfly step
-template <bool HALF>
-__device__ __forceinline__ double swap_sum(double v)
-{
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    if constexpr (HALF) {
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-    } else {
-        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-    }
-}
-template <bool HALF>
-__device__ __forceinline__ float swap_sum(float v)
-{
-    const int w = __float_as_int(v);
-    if constexpr (HALF) {
-        const auto a = __builtin_amdgcn_permlane32_swap(w, w, false, false);
-        return __int_as_float(a[0]) + __int_as_float(a[1]);
-    } else {
-        const auto a = __builtin_amdgcn_permlane16_swap(w, w, false, false);
-        return __int_as_float(a[0]) + __int_as_float(a[1]);
-    }
-}
-
-template <int L, typename T>
-__device__ __forceinline__ T seg_allreduce(T v)
-{
-    v = v + dpp_mov<0xB1>(v);                                   // quad_perm [1,0,3,2]: lane ^ 1
-    v = v + dpp_mov<0x4E>(v);                                   // quad_perm [2,3,0,1]: lane ^ 2
-    if constexpr (L >= 8) v = v + dpp_mov<0x141>(v);            // row_half_mirror: the other quad of the 8
-    if constexpr (L >= 16) v = v + dpp_mov<0x140>(v);           // row_mirror: the other half of the 16
-    if constexpr (L >= 32) v = swap_sum<false>(v);              // lane ^ 16
-    if constexpr (L >= 64) v = swap_sum<true>(v);               // lane ^ 32
-    return v;
-}
 
 template <typename T> __device__ __forceinline__ T rec_rd(const int4 &q);
 template <> __device__ __forceinline__ double rec_rd<double>(const int4 &q) { return __hiloint2double(q.w, q.z); }
@@ -277,11 +200,7 @@ __device__ __forceinline__ void lane_finish(const LaneArgs<T> &a, const LaneSet<
     }
     s = seg_allreduce<L, T>(s);
     if (head && S.rid >= 0) lane_publish<T, EPI, MODE>(a, S.rid, s, D.bv, S.rd, D.xo);
-    if (a.prof && lane == 0) {
-        long long *o = a.prof + (size_t)g * 4;
-        o[0] = D.t0; o[1] = t1; o[2] = wall_clock64();
-        o[3] = (long long)((__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) | (blockIdx.x << 4));
-    }
+    if (a.prof && lane == 0) profile_stamp(a.prof + (size_t)g * 4, D.t0, t1);
 }
 
 constexpr int LANE_WPB = BLK / 64;            // waves per workgroup (they never meet)
@@ -289,7 +208,6 @@ constexpr int LANE_WPB = BLK / 64;            // waves per workgroup (they never
 template <typename T, int EPI, int L, int K, int MODE>
 __global__ __launch_bounds__(BLK) void gs_lane_kernel(const LaneArgs<T> a)
 {
-    const int lane = threadIdx.x & 63;
     const int wib = threadIdx.x >> 6;
     const int idle = (int)((((unsigned)blockIdx.x * LANE_WPB + (unsigned)wib) * 16u) % (unsigned)a.nidle);
     LaneSet<T, K> P, Q;
@@ -308,42 +226,34 @@ __global__ __launch_bounds__(BLK) void gs_lane_kernel(const LaneArgs<T> a)
             lane_finish<T, EPI, L, K, MODE>(a, P, D, g, idle);
         }
     } else {
-        __shared__ int sh_home;
-        if (threadIdx.x == 0) {
-            const unsigned me = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) + 1u;     // HW_REG_XCC_ID[3:0] + 1
-            unsigned home = 0u;
-            __hip_atomic_compare_exchange_strong(a.ticket + 1, &home, me, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            sh_home = (home == 0u || home == me) ? 1 : 0;      // home holds the previous value
-        }
-        __syncthreads();
-        if (!sh_home) return;
-        // tickets: lane 0 draws, the wave reads lane 0's register; two tickets are always ahead of the running group
+        if (!claim_home_xcd(a.ticket + 1)) return;
+        // two tickets are always ahead of the running group
         unsigned tk = 0;
-        if (lane == 0) tk = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int g = (int)__builtin_amdgcn_readfirstlane(tk);
+        draw_ticket(a.ticket, tk);
+        int g = ticket_number(tk);
         if (g >= a.ngroups) return;
         lane_load<T, L, K>(a, g, P);
-        if (lane == 0) tk = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int g2 = (int)__builtin_amdgcn_readfirstlane(tk);
+        draw_ticket(a.ticket, tk);
+        int g2 = ticket_number(tk);
         while (true) {
             unsigned tk3 = 0;
             lane_issue<T, EPI, K>(a, P, D, idle);
             if (g2 < a.ngroups) {
                 lane_load<T, L, K>(a, g2, Q);
-                if (lane == 0) tk3 = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                draw_ticket(a.ticket, tk3);
             }
             lane_finish<T, EPI, L, K, MODE>(a, P, D, g, idle);
             if (g2 >= a.ngroups) break;
-            g = (int)__builtin_amdgcn_readfirstlane(tk3);
+            g = ticket_number(tk3);
             unsigned tk4 = 0;
             lane_issue<T, EPI, K>(a, Q, D, idle);
             if (g < a.ngroups) {
                 lane_load<T, L, K>(a, g, P);
-                if (lane == 0) tk4 = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                draw_ticket(a.ticket, tk4);
             }
             lane_finish<T, EPI, L, K, MODE>(a, Q, D, g2, idle);
             if (g >= a.ngroups) break;
-            g2 = (int)__builtin_amdgcn_readfirstlane(tk4);
+            g2 = ticket_number(tk4);
         }
     }
 }
@@ -803,35 +713,27 @@ __global__ __launch_bounds__(BLK) void gs_lanem_kernel(const LaneMArgs a)
             q0 = n0; q1 = n1;
         }
     } else {
-        __shared__ int sh_home;
-        if (threadIdx.x == 0) {
-            const unsigned me = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) + 1u;
-            unsigned home = 0u;
-            __hip_atomic_compare_exchange_strong(a.ticket + 1, &home, me, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            sh_home = (home == 0u || home == me) ? 1 : 0;
-        }
-        __syncthreads();
-        if (!sh_home) return;
+        if (!claim_home_xcd(a.ticket + 1)) return;
         unsigned tk = 0;
-        if (lane == 0) tk = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int g = (int)__builtin_amdgcn_readfirstlane(tk);
+        draw_ticket(a.ticket, tk);
+        int g = ticket_number(tk);
         if (g >= gend) return;
-        if (lane == 0) tk = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int g2 = (int)__builtin_amdgcn_readfirstlane(tk);
+        draw_ticket(a.ticket, tk);
+        int g2 = ticket_number(tk);
         int4 q0, q1;
         m_rec(rp, g, gend, q0, q1);
         while (true) {
             int4 n0, n1;
             m_rec(rp, g2, gend, n0, n1);
             unsigned tk3 = 0;
-            if (g2 < gend && lane == 0) tk3 = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            draw_ticket(a.ticket, tk3, g2 < gend);
             m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
             m_gather<NREG>(a, X, idle);
             const double val = m_finish<RPW, NREG>(a, X, idle);
             m_publish<RPW, MODE, NREG, 0, Z == 1, Z == 2>(a, X, val);
             if (g2 >= gend) break;
             g = g2; q0 = n0; q1 = n1;
-            g2 = (int)__builtin_amdgcn_readfirstlane(tk3);
+            g2 = ticket_number(tk3);
         }
     }
     }
@@ -922,18 +824,18 @@ __device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, in
         }
     } else {
         unsigned tk = 0;
-        if (lane == 0) tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int g = (int)__builtin_amdgcn_readfirstlane(tk);
+        draw_ticket(ticket, tk);
+        int g = ticket_number(tk);
         if (g >= gend) return 0;
-        if (lane == 0) tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int g2 = (int)__builtin_amdgcn_readfirstlane(tk);
+        draw_ticket(ticket, tk);
+        int g2 = ticket_number(tk);
         int4 q0, q1;
         m_rec(rp, g, gend, q0, q1);
         while (true) {
             int4 n0, n1;
             m_rec(rp, g2, gend, n0, n1);
             unsigned tk3 = 0;
-            if (g2 < gend && lane == 0) tk3 = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            draw_ticket(ticket, tk3, g2 < gend);
             m_slots<RPW, NREG>(a, X, q0, q1, g, lane);
             m_gather<NREG, Z && PH == 2, Z == 2 && PH == 1>(a, X, idle, xz, PH == 2);
             const double val = m_finish<RPW, NREG>(a, X, idle, nullptr, nullptr, xz);
@@ -942,7 +844,7 @@ __device__ __forceinline__ unsigned m_phase(const LaneMArgs &a, double *wipe, in
             ++done;
             if (g2 >= gend) break;
             g = g2; q0 = n0; q1 = n1;
-            g2 = (int)__builtin_amdgcn_readfirstlane(tk3);
+            g2 = ticket_number(tk3);
         }
     }
     }
@@ -1001,12 +903,7 @@ __global__ __launch_bounds__(BLK) void gs_lanem_sym_kernel(const LaneMSymArgs a)
     if (threadIdx.x == 0) {
         sh_done = 0u;
         sh_home = 1;
-        if constexpr (MODE == 1) {
-            const unsigned me = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF) + 1u;
-            unsigned home = 0u;
-            __hip_atomic_compare_exchange_strong(a.sync + 4, &home, me, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            sh_home = (home == 0u || home == me) ? 1 : 0;
-        }
+        if constexpr (MODE == 1) sh_home = home_xcd_vote(a.sync + 4) ? 1 : 0;     // (the vote alone: this barrier is shared with sh_done)
     }
     __syncthreads();
     if (sh_home) {                                               // (uniform per workgroup: the barriers below are met by all of its waves or by none)
@@ -1023,17 +920,6 @@ __global__ __launch_bounds__(BLK) void gs_lanem_sym_kernel(const LaneMSymArgs a)
 
 // ------------------------------------------------------------------ host side
 namespace {
-
-template <typename U>
-int lane_upload(U **dst, const void *src, size_t bytes, size_t *total)
-{
-    *dst = nullptr;
-    const size_t alloc = std::max<size_t>(bytes, 256) + 256;   // slack: nothing reads past the end, but keep allocations non-empty
-    PAMG_HIP(hipMalloc((void **)dst, alloc));
-    if (bytes && src) PAMG_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));      // src = nullptr: allocation only (filled on the device)
-    if (total) *total += alloc;
-    return PAMG_OK;
-}
 
 template <typename T, int EPI, int L, int MODE>
 const void *lane_kernel_k(int K)
@@ -1189,16 +1075,16 @@ int build_lane_part(pamg_matrix_s *A, GsSchedule *g)
             rec[q].rd_lo = rec[q].rd_hi = 0;
             std::memcpy(&rec[q].rd_lo, &P.rdiag[q * (size_t)ts], (size_t)ts);
         }
-        st = lane_upload(&t->d_rec, rec.data(), nrec * sizeof(LaneRec), &t->bytes);
-        if (!st) st = lane_upload(&t->d_cols, P.cols.data(), P.cols.size() * sizeof(int), &t->bytes);
-        if (!st) st = lane_upload(&t->d_vals, P.vals.data(), P.vals.size(), &t->bytes);
+        st = device_upload(&t->d_rec, rec.data(), nrec * sizeof(LaneRec), &t->bytes);
+        if (!st) st = device_upload(&t->d_cols, P.cols.data(), P.cols.size() * sizeof(int), &t->bytes);
+        if (!st) st = device_upload(&t->d_vals, P.vals.data(), P.vals.size(), &t->bytes);
     } else {
         int *d_rid = nullptr, *d_gate = nullptr;
-        st = lane_upload(&d_rid, P.rid.data(), P.rid.size() * sizeof(int), nullptr);
-        if (!st) st = lane_upload(&d_gate, P.gate.data(), P.gate.size() * sizeof(int), nullptr);
-        if (!st) st = lane_upload(&t->d_rec, nullptr, nrec * sizeof(LaneRec), &t->bytes);
-        if (!st) st = lane_upload(&t->d_cols, nullptr, (size_t)P.n_slots * sizeof(int), &t->bytes);
-        if (!st) st = lane_upload(&t->d_vals, nullptr, (size_t)P.n_slots * ts, &t->bytes);
+        st = device_upload(&d_rid, P.rid.data(), P.rid.size() * sizeof(int), nullptr);
+        if (!st) st = device_upload(&d_gate, P.gate.data(), P.gate.size() * sizeof(int), nullptr);
+        if (!st) st = device_upload(&t->d_rec, nullptr, nrec * sizeof(LaneRec), &t->bytes);
+        if (!st) st = device_upload(&t->d_cols, nullptr, (size_t)P.n_slots * sizeof(int), &t->bytes);
+        if (!st) st = device_upload(&t->d_vals, nullptr, (size_t)P.n_slots * ts, &t->bytes);
         if (!st) {
             const unsigned grid = (unsigned)((P.ngroups + 3) / 4);
             (void)hipGetLastError();                                  // a stale error of an earlier query must not be taken for this launch's
@@ -1317,12 +1203,12 @@ static int lanem_to_device(const LaneMPlan &P, int s_max, LaneMSched **out)
                 crec[(size_t)q] = make_int4(P.gate[(size_t)q], P.c_uunit[(size_t)q], P.c_sunit[(size_t)q],
                                             (int)P.c_KU[(size_t)q] | ((int)P.c_KS[(size_t)q] << 8) | ((int)P.c_rows[(size_t)q] << 16));
         });
-        int st = lane_upload(&t->d_crec, crec.data(), crec.size() * sizeof(int4), &t->bytes);
-        if (!st) st = lane_upload(&t->d_cols, P.ucodes.data(), P.ucodes.size() * sizeof(int), &t->bytes);
-        if (!st) st = lane_upload(&t->d_vals, P.svals.data(), P.svals.size() * sizeof(double), &t->bytes);
-        if (!st) st = lane_upload(&t->d_sidx, P.sidx.data(), P.sidx.size() * sizeof(unsigned short), &t->bytes);
-        if (!st) st = lane_upload(&t->d_crid, P.rid.data(), P.rid.size() * sizeof(int), &t->bytes);
-        if (!st) st = lane_upload(&t->d_crd, P.rdiag.data(), P.rdiag.size() * sizeof(double), &t->bytes);
+        int st = device_upload(&t->d_crec, crec.data(), crec.size() * sizeof(int4), &t->bytes);
+        if (!st) st = device_upload(&t->d_cols, P.ucodes.data(), P.ucodes.size() * sizeof(int), &t->bytes);
+        if (!st) st = device_upload(&t->d_vals, P.svals.data(), P.svals.size() * sizeof(double), &t->bytes);
+        if (!st) st = device_upload(&t->d_sidx, P.sidx.data(), P.sidx.size() * sizeof(unsigned short), &t->bytes);
+        if (!st) st = device_upload(&t->d_crid, P.rid.data(), P.rid.size() * sizeof(int), &t->bytes);
+        if (!st) st = device_upload(&t->d_crd, P.rdiag.data(), P.rdiag.size() * sizeof(double), &t->bytes);
         if (st) { free_lanem_part(t); return st; }
         if (getenv("PAMG_TIMING")) fprintf(stderr, "[pamg timing]     lanem plan: cluster layout, %d rows per wave: %zu bytes uploaded\n", P.cluster, t->bytes);
         *out = t;
@@ -1341,9 +1227,9 @@ static int lanem_to_device(const LaneMPlan &P, int s_max, LaneMSched **out)
             std::memcpy(&R.rdb_lo, P.rpw == 2 ? &P.rdiag[q0 + 1] : &zero, 8);
         }
     });
-    int st = lane_upload(&t->d_rec, rec.data(), rec.size() * sizeof(LaneMRec), &t->bytes);
-    if (!st) st = lane_upload(&t->d_cols, P.cols.data(), P.cols.size() * sizeof(int), &t->bytes);
-    if (!st) st = lane_upload(&t->d_vals, P.vals.data(), P.vals.size() * sizeof(double), &t->bytes);
+    int st = device_upload(&t->d_rec, rec.data(), rec.size() * sizeof(LaneMRec), &t->bytes);
+    if (!st) st = device_upload(&t->d_cols, P.cols.data(), P.cols.size() * sizeof(int), &t->bytes);
+    if (!st) st = device_upload(&t->d_vals, P.vals.data(), P.vals.size() * sizeof(double), &t->bytes);
     if (st) { free_lanem_part(t); return st; }
     if (getenv("PAMG_TIMING")) fprintf(stderr, "[pamg timing]     lanem plan: %d row(s) per wave: %zu bytes uploaded\n", P.rpw, t->bytes);
     *out = t;
@@ -1450,6 +1336,55 @@ static void lanem_layout_args(const LaneMSched *t, LaneMArgs &a)
     a.sidx = t->d_sidx; a.crid = t->d_crid; a.crd = t->d_crd; a.crows = t->cluster;
 }
 
+// the instantiation of a layout: the cluster layout (static form only), two rows per wave with four units in registers, one row per wave with
+// every unit (all_regs) or two in registers; xcd: the ticket form inside one XCD.  Z as in the kernels
+template <int Z>
+static const void *lanem_kernel(int cluster, int rpw, bool all_regs, bool xcd)
+{
+    if (cluster) return (const void *)gs_lanem_kernel<0, 0, 8, Z>;
+    if (rpw == 2) return xcd ? (const void *)gs_lanem_kernel<1, 2, 4, Z> : (const void *)gs_lanem_kernel<0, 2, 4, Z>;
+    if (all_regs) return xcd ? (const void *)gs_lanem_kernel<1, 1, 8, Z> : (const void *)gs_lanem_kernel<0, 1, 8, Z>;
+    return xcd ? (const void *)gs_lanem_kernel<1, 1, 2, Z> : (const void *)gs_lanem_kernel<0, 1, 2, Z>;
+}
+template <int Z>
+static const void *lanem_sym_kernel(int cluster, int rpw, bool all_regs, bool xcd)
+{
+    if (cluster) return (const void *)gs_lanem_sym_kernel<0, 0, 8, Z>;
+    if (rpw == 2) return xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4, Z> : (const void *)gs_lanem_sym_kernel<0, 2, 4, Z>;
+    if (all_regs) return xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 8, Z> : (const void *)gs_lanem_sym_kernel<0, 1, 8, Z>;
+    return xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 2, Z> : (const void *)gs_lanem_sym_kernel<0, 1, 2, Z>;
+}
+
+// every unit of a row in registers: one-row-per-wave plans of the small levels (PAMG_LANEM_NREG, A/B: 2 / 8 units whatever the level)
+static bool lanem_all_regs(const pamg_matrix_s *A, const LaneMSched *t)
+{
+    static const int nreg_env = [] { const char *e = getenv("PAMG_LANEM_NREG"); return e ? atoi(e) : 0; }();
+    return t->rpw == 1 && (nreg_env ? nreg_env == 8 : A->nrows <= 131072);
+}
+
+// the ticket form inside one XCD only for tiny levels: one row per group means one ticket per ROW, and the ticket counter is one address whose
+// atomics serialise (11.4 ns each) -- level 2 of the 256^3 hierarchy (44.6 K rows): 0.58 ms inside one XCD, 0.48 across the chip
+// (the cluster layout: static form only)
+static bool lanem_one_xcd(const pamg_matrix_s *A, const GsSchedule *g, const LaneMSched *t)
+{
+    return !t->cluster && (A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= 8192));
+}
+
+// workgroups a plan wants, given `cap` co-resident ones per CU on `cus` CUs
+static int lanem_want_grid(const pamg_matrix_s *A, const LaneMSched *t, int cap, int cus)
+{
+    // waves wanted: 4 x the rows of an average super-level (level 2 of the 256^3 hierarchy, 199 rows per super-level at s = 6: 0.487 ms with 115
+    // workgroups, 0.459 with 192, 0.473 with 256, 0.52 with 384), capped below
+    const int per_level = (int)((t->ngroups + t->nsuper - 1) / std::max(1, t->nsuper));
+    const int64_t want_waves = std::max<int64_t>(128, ((int64_t)A->lanem_ahead10 * per_level + 9) / 10);
+    // three workgroups per CU at most: from 768 workgroups on the sweep delivers what it delivers, more waves only slow each other down
+    // (level 1 of the 256^3 hierarchy, s = 3: 1.76 ms with 768 workgroups, 1.88 with 1 024, 2.17 with 1 536, 2.33 with 1 792)
+    // (two rows per wave, s = 3: 1.74 ms with 512 workgroups, 1.89 with 768, 2.08 with 1 024: two per CU)
+    int G = (int)std::min<int64_t>((want_waves + LANE_WPB - 1) / LANE_WPB, (int64_t)std::min(cap, (t->rpw == 2 || t->cluster) ? 2 : 3) * cus);
+    if (A->lane_G > 0) G = std::min(A->lane_G, cap * cus);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(G, (t->ngroups + LANE_WPB - 1) / LANE_WPB));
+}
+
 // t: the schedule's own plan, or a zero-iterate plan of the operator run on the schedule's buffers (w: where Zf stores its numerators)
 // acc: the backward half of the correction form -- the schedule's snapshot already holds the forward half's values (the caller swept into it), so
 // only the hand-off buffer is prepared, and the kernel adds its values to x
@@ -1465,65 +1400,22 @@ static int lanem_launch_plan(pamg_matrix_s *A, GsSchedule *g, LaneMSched *t, voi
     a.err = g->d_sync + 1; a.ticket = g->d_sync + 20;
     a.ngroups = (int)t->ngroups;
     a.nidle = (int)std::max<int64_t>(1, std::min<int64_t>(n, 1 << 20));
-    if (A->gs_prof && !t->d_prof && !t->cluster) {
-        PAMG_HIP(hipMalloc((void **)&t->d_prof, (size_t)t->ngroups * 4 * sizeof(long long)));
-        PAMG_HIP(hipMemset(t->d_prof, 0, (size_t)t->ngroups * 4 * sizeof(long long)));
-    }
+    if (A->gs_prof && !t->cluster) PAMG_TRY(ensure_profile(&t->d_prof, t->ngroups));
     a.prof = (A->gs_prof && !t->cluster) ? t->d_prof : nullptr;
     const int fgrid = (int)std::min<int64_t>(4096, (n + BLK - 1) / BLK);
-    if (acc) hipLaunchKernelGGL((lane_fill_sentinel_kernel<double>), dim3(fgrid), dim3(BLK), 0, s, (double *)g->d_xs, n);
+    if (acc) hipLaunchKernelGGL((fill_sentinel_kernel<double>), dim3(fgrid), dim3(BLK), 0, s, (double *)g->d_xs, n);
     else hipLaunchKernelGGL(lanem_prepare_kernel, dim3(fgrid), dim3(BLK), 0, s, (const double *)x, (double *)g->d_xold, (double *)g->d_xs, n);
     PAMG_HIP(hipGetLastError());
-    // the ticket form inside one XCD only for tiny levels: one row per group means one ticket per ROW, and the ticket counter is one address whose
-    // atomics serialise (11.4 ns each) -- level 2 of the 256^3 hierarchy (44.6 K rows): 0.58 ms inside one XCD, 0.48 across the chip
-    const bool xcd = !t->cluster && (A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= 8192));      // (the cluster layout: static form only)
-    static const int nreg_env = [] { const char *e = getenv("PAMG_LANEM_NREG"); return e ? atoi(e) : 0; }();     // A/B: 2 / 8 units in registers on one-row-per-wave levels
-    const bool all_regs = t->rpw == 1 && (nreg_env ? nreg_env == 8 : A->nrows <= 131072);
-    const void *k = t->cluster  ? (const void *)gs_lanem_kernel<0, 0, 8>
-                  : t->rpw == 2 ? (xcd ? (const void *)gs_lanem_kernel<1, 2, 4> : (const void *)gs_lanem_kernel<0, 2, 4>)
-                  : all_regs    ? (xcd ? (const void *)gs_lanem_kernel<1, 1, 8> : (const void *)gs_lanem_kernel<0, 1, 8>)
-                                : (xcd ? (const void *)gs_lanem_kernel<1, 1, 2> : (const void *)gs_lanem_kernel<0, 1, 2>);
-    if (w)
-        k = t->cluster  ? (const void *)gs_lanem_kernel<0, 0, 8, 1>
-          : t->rpw == 2 ? (xcd ? (const void *)gs_lanem_kernel<1, 2, 4, 1> : (const void *)gs_lanem_kernel<0, 2, 4, 1>)
-          : all_regs    ? (xcd ? (const void *)gs_lanem_kernel<1, 1, 8, 1> : (const void *)gs_lanem_kernel<0, 1, 8, 1>)
-                        : (xcd ? (const void *)gs_lanem_kernel<1, 1, 2, 1> : (const void *)gs_lanem_kernel<0, 1, 2, 1>);
-    if (acc)
-        k = t->cluster  ? (const void *)gs_lanem_kernel<0, 0, 8, 2>
-          : t->rpw == 2 ? (xcd ? (const void *)gs_lanem_kernel<1, 2, 4, 2> : (const void *)gs_lanem_kernel<0, 2, 4, 2>)
-          : all_regs    ? (xcd ? (const void *)gs_lanem_kernel<1, 1, 8, 2> : (const void *)gs_lanem_kernel<0, 1, 8, 2>)
-                        : (xcd ? (const void *)gs_lanem_kernel<1, 1, 2, 2> : (const void *)gs_lanem_kernel<0, 1, 2, 2>);
-    static thread_local int cus = 0;
-    if (!cus) cus = device_cus_lane();
-    if (!(t->cap > 0 && t->cap_kernel == k)) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess) nb = 2;
-        t->cap = std::max(1, std::min(nb - 1, 8));
-        t->cap_kernel = k;
-    }
-    const int cap = t->cap;
-    // waves wanted: 4 x the rows of an average super-level (level 2 of the 256^3 hierarchy, 199 rows per super-level at s = 6: 0.487 ms with 115
-    // workgroups, 0.459 with 192, 0.473 with 256, 0.52 with 384), capped below
-    const int per_level = (int)((t->ngroups + t->nsuper - 1) / std::max(1, t->nsuper));
-    const int64_t want_waves = std::max<int64_t>(128, ((int64_t)A->lanem_ahead10 * per_level + 9) / 10);
-    const int cwpb = LANE_WPB;
-    // three workgroups per CU at most: from 768 workgroups on the sweep delivers what it delivers, more waves only slow each other down
-    // (level 1 of the 256^3 hierarchy, s = 3: 1.76 ms with 768 workgroups, 1.88 with 1 024, 2.17 with 1 536, 2.33 with 1 792)
-    // (two rows per wave, s = 3: 1.74 ms with 512 workgroups, 1.89 with 768, 2.08 with 1 024: two per CU)
-    int G = (int)std::min<int64_t>((want_waves + cwpb - 1) / cwpb, (int64_t)std::min(cap, (t->rpw == 2 || t->cluster) ? 2 : 3) * cus);
-    if (A->lane_G > 0) G = std::min(A->lane_G, cap * cus);
-    G = (int)std::max<int64_t>(1, std::min<int64_t>(G, (t->ngroups + cwpb - 1) / cwpb));
+    const bool xcd = lanem_one_xcd(A, g, t);
+    const bool all_regs = lanem_all_regs(A, t);
+    const int Z = acc ? 2 : w ? 1 : 0;
+    const void *k = Z == 0 ? lanem_kernel<0>(t->cluster, t->rpw, all_regs, xcd)
+                  : Z == 1 ? lanem_kernel<1>(t->cluster, t->rpw, all_regs, xcd)
+                           : lanem_kernel<2>(t->cluster, t->rpw, all_regs, xcd);
+    const int cus = device_cus();
+    const int cap = resident_cap(t->cap, t->cap_kernel, k);
     void *args[] = {(void *)&a};
-    if (xcd) {
-        PAMG_HIP(hipMemsetAsync(g->d_sync + 20, 0, 2 * sizeof(unsigned), s));
-        const int Gx = std::max(1, std::min(G, (cus / 8) * cap));
-        t->last_grid = 8 * Gx;
-        PAMG_HIP(hipLaunchKernel(k, dim3(8 * Gx), dim3(BLK), args, 0, s));
-        return PAMG_OK;
-    }
-    t->last_grid = G;
-    PAMG_HIP(hipLaunchKernel(k, dim3(G), dim3(BLK), args, 0, s));
-    return PAMG_OK;
+    return launch_persistent(k, args, lanem_want_grid(A, t, cap, cus), xcd, g->d_sync + 20, cus, cap, &t->last_grid, s);
 }
 
 int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStream_t s) { return lanem_launch_plan(A, g, g->lanem, x, b, nullptr, s); }
@@ -1552,14 +1444,14 @@ int sym_fill_sentinels(void *p, int64_t n)
 {
     if (n <= 0) return PAMG_OK;
     const int fgrid = (int)std::min<int64_t>(4096, (n + BLK - 1) / BLK);
-    hipLaunchKernelGGL((lane_fill_sentinel_kernel<double>), dim3(fgrid), dim3(BLK), 0, 0, (double *)p, n);
+    hipLaunchKernelGGL((fill_sentinel_kernel<double>), dim3(fgrid), dim3(BLK), 0, 0, (double *)p, n);
     PAMG_HIP(hipGetLastError());
     PAMG_HIP(hipDeviceSynchronize());
     return PAMG_OK;
 }
 
 // The fused symmetric sweep (gs_lanem_sym_kernel).  PAMG_E_UNSUPPORTED: the two schedules would not run the same kernel -- the caller sweeps
-// them one after the other.  The grid is the larger of the two directional wishes (lanem_launch) under the fused kernel's own co-residency cap.
+// them one after the other.  The grid is the larger of the two directional wishes (lanem_want_grid) under the fused kernel's own co-residency cap.
 // acc: the correction form, x += sweep(0, b), on the zero-iterate plans (PAMG_E_UNSUPPORTED without them): the launch announced from zero whose second
 // phase adds to x
 int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, bool x_zero, hipStream_t s, bool acc)
@@ -1572,9 +1464,8 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
     const bool zero = x_zero && zero_plans_ready(A, gf, gb);
     if (zero) { tf = A->zplan[0]; tb = A->zplan[1]; }
     const int64_t n = A->nrows;
-    auto one_xcd = [&](const GsSchedule *g) { return !g->lanem->cluster && (A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= 8192)); };
-    const bool xcd = one_xcd(gf);
-    if (xcd != one_xcd(gb) || tf->rpw != tb->rpw || tf->cluster != tb->cluster || tf->ngroups < 1 || tb->ngroups < 1) return PAMG_E_UNSUPPORTED;
+    const bool xcd = lanem_one_xcd(A, gf, gf->lanem);
+    if (xcd != lanem_one_xcd(A, gb, gb->lanem) || tf->rpw != tb->rpw || tf->cluster != tb->cluster || tf->ngroups < 1 || tb->ngroups < 1) return PAMG_E_UNSUPPORTED;
     LaneMSymArgs a;
     LaneMSched *ts2[2] = {tf, tb};
     for (int p = 0; p < 2; ++p) {
@@ -1598,43 +1489,17 @@ int lanem_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, 
     a.hf[0] = (double *)A->d_sym_hf[0]; a.hf[1] = (double *)A->d_sym_hf[1];
     a.sync = A->d_sym_sync;
     a.xzero = x_zero ? 1 : 0;
-    static const int nreg_env = [] { const char *e = getenv("PAMG_LANEM_NREG"); return e ? atoi(e) : 0; }();
-    const bool all_regs = tf->rpw == 1 && (nreg_env ? nreg_env == 8 : A->nrows <= 131072);
-    const void *k = tf->cluster  ? (const void *)gs_lanem_sym_kernel<0, 0, 8>
-                  : tf->rpw == 2 ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4> : (const void *)gs_lanem_sym_kernel<0, 2, 4>)
-                  : all_regs     ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 8> : (const void *)gs_lanem_sym_kernel<0, 1, 8>)
-                                 : (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 2> : (const void *)gs_lanem_sym_kernel<0, 1, 2>);
-    if (zero)
-        k = tf->cluster  ? (const void *)gs_lanem_sym_kernel<0, 0, 8, 1>
-          : tf->rpw == 2 ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4, 1> : (const void *)gs_lanem_sym_kernel<0, 2, 4, 1>)
-          : all_regs     ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 8, 1> : (const void *)gs_lanem_sym_kernel<0, 1, 8, 1>)
-                         : (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 2, 1> : (const void *)gs_lanem_sym_kernel<0, 1, 2, 1>);
-    if (acc)
-        k = tf->cluster  ? (const void *)gs_lanem_sym_kernel<0, 0, 8, 2>
-          : tf->rpw == 2 ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 2, 4, 2> : (const void *)gs_lanem_sym_kernel<0, 2, 4, 2>)
-          : all_regs     ? (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 8, 2> : (const void *)gs_lanem_sym_kernel<0, 1, 8, 2>)
-                         : (xcd ? (const void *)gs_lanem_sym_kernel<1, 1, 2, 2> : (const void *)gs_lanem_sym_kernel<0, 1, 2, 2>);
-    static thread_local int cus = 0;
-    if (!cus) cus = device_cus_lane();
-    int &kcap = acc ? A->csym_cap : zero ? A->zsym_cap : A->sym_cap;      // (the kernels alternate within a cycle: one cached answer each)
-    const void *&kcap_kernel = acc ? A->csym_cap_kernel : zero ? A->zsym_cap_kernel : A->sym_cap_kernel;
-    if (!(kcap > 0 && kcap_kernel == k)) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess) nb = 2;
-        kcap = std::max(1, std::min(nb - 1, 8));                // every workgroup must be resident (the query can over-report by one)
-        kcap_kernel = k;
-    }
-    const int cap = kcap;
-    int G = 1;
-    for (int p = 0; p < 2; ++p) {                               // the directional rule (lanem_launch), the larger wish of the two
-        const LaneMSched *t = ts2[p];
-        const int per_level = (int)((t->ngroups + t->nsuper - 1) / std::max(1, t->nsuper));
-        const int64_t want_waves = std::max<int64_t>(128, ((int64_t)A->lanem_ahead10 * per_level + 9) / 10);
-        int Gp = (int)std::min<int64_t>((want_waves + LANE_WPB - 1) / LANE_WPB, (int64_t)std::min(cap, (t->rpw == 2 || t->cluster) ? 2 : 3) * cus);
-        if (A->lane_G > 0) Gp = std::min(A->lane_G, cap * cus);
-        Gp = (int)std::max<int64_t>(1, std::min<int64_t>(Gp, (t->ngroups + LANE_WPB - 1) / LANE_WPB));
-        G = std::max(G, Gp);
-    }
+    const bool all_regs = lanem_all_regs(A, tf);
+    const int Z = acc ? 2 : zero ? 1 : 0;
+    const void *k = Z == 0 ? lanem_sym_kernel<0>(tf->cluster, tf->rpw, all_regs, xcd)
+                  : Z == 1 ? lanem_sym_kernel<1>(tf->cluster, tf->rpw, all_regs, xcd)
+                           : lanem_sym_kernel<2>(tf->cluster, tf->rpw, all_regs, xcd);
+    const int cus = device_cus();
+    // (the kernels alternate within a cycle: one cached answer each)
+    const int cap = acc  ? resident_cap(A->csym_cap, A->csym_cap_kernel, k)
+                  : zero ? resident_cap(A->zsym_cap, A->zsym_cap_kernel, k)
+                         : resident_cap(A->sym_cap, A->sym_cap_kernel, k);
+    int G = std::max(lanem_want_grid(A, tf, cap, cus), lanem_want_grid(A, tb, cap, cus));      // the larger wish of the two directions
     if (xcd) G = 8 * std::max(1, std::min(G, (cus / 8) * cap));   // 8x the wanted grid; the workgroups off the home XCD leave at once
     void *args[] = {(void *)&a};
     PAMG_HIP(hipLaunchKernel(k, dim3(G), dim3(BLK), args, 0, s));
@@ -1668,26 +1533,6 @@ int lanem_plan_info(const LaneMSched *t, int64_t *info, double *growth)
 }
 
 
-// workgroups of the static form that are certainly co-resident: (occupancy - 1, at most 8) per CU -- the occupancy query
-// can over-report by one per CU (MI355X_MICROARCH.md).  Asked once per schedule and kernel, not per sweep.
-static int lane_grid_cap(LaneSched *t, const void *k)
-{
-    if (t->cap > 0 && t->cap_kernel == k) return t->cap;
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess) nb = 2;
-    nb = std::max(1, std::min(nb - 1, 8));
-    t->cap = nb; t->cap_kernel = k;
-    return nb;
-}
-
-int device_cus_lane()
-{
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 64;
-    return p.multiProcessorCount;
-}
-
 template <typename T>
 static int lane_launch_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, const void *b, double omega, hipStream_t s)
 {
@@ -1708,21 +1553,17 @@ static int lane_launch_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, cons
         PAMG_HIP(hipMemcpyAsync(g->d_xold, x, (size_t)n * ts, hipMemcpyDeviceToDevice, s));
         a.x = (const T *)g->d_xold;
     }
-    if (A->gs_prof && !t->d_prof) {
-        PAMG_HIP(hipMalloc((void **)&t->d_prof, (size_t)t->ngroups * 4 * sizeof(long long)));
-        PAMG_HIP(hipMemset(t->d_prof, 0, (size_t)t->ngroups * 4 * sizeof(long long)));
-    }
+    if (A->gs_prof) PAMG_TRY(ensure_profile(&t->d_prof, t->ngroups));
     a.prof = A->gs_prof ? t->d_prof : nullptr;
     const int fgrid = (int)std::min<int64_t>(4096, (n + BLK - 1) / BLK);
-    hipLaunchKernelGGL((lane_fill_sentinel_kernel<T>), dim3(fgrid), dim3(BLK), 0, s, (T *)g->d_xs, n);
+    hipLaunchKernelGGL((fill_sentinel_kernel<T>), dim3(fgrid), dim3(BLK), 0, s, (T *)g->d_xs, n);
     PAMG_HIP(hipGetLastError());
     const int per_level = (int)((t->ngroups + g->nlevels - 1) / g->nlevels);
     const bool xcd = lane_one_xcd(A, g);
     const void *k = lane_kernel<T>(epi, t->L, t->K, xcd ? 1 : 0);
     if (!k) return PAMG_E_ARG;
-    static thread_local int cus = 0;
-    if (!cus) cus = device_cus_lane();
-    const int cap = lane_grid_cap(t, k);
+    const int cus = device_cus();
+    const int cap = resident_cap(t->cap, t->cap_kernel, k);
     // waves wanted: ~4 dependency levels of look-ahead (a wave that runs ahead waits in its poll loop with its operands in
     // registers) -- more waves poll more and the polls load the memory system (measured on the 256^3 hierarchy,
     // profiles/r04_microbench_lane_first.json: level 1, 227 groups per dependency level: 2.67 ms with 512 waves, 2.72 with
@@ -1733,17 +1574,7 @@ static int lane_launch_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, cons
     if (A->lane_G > 0) G = std::min(A->lane_G, cap * cus);
     G = (int)std::max<int64_t>(1, std::min<int64_t>(G, (t->ngroups + LANE_WPB - 1) / LANE_WPB));
     void *args[] = {(void *)&a};
-    if (xcd) {
-        // 8x the wanted grid is launched; the workgroups off the home XCD leave at once
-        PAMG_HIP(hipMemsetAsync(g->d_sync + 20, 0, 2 * sizeof(unsigned), s));
-        const int Gx = std::max(1, std::min(G, (cus / 8) * cap));
-        t->last_grid = 8 * Gx;
-        PAMG_HIP(hipLaunchKernel(k, dim3(8 * Gx), dim3(BLK), args, 0, s));
-        return PAMG_OK;
-    }
-    t->last_grid = G;
-    PAMG_HIP(hipLaunchKernel(k, dim3(G), dim3(BLK), args, 0, s));
-    return PAMG_OK;
+    return launch_persistent(k, args, G, xcd, g->d_sync + 20, cus, cap, &t->last_grid, s);
 }
 
 int lane_launch(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, const void *b, double omega, hipStream_t s)
@@ -1778,16 +1609,10 @@ int lanem_levels(const GsSchedule *g, int64_t *out, int64_t cap, int64_t *n)
 int lane_profile(const GsSchedule *g, long long *out, int64_t cap, int64_t *n)
 {
     *n = 0;
-    if (g && g->lanem && g->lanem->d_prof) {
-        // merged form: per ROW {arrival | spins << 52, slots arrived, all operands present, published}
-        *n = g->lanem->ngroups;
-        if (out && cap >= *n) PAMG_HIP(hipMemcpy(out, g->lanem->d_prof, (size_t)*n * 4 * sizeof(long long), hipMemcpyDeviceToHost));
-        return PAMG_OK;
-    }
+    // merged form: per ROW {arrival | spins << 52, slots arrived, all operands present, published}
+    if (g && g->lanem && g->lanem->d_prof) return read_profile(g->lanem->d_prof, g->lanem->ngroups, out, cap, n);
     if (!g || !g->lane || !g->lane->d_prof) return PAMG_OK;
-    *n = g->lane->ngroups;
-    if (out && cap >= *n) PAMG_HIP(hipMemcpy(out, g->lane->d_prof, (size_t)*n * 4 * sizeof(long long), hipMemcpyDeviceToHost));
-    return PAMG_OK;
+    return read_profile(g->lane->d_prof, g->lane->ngroups, out, cap, n);
 }
 
 }  // namespace pamg

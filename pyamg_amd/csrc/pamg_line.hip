@@ -14,6 +14,8 @@
 // scattered rows.
 #include "pamg_common.h"
 #include "pamg_line_plan.h"
+#include "pamg_wave.h"
+#include "pamg_sweep_host.h"
 
 namespace pamg {
 
@@ -30,26 +32,6 @@ struct LineSched {
     const void *cap_kernel = nullptr;
     size_t bytes = 0;
 };
-
-template <typename T> struct LSentinel;
-template <> struct LSentinel<double> {
-    using bits_t = unsigned long long;
-    static constexpr bits_t value = 0x7FF8DEADBEEF5A5Aull;
-    static __device__ __forceinline__ bits_t bits(double v) { return (bits_t)__double_as_longlong(v); }
-};
-template <> struct LSentinel<float> {
-    using bits_t = unsigned int;
-    static constexpr bits_t value = 0x7FC5BEEFu;
-    static __device__ __forceinline__ bits_t bits(float v) { return __float_as_uint(v); }
-};
-
-template <typename T>
-__global__ __launch_bounds__(BLK) void line_fill_sentinel_kernel(T *xs, int64_t n)
-{
-    using B = typename LSentinel<T>::bits_t;
-    B *p = reinterpret_cast<B *>(xs);
-    for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLK) p[i] = LSentinel<T>::value;
-}
 
 template <typename T>
 struct LineArgs {
@@ -174,13 +156,13 @@ __device__ __forceinline__ unsigned line_walk(const LineArgs<T> &a, T *wipe, int
             unsigned pend = 0;
 #pragma unroll
             for (int k = 0; k < K; ++k)
-                if (active && (S.c[k] & LINE_EARLY) && !(S.c[k] & LINE_NONE) && LSentinel<T>::bits(xv[k]) == LSentinel<T>::value) pend |= 1u << k;
+                if (active && (S.c[k] & LINE_EARLY) && !(S.c[k] & LINE_NONE) && Sentinel<T>::bits(xv[k]) == Sentinel<T>::value) pend |= 1u << k;
             unsigned spins = 0;
             if (a.use_gate && S.gate >= 0 && __builtin_amdgcn_ballot_w64(pend != 0)) {
                 const T *gp = a.xs + S.gate;
                 while (true) {
                     const T gv = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (LSentinel<T>::bits(gv) != LSentinel<T>::value) break;
+                    if (Sentinel<T>::bits(gv) != Sentinel<T>::value) break;
                     __builtin_amdgcn_s_sleep(2);
                     if ((++spins & 1023u) == 0 && (spins > (1u << 21) || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) break;
                 }
@@ -195,7 +177,7 @@ __device__ __forceinline__ unsigned line_walk(const LineArgs<T> &a, T *wipe, int
                 for (int k = 0; k < K; ++k)
                     if ((pend >> k) & 1u) {
                         xv[k] = t[k];
-                        if (LSentinel<T>::bits(t[k]) != LSentinel<T>::value) pend &= ~(1u << k);
+                        if (Sentinel<T>::bits(t[k]) != Sentinel<T>::value) pend &= ~(1u << k);
                     }
                 if ((++spins & 1023u) == 0) {
                     if (spins > (1u << 21) || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
@@ -232,10 +214,10 @@ __device__ __forceinline__ unsigned line_walk(const LineArgs<T> &a, T *wipe, int
             if (++g >= g1) break;
         }
         if constexpr (PH != 0) {
-            using B = typename LSentinel<T>::bits_t;
+            using B = typename Sentinel<T>::bits_t;
             const int lo = line * wq + (line < wr ? line : wr), cnt = wq + (line < wr ? 1 : 0);
             B *p = reinterpret_cast<B *>(wipe) + lo;
-            for (int i = lane; i < cnt; i += 64) __hip_atomic_store(p + i, LSentinel<T>::value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int i = lane; i < cnt; i += 64) __hip_atomic_store(p + i, Sentinel<T>::value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         ++walked;
     }
@@ -369,17 +351,6 @@ __global__ __launch_bounds__(256) void line_fill_kernel(int n, const int *__rest
 // ------------------------------------------------------------------ host side
 namespace {
 
-template <typename U>
-int line_upload(U **dst, const void *src, size_t bytes, size_t *total)
-{
-    *dst = nullptr;
-    const size_t alloc = std::max<size_t>(bytes, 256) + 256;
-    PAMG_HIP(hipMalloc((void **)dst, alloc));
-    if (bytes && src) PAMG_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));      // src = nullptr: allocation only (filled on the device)
-    if (total) *total += alloc;
-    return PAMG_OK;
-}
-
 template <typename T, int EPI>
 const void *line_kernel_k(int K)
 {
@@ -444,28 +415,28 @@ int build_line_part(pamg_matrix_s *A, GsSchedule *g)
     if (!t) return PAMG_E_ALLOC;
     t->K = P.K; t->step = P.step; t->nchunks = P.nchunks; t->nlines = P.nlines; t->nlevels = P.nlevels;
     t->n_early = P.n_early; t->max_level_lines = P.max_level_lines;
-    int st = line_upload(&t->d_row0, P.row0.data(), P.row0.size() * sizeof(int), &t->bytes);
-    if (!st) st = line_upload(&t->d_cnt, P.cnt.data(), P.cnt.size() * sizeof(int), &t->bytes);
-    if (!st) st = line_upload(&t->d_line_chunk, P.line_chunk.data(), P.line_chunk.size() * sizeof(int), &t->bytes);
+    int st = device_upload(&t->d_row0, P.row0.data(), P.row0.size() * sizeof(int), &t->bytes);
+    if (!st) st = device_upload(&t->d_cnt, P.cnt.data(), P.cnt.size() * sizeof(int), &t->bytes);
+    if (!st) st = device_upload(&t->d_line_chunk, P.line_chunk.data(), P.line_chunk.size() * sizeof(int), &t->bytes);
     if (host_fill) {
-        if (!st) st = line_upload(&t->d_cols, P.cols.data(), P.cols.size() * sizeof(int), &t->bytes);
-        if (!st) st = line_upload(&t->d_vals, P.vals.data(), P.vals.size(), &t->bytes);
-        if (!st) st = line_upload(&t->d_rdiag, P.rdiag.data(), P.rdiag.size(), &t->bytes);
-        if (!st) st = line_upload(&t->d_acoef, P.acoef.data(), P.acoef.size(), &t->bytes);
-        if (!st) st = line_upload(&t->d_nodiag, P.nodiag.data(), P.nodiag.size(), &t->bytes);
-        if (!st) st = line_upload(&t->d_gate, P.gate.data(), P.gate.size() * sizeof(int), &t->bytes);
+        if (!st) st = device_upload(&t->d_cols, P.cols.data(), P.cols.size() * sizeof(int), &t->bytes);
+        if (!st) st = device_upload(&t->d_vals, P.vals.data(), P.vals.size(), &t->bytes);
+        if (!st) st = device_upload(&t->d_rdiag, P.rdiag.data(), P.rdiag.size(), &t->bytes);
+        if (!st) st = device_upload(&t->d_acoef, P.acoef.data(), P.acoef.size(), &t->bytes);
+        if (!st) st = device_upload(&t->d_nodiag, P.nodiag.data(), P.nodiag.size(), &t->bytes);
+        if (!st) st = device_upload(&t->d_gate, P.gate.data(), P.gate.size() * sizeof(int), &t->bytes);
     } else {
         const size_t slots = (size_t)P.nchunks * P.K * 64, rows = (size_t)P.nchunks * 64;
         unsigned char *d_coupled = nullptr;
         unsigned long long *d_cnt2 = nullptr;
-        if (!st) st = line_upload(&t->d_cols, nullptr, slots * sizeof(int), &t->bytes);
-        if (!st) st = line_upload(&t->d_vals, nullptr, slots * ts, &t->bytes);
-        if (!st) st = line_upload(&t->d_rdiag, nullptr, rows * ts, &t->bytes);
-        if (!st) st = line_upload(&t->d_acoef, nullptr, rows * ts, &t->bytes);
-        if (!st) st = line_upload(&t->d_nodiag, nullptr, rows, &t->bytes);
-        if (!st) st = line_upload(&t->d_gate, nullptr, (size_t)P.nchunks * sizeof(int), &t->bytes);
-        if (!st) st = line_upload(&d_coupled, P.coupled.data(), P.coupled.size(), nullptr);
-        if (!st) st = line_upload(&d_cnt2, nullptr, 16, nullptr);
+        if (!st) st = device_upload(&t->d_cols, nullptr, slots * sizeof(int), &t->bytes);
+        if (!st) st = device_upload(&t->d_vals, nullptr, slots * ts, &t->bytes);
+        if (!st) st = device_upload(&t->d_rdiag, nullptr, rows * ts, &t->bytes);
+        if (!st) st = device_upload(&t->d_acoef, nullptr, rows * ts, &t->bytes);
+        if (!st) st = device_upload(&t->d_nodiag, nullptr, rows, &t->bytes);
+        if (!st) st = device_upload(&t->d_gate, nullptr, (size_t)P.nchunks * sizeof(int), &t->bytes);
+        if (!st) st = device_upload(&d_coupled, P.coupled.data(), P.coupled.size(), nullptr);
+        if (!st) st = device_upload(&d_cnt2, nullptr, 16, nullptr);
         if (!st) st = (int)hipMemset(d_cnt2, 0, 16);
         if (!st) {
             const unsigned grid = (unsigned)((P.nchunks + 3) / 4);
@@ -491,14 +462,6 @@ int build_line_part(pamg_matrix_s *A, GsSchedule *g)
     return PAMG_OK;
 }
 
-static int line_cus()
-{
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 64;
-    return p.multiProcessorCount;
-}
-
 template <typename T>
 static int line_launch_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, const void *b, double omega, hipStream_t s)
 {
@@ -520,19 +483,12 @@ static int line_launch_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, cons
         a.x = (const T *)g->d_xold;
     }
     const int fgrid = (int)std::min<int64_t>(4096, (n + BLK - 1) / BLK);
-    hipLaunchKernelGGL((line_fill_sentinel_kernel<T>), dim3(fgrid), dim3(BLK), 0, s, (T *)g->d_xs, n);
+    hipLaunchKernelGGL((fill_sentinel_kernel<T>), dim3(fgrid), dim3(BLK), 0, s, (T *)g->d_xs, n);
     PAMG_HIP(hipGetLastError());
     const void *k = epi == EPI_SOR ? line_kernel_k<T, EPI_SOR>(t->K) : line_kernel_k<T, EPI_GS>(t->K);
     if (!k) return PAMG_E_ARG;
-    static thread_local int cus = 0;
-    if (!cus) cus = line_cus();
-    if (t->cap <= 0 || t->cap_kernel != k) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess) nb = 2;
-        t->cap = std::max(1, std::min(nb - 1, 8));              // every workgroup must be resident (the query can over-report by one)
-        t->cap_kernel = k;
-    }
-    const int cap = t->cap;
+    const int cus = device_cus();
+    const int cap = resident_cap(t->cap, t->cap_kernel, k);
     // waves: a few dependency levels of lines in flight (a line that runs ahead waits with its operands in registers)
     const int64_t want_waves = std::max<int64_t>(256, 4 * t->max_level_lines);
     int G = (int)std::min<int64_t>((want_waves + LINE_WPB - 1) / LINE_WPB, (int64_t)cap * cus);
@@ -583,15 +539,8 @@ int line_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, c
         case 8: k = (const void *)gs_line_sym_kernel<T, 8>; break;
     }
     if (!k) return PAMG_E_UNSUPPORTED;
-    static thread_local int cus = 0;
-    if (!cus) cus = line_cus();
-    if (A->sym_cap <= 0 || A->sym_cap_kernel != k) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, BLK, 0) != hipSuccess) nb = 2;
-        A->sym_cap = std::max(1, std::min(nb - 1, 8));          // every workgroup must be resident (the query can over-report by one)
-        A->sym_cap_kernel = k;
-    }
-    const int cap = A->sym_cap;
+    const int cus = device_cus();
+    const int cap = resident_cap(A->sym_cap, A->sym_cap_kernel, k);
     int G = 1;
     for (int p = 0; p < 2; ++p) {
         const LineSched *t = gs2[p]->line;

@@ -2416,7 +2416,7 @@ int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[9])
     std::vector<unsigned long long> h((size_t)A->nrows);
     if (A->nrows) PAMG_HIP(hipMemcpy(h.data(), A->d_sym_hf[w[5] & 1u], (size_t)A->nrows * 8, hipMemcpyDeviceToHost));
     int64_t bad = 0;
-    for (unsigned long long v : h) bad += (v != 0x7FF8DEADBEEF5A5Aull);
+    for (unsigned long long v : h) bad += (v != pamg::Sentinel<double>::value);
     info[5] = bad;
     info[6] = 0;
     for (int k = 0; k < 5; ++k) info[6] += w[k] != 0u;

@@ -25,6 +25,7 @@
 
 #include "pamg_common.h"
 #include "pamg_schwarz_plan.h"
+#include "pamg_wave.h"
 
 namespace pamg {
 struct SchwarzSchedule {
@@ -99,26 +100,6 @@ __global__ __launch_bounds__(SW_THREADS) void schwarz_level_kernel(const int *or
 
 
 // ---- the versioned persistent sweep: see the header
-template <typename T> struct SwSentinel;
-template <> struct SwSentinel<double> {
-    using bits_t = unsigned long long;
-    static constexpr bits_t value = 0x7FF8DEADBEEF5A5Aull;
-    static __device__ __forceinline__ bits_t bits(double v) { return (bits_t)__double_as_longlong(v); }
-};
-template <> struct SwSentinel<float> {
-    using bits_t = unsigned int;
-    static constexpr bits_t value = 0x7FC5BEEFu;
-    static __device__ __forceinline__ bits_t bits(float v) { return __float_as_uint(v); }
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void schwarz_fill_kernel(T *xs, int64_t n)
-{
-    using B = typename SwSentinel<T>::bits_t;
-    B *p = reinterpret_cast<B *>(xs);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = SwSentinel<T>::value;
-}
-
 // x takes the last version of every row the sweep updated
 template <typename T>
 __global__ __launch_bounds__(256) void schwarz_close_kernel(const T *xs, const int *last, T *x, int n)
@@ -140,7 +121,7 @@ __global__ __launch_bounds__(SW_THREADS) void schwarz_versioned_kernel(const int
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     T *r = reinterpret_cast<T *>(smem);
-    using S = SwSentinel<T>;
+    using S = Sentinel<T>;
     for (int q = blockIdx.x; q < m; q += gridDim.x) {
         const int d = order[q], e0 = ebase[q];
         const int s0 = Sp[d], size = Sp[d + 1] - s0;
@@ -425,16 +406,16 @@ int schwarz_sweep(pamg_schwarz_s *h, void *x, const void *b, int start, int stop
     if (h->mode == 0 && !force_levels && g->nlevels > 1 && g->versioned) {
         const int grid = A->dtype == PAMG_F64 ? persistent_grid<double>(h, *g, lds) : persistent_grid<float>(h, *g, lds);
         if (grid > 0) {
-            const int fill_grid = (int)std::min<int64_t>(4096, (g->nslots + 255) / 256), close_grid = (int)std::min<int64_t>(4096, ((int64_t)A->nrows + 255) / 256);
+            const int fill_grid = (int)std::min<int64_t>(4096, (g->nslots + BLK - 1) / BLK), close_grid = (int)std::min<int64_t>(4096, ((int64_t)A->nrows + 255) / 256);
             if (A->dtype == PAMG_F64) {
-                hipLaunchKernelGGL((schwarz_fill_kernel<double>), dim3(fill_grid), dim3(256), 0, s, (double *)h->d_xs, g->nslots);
+                hipLaunchKernelGGL((fill_sentinel_kernel<double>), dim3(fill_grid), dim3(BLK), 0, s, (double *)h->d_xs, g->nslots);
                 hipLaunchKernelGGL((schwarz_versioned_kernel<double>), dim3(grid), dim3(SW_THREADS), lds, s, (const int *)g->d_order, (const int *)g->d_ebase,
                                    (const int *)g->d_wslot, (const int *)g->d_prev, (const int *)g->d_roff, (const unsigned char *)g->d_rver, (const int *)g->d_vbase,
                                    g->m, (double *)h->d_xs, h->d_err, h->d_Sp, h->d_Sj, h->d_Tp, (const double *)h->d_Tx, A->d_Ap, A->d_Aj, (const double *)A->d_Ax,
                                    (const double *)x, (const double *)b);
                 hipLaunchKernelGGL((schwarz_close_kernel<double>), dim3(close_grid), dim3(256), 0, s, (const double *)h->d_xs, (const int *)g->d_last, (double *)x, (int)A->nrows);
             } else {
-                hipLaunchKernelGGL((schwarz_fill_kernel<float>), dim3(fill_grid), dim3(256), 0, s, (float *)h->d_xs, g->nslots);
+                hipLaunchKernelGGL((fill_sentinel_kernel<float>), dim3(fill_grid), dim3(BLK), 0, s, (float *)h->d_xs, g->nslots);
                 hipLaunchKernelGGL((schwarz_versioned_kernel<float>), dim3(grid), dim3(SW_THREADS), lds, s, (const int *)g->d_order, (const int *)g->d_ebase,
                                    (const int *)g->d_wslot, (const int *)g->d_prev, (const int *)g->d_roff, (const unsigned char *)g->d_rver, (const int *)g->d_vbase,
                                    g->m, (float *)h->d_xs, h->d_err, h->d_Sp, h->d_Sj, h->d_Tp, (const float *)h->d_Tx, A->d_Ap, A->d_Aj, (const float *)A->d_Ax,

@@ -354,7 +354,7 @@ __device__ __forceinline__ bool compute_step(const TileArgs<T> &a, const SlotGeo
     lds_flag_store(TC_DONE, (unsigned)(t + 1));             // every read of this slot has been consumed: the loader may refill it
     if (a.prof && lane == 0) {
         long long *o = a.prof + (size_t)(s0 + t) * 8;
-        o[0] = tp0; o[1] = wall_clock64(); o[2] = (long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xF); o[3] = tile;
+        o[0] = tp0; o[1] = wall_clock64(); o[2] = (long long)xcc_id(); o[3] = tile;
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[4 + k] = stamps[k];
     }

@@ -1193,6 +1193,132 @@ def test_kaczmarz_fast_order_agrees_to_rounding():
             dL.free()
 
 
+def _banded_lines(m, per_line, rng):
+    """m x m, non-symmetric, contiguous diagonals with twice as many below the main one as above it: exactly `per_line` stored entries per
+    interior line; the diagonal is the row's absolute sum plus one"""
+    up = (per_line - 1) // 3
+    offs = [o for o in range(up + 1 - per_line, up + 1) if o != 0]
+    M = sp.csr_array(sp.diags_array([2.0 * rng.rand(m - abs(o)) - 1.0 for o in offs], offsets=offs, shape=(m, m)))
+    M = sp.csr_array(M + sp.diags_array(np.asarray(abs(M).sum(axis=1)).ravel() + 1.0))
+    M.sort_indices()
+    return M
+
+
+def _narrow_block_rows(rng, nbr=900, bs=3, most=8, diag_boost=5.0):
+    """the "3x3 nonsym" operator of test_block_gauss_seidel_fast_order_agrees_to_rounding (random non-symmetric block pattern, every eleventh
+    diagonal block missing) with at most `most` blocks per block row -- the diagonal one and off-diagonal ones spread over the row --, so that
+    the narrowest lane kernel holds a row"""
+    Pn = sp.random(nbr, nbr, density=0.01, random_state=rng, format="lil")
+    for i in range(nbr):
+        if i % 11 != 5:
+            Pn[i, i] = 1.0
+    P = sp.csr_array(Pn); P.sort_indices()
+    rows = np.repeat(np.arange(nbr), np.diff(P.indptr))
+    keep = rows == P.indices
+    for i in range(nbr):
+        off = np.flatnonzero((rows == i) & ~keep)
+        keep[off[::max(1, -(-off.size // (most - 1)))]] = True
+    ip = np.concatenate([[0], np.cumsum(np.bincount(rows[keep], minlength=nbr))]).astype(np.int32)
+    ij = P.indices[keep].astype(np.int32)
+    dat = (rng.rand(ij.size, bs, bs) - 0.5) * 0.3
+    dat[rows[keep] == ij] += diag_boost * np.eye(bs)
+    return sp.bsr_array((dat, ij, ip), shape=(bs * nbr, bs * nbr), blocksize=(bs, bs))
+
+
+def test_every_lane_width_of_the_block_and_kaczmarz_sweeps():
+    """Every width of the sum across the lanes of a row (csrc/pamg_wave.h: seg_allreduce) in the two sweeps whose other tests do not reach them
+    all.  Kaczmarz (csrc/pamg_kz.hip): banded non-symmetric operators of 768 lines with 5, 24, 48, 96 and 192 entries per line -- 4, 8, 16, 32
+    and 64 lanes per line (pamg_lane_plan.h: lane_geometry) --, gauss_seidel_ne and gauss_seidel_nr, symmetric sweep, two iterations: exact order
+    = the oracle's loops bit for bit, fast order within 1e-13 of them, the same bits on a second run, no time-out.  Block Gauss-Seidel
+    (csrc/pamg_blane.hip): a 3x3 non-symmetric pattern of 900 block rows of at most 8 blocks with 8, 16, 32 and 64 lanes per block row forced in
+    turn: fast order within 1e-13 of the exact order (= the reference's bits), reproducible."""
+    from oracle import oracle as orc
+    from pyamg_amd.hierarchy import _normal_equation_spec as _nes
+    rng = np.random.RandomState(47)
+    m = 768
+    for per_line, lanes in ((5, 4), (24, 8), (48, 16), (96, 32), (192, 64)):
+        M = _banded_lines(m, per_line, rng)
+        assert np.diff(M.indptr).max() == per_line and np.diff(sp.csc_array(M).indptr).max() == per_line
+        x, b = rng.rand(m), rng.rand(m)
+        for kind, omega in (("gauss_seidel_ne", 0.9), ("gauss_seidel_nr", 1.1)):
+            spec = _nes(kind, M, 1, "forward", omega)
+            Lop = sparse_op(M) if kind == "gauss_seidel_ne" else spec.At
+            dL = DeviceMatrix(Lop)
+            dD = capi.DeviceArray.from_host(spec.Dinv)
+            db = capi.DeviceArray.from_host(b)
+            out = {}
+            for order in (0, 1, 1):
+                dL.tune(gs_order=order)
+                if kind == "gauss_seidel_ne":
+                    dv = capi.DeviceArray.from_host(x)
+                    dL.kaczmarz(dv, dD, omega, "symmetric", 2, b=db)
+                    got = (dv.download(),)
+                else:
+                    dr = capi.DeviceArray.from_host(b - M @ x)
+                    dxo = capi.DeviceArray.from_host(x)
+                    dL.kaczmarz(dr, dD, omega, "symmetric", 2, xout=dxo)
+                    got = (dxo.download(), dr.download())
+                assert not dL.flow_error(), (per_line, kind, order)
+                if order == 1:
+                    info = dL.kz_info(0)
+                    assert info["groups"] > 0 and info["lanes_per_line"] == lanes, (per_line, kind, info)
+                    if 1 in out:
+                        assert all(np.array_equal(a_, b_) for a_, b_ in zip(out[1], got)), (per_line, kind)      # reproducible
+                out[order] = got
+            dirs = [(0, m, 1), (m - 1, -1, -1)] * 2
+            if kind == "gauss_seidel_ne":
+                xo = x.copy()
+                for (r0, r1, rs) in dirs:
+                    orc.gauss_seidel_ne(Lop.indptr, Lop.indices, Lop.data, xo, b, r0, r1, rs, spec.Dinv, omega)
+                want = (xo,)
+            else:
+                xo, ro = x.copy(), b - M @ x
+                for (r0, r1, rs) in dirs:
+                    orc.gauss_seidel_nr(Lop.indptr, Lop.indices, Lop.data, xo, ro, r0, r1, rs, spec.Dinv, omega)
+                want = (xo, ro)
+            for w_, e_, f_ in zip(want, out[0], out[1]):
+                err = np.max(np.abs(w_ - f_))
+                print(f"kaczmarz {kind} {per_line} entries per line, {lanes} lanes: fast order - oracle = {err:.3e} (bound {1e-13 * max(1.0, np.max(np.abs(w_))):.3e})")
+                assert np.array_equal(w_, e_), (per_line, kind)                                   # exact order: the oracle's bits
+                assert err <= 1e-13 * max(1.0, np.max(np.abs(w_))), (per_line, kind, err)
+            dL.free()
+    # block Gauss-Seidel
+    rng = np.random.RandomState(31)
+    M = _narrow_block_rows(rng)
+    bs = M.blocksize[0]
+    assert np.diff(M.indptr).max() <= 8
+    op = sparse_op(M)
+    n = op.shape[0]; nb = n // bs
+    x, b = rng.rand(n), rng.rand(n)
+    Dinv = np.zeros((nb, bs, bs))
+    rows = np.repeat(np.arange(nb), np.diff(M.indptr))
+    dm = rows == M.indices
+    Dinv[rows[dm]] = np.linalg.inv(M.data[dm])
+    db = capi.DeviceArray.from_host(b)
+    dD = capi.DeviceArray.from_host(Dinv.reshape(-1))
+    for lanes in (8, 16, 32, 64):
+        dM = DeviceMatrix(op)
+        dM.tune(lane_L=lanes)
+        out = {}
+        for order in (0, 1, 1):
+            dM.tune(gs_order=order)
+            dx = capi.DeviceArray.from_host(x)
+            dM.block_gauss_seidel(dx, db, dD, sweep="symmetric", iterations=2)
+            got = dx.download()
+            assert not dM.flow_error(), (lanes, order)
+            if order == 1:
+                for which in (0, 1):
+                    info = dM.lane_info(which)
+                    assert info["groups"] > 0 and info["lanes_per_row"] == lanes, (lanes, which, info)
+                if 1 in out:
+                    assert np.array_equal(out[1], got), lanes                                     # reproducible
+            out[order] = got
+        err = np.max(np.abs(out[0] - out[1]))
+        print(f"block gauss_seidel, {lanes} lanes per block row: fast order - exact order = {err:.3e} (bound {1e-13 * max(1.0, np.max(np.abs(out[0]))):.3e})")
+        assert err <= 1e-13 * max(1.0, np.max(np.abs(out[0]))), (lanes, err)
+        dM.free()
+
+
 def test_layer1_operator_cache():
     """Layer 1 keeps the last operators resident: the same three arrays again -> no new entry; the same arrays with
     CHANGED contents -> the stale copy is replaced and the sweep uses the new values; other arrays -> another entry.
