@@ -414,6 +414,44 @@ int pamg_min_blocks_f64(int32_t n_blocks, int32_t blocksize, const double *Sx, i
 int pamg_evolution_strength_vector_f64(double *Sx, int Sx_size, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,
                                        int32_t nrows, const double *d, int d_size, const double *b, int b_size);
 
+/* Energy-minimisation prolongation smoothing with CG (csrc/pamg_energy.hip, the arithmetic in csrc/pamg_energy.h).  float64, HOST
+ * arrays; blocks are row-major and at most 6 x 6, at most 6 candidates (beyond: PAMG_E_UNSUPPORTED).  Patterns are checked as above
+ * before anything is written.
+ *
+ * amg_core::incomplete_mat_mult_bsr, smoothed_aggregation.h:970-1042: Sx += (A B) on the stored blocks of S.  A has brow_A x bcol_A
+ * blocks, B bcol_A x bcol_B, S brow_A x bcol_B.  An element accumulates, onto the value that came in, the contributions in the order of
+ * A's stored row and within it of B's stored row (every match; no row need be sorted), a block product in gemm's order: the
+ * reference's result bit for bit.  A stored block of S that receives nothing keeps its values. */
+int pamg_incomplete_mat_mult_bsr_f64(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *Ax, int Ax_size,
+                                     const int32_t *Bp, int Bp_size, const int32_t *Bj, int Bj_size, const double *Bx, int Bx_size,
+                                     const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size, double *Sx, int Sx_size,
+                                     int32_t n_brow, int32_t n_bcol, int32_t brow_A, int32_t bcol_A, int32_t bcol_B);
+/* amg_core::satisfy_constraints_helper, smoothed_aggregation.h:722-771 (real T): Sx -= UB_i (BtBinv_i B_j^H) for every stored block
+ * (i, j).  Bt = B row-major [n_bcol * cols_per_block, NullDim], UB [num_block_rows * rows_per_block, NullDim], BtBinv
+ * [num_block_rows, NullDim, NullDim].  Bit for bit. */
+int pamg_satisfy_constraints_helper_f64(int32_t rows_per_block, int32_t cols_per_block, int32_t num_block_rows, int32_t NullDim,
+                                        const double *Bt, int Bt_size, const double *UB, int UB_size, const double *BtBinv,
+                                        int BtBinv_size, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size, double *Sx,
+                                        int Sx_size);
+/* aggregation/smooth.py satisfy_constraints whole: UB = S @ B in the order of SciPy's bsr_matvecs (blocks in stored order), then the
+ * helper above, in one kernel.  Bit for bit. */
+int pamg_satisfy_constraints_f64(int32_t rows_per_block, int32_t cols_per_block, int32_t num_block_rows, int32_t NullDim,
+                                 const double *B, int B_size, const double *BtBinv, int BtBinv_size, const int32_t *Sp, int Sp_size,
+                                 const int32_t *Sj, int Sj_size, double *Sx, int Sx_size);
+/* The loop of cg_prolongation_smoothing (smooth.py:347-442) resident on the device.  A: BSR, n_brow x n_brow blocks of r x r; Sp / Sj:
+ * the pattern, n_brow x n_bcol blocks of r x c; Tx: T expanded onto the pattern (in: the tentative prolongator, out: the smoothed one
+ * -- the only array that travels both ways); B [n_bcol * c, NullDim]; BtBinv [n_brow, NullDim, NullDim]; Dinv [n_brow * r]: the row
+ * weights; cmask [n_brow * r] (non-zero: a C-point row) and PIx (the injection expanded onto the pattern): both or neither.
+ * iterations <- the updates of T done, newsums[0 .. *n_newsums) <- <R, Dinv R> of every iteration that computed it (the one that met
+ * `newsum < tol` included; room for maxiter values).  The two inner products are summed by a fixed tree over the block rows, so the
+ * result depends on the operands alone; against the reference's summation order it agrees to rounding.  Per iteration one int is
+ * read back. */
+int pamg_energy_cg_f64(int32_t n_brow, int32_t n_bcol, int32_t r, int32_t c, int32_t NullDim, const int32_t *Ap, int Ap_size,
+                       const int32_t *Aj, int Aj_size, const double *Ax, int64_t Ax_size, const int32_t *Sp, int Sp_size,
+                       const int32_t *Sj, int Sj_size, double *Tx, int64_t Tx_size, const double *B, int B_size,
+                       const double *BtBinv, int64_t BtBinv_size, const double *Dinv, int Dinv_size, const unsigned char *cmask,
+                       const double *PIx, int32_t maxiter, double tol, int32_t *iterations, double *newsums, int32_t *n_newsums);
+
 /* ------------------------------------------------------ Layer 2: resident engine (HBM) */
 /* Operator handle: uploads CSR/BSR arrays (HOST pointers) to HBM once and analyses them
  * (row-block plan for the LDS-streamed kernels; dependency-level schedules for the

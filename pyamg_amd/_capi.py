@@ -133,6 +133,11 @@ def _declare(lib):
     f("pamg_apply_absolute_distance_filter_f64", _i, _d, *(_vp, _i) * 3)
     f("pamg_min_blocks_f64", _i, _i, _vp, _i, _vp, _i)
     f("pamg_evolution_strength_vector_f64", *(_vp, _i) * 3, _i, *(_vp, _i) * 2)
+    f("pamg_incomplete_mat_mult_bsr_f64", *(_vp, _i) * 9, _i, _i, _i, _i, _i)
+    f("pamg_satisfy_constraints_helper_f64", _i, _i, _i, _i, *(_vp, _i) * 6)
+    f("pamg_satisfy_constraints_f64", _i, _i, _i, _i, *(_vp, _i) * 5)
+    f("pamg_energy_cg_f64", _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, C.c_int64, _vp, _i, _vp, _i, _vp, C.c_int64, _vp, _i, _vp, C.c_int64,
+      _vp, _i, _vp, _vp, _i, _d, P(_i), _vp, P(_i))
     f("pamg_fit_tentative_f64", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d)
     f("pamg_fit_tentative_f32", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float)
     f("pamg_matrix_create", P(_vp), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp)

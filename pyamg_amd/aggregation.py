@@ -761,7 +761,8 @@ _CLASSICAL_NAMES = ("classical_strength_of_connection", "direct_interpolation", 
 
 
 @contextlib.contextmanager
-def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False, evolution=False):
+def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False, evolution=False,
+                 energy=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -795,7 +796,13 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     deprecated ``ode_strength_of_connection`` resolves the patched name by itself).  Given the same spectral radius the arrays are the
     reference's bit for bit; with the device Arnoldi's they agree to rounding (``pyamg_amd.evolution``).  Off by default for the reason
     given for ``classical``: the measurement in DESIGN 3b decides a later default.  With ``evolution=False`` nothing changes, and neither
-    ``pyamg_amd.evolution`` nor anything under ``<pyamg>.classical`` is imported on its account."""
+    ``pyamg_amd.evolution`` nor anything under ``<pyamg>.classical`` is imported on its account.
+    ``energy=True`` routes ``cg_prolongation_smoothing`` and ``satisfy_constraints`` to ``pyamg_amd.energy`` in ``<pyamg>.aggregation.smooth``,
+    where ``energy_prolongation_smoother`` -- the only smoother ``rootnode_solver`` accepts -- resolves them: the CG loop then runs resident
+    on the device.  ``satisfy_constraints`` is the reference's bit for bit; the CG result agrees to rounding (its two inner products are
+    summed in a fixed tree, not in SciPy's order: ``pyamg_amd.energy``).  ``weighting='block'``, complex or float32 operands and whatever
+    else the device path does not take go to the function that was patched out; the CGNR and GMRES variants are not touched.  Off by
+    default for the reason given for ``classical``.  With ``energy=False`` nothing changes and ``pyamg_amd.energy`` is not imported."""
     import importlib
     from . import air as _air
     from . import classical as _cls
@@ -811,6 +818,11 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
         evo_table = tuple((mod, "evolution_strength_of_connection", _evo.evolution_strength_of_connection)
                           for mod in ("strength", "aggregation.aggregation", "aggregation.rootnode", "aggregation.adaptive",
                                       "classical.classical", "classical.air"))
+    energy_table = ()
+    if energy:
+        from . import energy as _en
+        energy_table = (("aggregation.smooth", "cg_prolongation_smoothing", _en.cg_prolongation_smoothing),
+                        ("aggregation.smooth", "satisfy_constraints", _en.satisfy_constraints))
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
                           ("aggregation.aggregation", "richardson_prolongation_smoother", richardson_prolongation_smoother),
@@ -831,7 +843,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                           ("classical.classical", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.interpolate", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.split", "PMIS", _cls.PMIS),
-                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table:
+                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table:
         of_air = (mod, name, fn) in air_table
         if not classical and name in _CLASSICAL_NAMES and not of_air:
             continue                            # (before the import: with classical=False nothing of <pyamg>.classical is touched)
@@ -852,7 +864,8 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                 setattr(m, name, _rho_or_reference(old))
             elif name == "schwarz_parameters":
                 setattr(m, name, _schwarz_parameters_or_reference(old))
-            elif name in ("standard_aggregation", "fit_candidates", "evolution_strength_of_connection") or name in _CLASSICAL_NAMES or of_air:
+            elif name in ("standard_aggregation", "fit_candidates", "evolution_strength_of_connection") or name in _CLASSICAL_NAMES or of_air or \
+                    (mod, name, fn) in energy_table:
                 setattr(m, name, _device_or_reference(fn, old))
             else:
                 setattr(m, name, fn)

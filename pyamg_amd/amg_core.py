@@ -21,7 +21,7 @@ __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_
            "rs_classical_interpolation_pass1", "rs_classical_interpolation_pass2",
            "one_point_interpolation", "approx_ideal_restriction_pass1", "approx_ideal_restriction_pass2",
            "incomplete_mat_mult_csr", "evolution_strength_helper", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
-           "evolution_strength_vector"]
+           "evolution_strength_vector", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "satisfy_constraints", "energy_cg"]
 
 
 def _sfx(Ax, *vals):
@@ -391,3 +391,50 @@ def evolution_strength_vector(Sx, Sp, Sj, nrows, d, b):
     _idx(Sp, Sj)
     _f64(Sx, d, b)
     capi.check(capi.lib().pamg_evolution_strength_vector_f64(*_pairs(Sx, Sp, Sj), int(nrows), *_pairs(d, b)), "evolution_strength_vector")
+
+
+# ------------------------------------------------------------------ energy-minimisation prolongation smoothing: csrc/pamg_energy.hip
+def incomplete_mat_mult_bsr(Ap, Aj, Ax, Bp, Bj, Bx, Sp, Sj, Sx, n_brow, n_bcol, brow_A, bcol_A, bcol_B):
+    """amg_core.incomplete_mat_mult_bsr (smoothed_aggregation.h:970-1042): Sx += (A @ B) on the stored blocks of S; blocks up to 6 x 6."""
+    _idx(Ap, Aj, Bp, Bj, Sp, Sj)
+    _f64(Ax, Bx, Sx)
+    capi.check(capi.lib().pamg_incomplete_mat_mult_bsr_f64(*_pairs(Ap, Aj, Ax, Bp, Bj, Bx, Sp, Sj, Sx), int(n_brow), int(n_bcol), int(brow_A),
+                                                          int(bcol_A), int(bcol_B)), "incomplete_mat_mult_bsr")
+
+
+def satisfy_constraints_helper(rows_per_block, cols_per_block, num_block_rows, NullDim, x, y, z, Sp, Sj, Sx):
+    """amg_core.satisfy_constraints_helper (smoothed_aggregation.h:722-771), real float64: x = conj(B) ravelled, y = U @ B ravelled,
+    z = BtBinv ravelled."""
+    _idx(Sp, Sj)
+    _f64(x, y, z, Sx)
+    capi.check(capi.lib().pamg_satisfy_constraints_helper_f64(int(rows_per_block), int(cols_per_block), int(num_block_rows), int(NullDim),
+                                                             *_pairs(x, y, z, Sp, Sj, Sx)), "satisfy_constraints_helper")
+
+
+def satisfy_constraints(rows_per_block, cols_per_block, num_block_rows, NullDim, B, BtBinv, Sp, Sj, Sx):
+    """smooth.py's satisfy_constraints on the raw arrays: U @ B in the order of SciPy's bsr_matvecs, then the helper, as one kernel.  (The
+    reference composes this in Python; it has no amg_core twin.)"""
+    _idx(Sp, Sj)
+    _f64(B, BtBinv, Sx)
+    capi.check(capi.lib().pamg_satisfy_constraints_f64(int(rows_per_block), int(cols_per_block), int(num_block_rows), int(NullDim),
+                                                      *_pairs(B, BtBinv, Sp, Sj, Sx)), "satisfy_constraints")
+
+
+def energy_cg(n_brow, n_bcol, r, c, NullDim, Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, Dinv, cmask, PIx, maxiter, tol):
+    """The loop of cg_prolongation_smoothing resident on the device (pamg_energy_cg_f64): Tx, T expanded onto the pattern Sp / Sj, is
+    smoothed in place; returns (iterations done, the newsum of every iteration)."""
+    import ctypes
+    _idx(Ap, Aj, Sp, Sj)
+    _f64(Ax, Tx, B, BtBinv, Dinv)
+    if (cmask is None) != (PIx is None):
+        raise TypeError("incompatible function arguments (cmask and PIx go together)")
+    if cmask is not None:
+        _f64(PIx)
+        if not isinstance(cmask, np.ndarray) or cmask.dtype != np.uint8 or not cmask.flags.c_contiguous or cmask.size != n_brow * r or PIx.size != Tx.size:
+            raise TypeError("incompatible function arguments (cmask: contiguous uint8 per row, PIx: like Tx)")
+    its, ns = ctypes.c_int(0), ctypes.c_int(0)
+    sums = np.zeros(max(int(maxiter), 1))
+    p = capi.ptr
+    capi.check(capi.lib().pamg_energy_cg_f64(int(n_brow), int(n_bcol), int(r), int(c), int(NullDim), *_pairs(Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, Dinv),
+                                            p(cmask), p(PIx), int(maxiter), float(tol), ctypes.byref(its), p(sums), ctypes.byref(ns)), "energy_cg")
+    return int(its.value), sums[:int(ns.value)].copy()

@@ -5,9 +5,13 @@
 // pamg_*_f64).  Plain g++ builds it (no HIP here); pyamg_amd/amg_core.py is the ctypes twin of the same surface.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
+#include <pybind11/stl.h>
 
+#include <algorithm>
+#include <optional>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/pyamg_amd.h"
 
@@ -251,5 +255,41 @@ PYBIND11_MODULE(_amg_core_pybind, m)
         done(pamg_evolution_strength_vector_f64(Sx.mutable_data(), len(Sx), Sp.data(), len(Sp), Sj.data(), len(Sj), nrows, d.data(), len(d), b.data(),
                                                 len(b)), "evolution_strength_vector");
     }, nc("Sx"), nc("Sp"), nc("Sj"), py::arg("nrows"), nc("d"), nc("b"));
+    // energy-minimisation prolongation smoothing, float64 (smoothed_aggregation_bind.cpp): csrc/pamg_energy.hip
+    m.def("incomplete_mat_mult_bsr", [](Idx &Ap, Idx &Aj, D &Ax, Idx &Bp, Idx &Bj, D &Bx, Idx &Sp, Idx &Sj, D &Sx, int n_brow, int n_bcol, int brow_A,
+                                        int bcol_A, int bcol_B) {
+        done(pamg_incomplete_mat_mult_bsr_f64(Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), Bp.data(), len(Bp), Bj.data(), len(Bj),
+                                              Bx.data(), len(Bx), Sp.data(), len(Sp), Sj.data(), len(Sj), Sx.mutable_data(), len(Sx), n_brow, n_bcol,
+                                              brow_A, bcol_A, bcol_B), "incomplete_mat_mult_bsr");
+    }, nc("Ap"), nc("Aj"), nc("Ax"), nc("Bp"), nc("Bj"), nc("Bx"), nc("Sp"), nc("Sj"), nc("Sx"), py::arg("n_brow"), py::arg("n_bcol"),
+       py::arg("brow_A"), py::arg("bcol_A"), py::arg("bcol_B"));
+    m.def("satisfy_constraints_helper", [](int rows_per_block, int cols_per_block, int num_block_rows, int NullDim, D &x, D &y, D &z, Idx &Sp,
+                                           Idx &Sj, D &Sx) {
+        done(pamg_satisfy_constraints_helper_f64(rows_per_block, cols_per_block, num_block_rows, NullDim, x.data(), len(x), y.data(), len(y),
+                                                 z.data(), len(z), Sp.data(), len(Sp), Sj.data(), len(Sj), Sx.mutable_data(), len(Sx)),
+             "satisfy_constraints_helper");
+    }, py::arg("rows_per_block"), py::arg("cols_per_block"), py::arg("num_block_rows"), py::arg("NullDim"), nc("x"), nc("y"), nc("z"), nc("Sp"),
+       nc("Sj"), nc("Sx"));
+    m.def("satisfy_constraints", [](int rows_per_block, int cols_per_block, int num_block_rows, int NullDim, D &B, D &BtBinv, Idx &Sp, Idx &Sj,
+                                    D &Sx) {
+        done(pamg_satisfy_constraints_f64(rows_per_block, cols_per_block, num_block_rows, NullDim, B.data(), len(B), BtBinv.data(), len(BtBinv),
+                                          Sp.data(), len(Sp), Sj.data(), len(Sj), Sx.mutable_data(), len(Sx)), "satisfy_constraints");
+    }, py::arg("rows_per_block"), py::arg("cols_per_block"), py::arg("num_block_rows"), py::arg("NullDim"), nc("B"), nc("BtBinv"), nc("Sp"), nc("Sj"),
+       nc("Sx"));
+    // cmask / PIx: None without root nodes.  Returns (iterations, the newsum of every iteration)
+    m.def("energy_cg", [](int n_brow, int n_bcol, int r, int c, int NullDim, Idx &Ap, Idx &Aj, D &Ax, Idx &Sp, Idx &Sj, D &Tx, D &B, D &BtBinv, D &Dinv,
+                          std::optional<py::array_t<unsigned char, py::array::c_style>> cmask, std::optional<D> PIx, int maxiter, double tol) {
+        if (cmask.has_value() != PIx.has_value() || (cmask && (cmask->size() != (py::ssize_t)n_brow * r || PIx->size() != Tx.size())))
+            throw py::type_error("energy_cg(): cmask (one byte per row) and PIx (like Tx) go together");
+        std::vector<double> sums((size_t)std::max(maxiter, 1));
+        int its = 0, ns = 0;
+        done(pamg_energy_cg_f64(n_brow, n_bcol, r, c, NullDim, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), (int64_t)Ax.size(), Sp.data(), len(Sp),
+                                Sj.data(), len(Sj), Tx.mutable_data(), (int64_t)Tx.size(), B.data(), len(B), BtBinv.data(), (int64_t)BtBinv.size(),
+                                Dinv.data(), len(Dinv), cmask ? cmask->data() : nullptr, PIx ? PIx->data() : nullptr, maxiter, tol, &its, sums.data(),
+                                &ns), "energy_cg");
+        return py::make_tuple(its, py::array_t<double>(ns, sums.data()));
+    }, py::arg("n_brow"), py::arg("n_bcol"), py::arg("r"), py::arg("c"), py::arg("NullDim"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Sp"), nc("Sj"), nc("Tx"),
+       nc("B"), nc("BtBinv"), nc("Dinv"), py::arg("cmask").noconvert().none(true), py::arg("PIx").noconvert().none(true), py::arg("maxiter"),
+       py::arg("tol"));
     m.def("version", [] { return std::string(pamg_version()); });
 }
