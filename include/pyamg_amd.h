@@ -469,102 +469,117 @@ int pamg_matrix_destroy(pamg_matrix_t A);
  * per block info[5]=bytes resident in HBM info[6]=fwd GS levels (0 = not analysed)
  * info[7]=bwd GS levels */
 int pamg_matrix_info(pamg_matrix_t A, int64_t info[8]);
-/* tuning knobs (speed only: every setting computes the same bits).  key 0 = LDS entries per row
- * range, 2 = max rows per range (these
- * re-plan the operator); 3 = flow_cap: an order-exact sweep whose schedule averages <= flow_cap/16
- * row ranges per dependency level runs as ONE persistent single-workgroup launch (default 32);
- * 5 = scheduler of the scalar order-exact sweeps: 0 automatic (narrow -> single workgroup, else the
- * granular sweep), 1 one launch per dependency level, 2 granular sync-free sweep (one persistent
- * launch, element-level hand-off, no barriers), 3 single workgroup; block sweeps read 2 as "grid
- * with a barrier per level"; 6 = cap on the persistent grid (0 = automatic); 7 = granular sweep
- * inside one XCD's L2: 0 automatic (small operators), 1 always, 2 never; 8 = streaming flags of the
- * whole-operator kernels: bit 0 non-temporal loads of the operator stream, bit 1 XCD-aware
- * row-range order, bit 4 value codes staged by six chains per lane, bit 5 the value-code instantiation also on operators without
- * value codes; a value with bit 2 or 3 (the retired ablations, which computed wrong results) is PAMG_E_ARG (1, entries per lane, was
- * removed: only 2 was ever kept; 9, LDS-staged x windows, was retired in round 5: 4-7 % slower than the direct gather);
- * 5 also accepts 5 = TILED sweep (one persistent workgroup per contiguous chunk of rows; dependency chains
- * stay in LDS, only chunk-crossing edges use the global hand-off); 11 = record time stamps of the granular /
- * tiled sweep (diagnostics, pamg_matrix_gs_profile); 12 = tiles of the tiled sweep (0 = automatic),
- * 13 = its LDS ring slots (0 = automatic, else a power of two, 64..8192), 14 = its entries per step
- * (0 = automatic, <= 1020), 15 = let the automatic choice (key 5 = 0) prefer the tiled sweep, 16 = cap on the
- * steps resident in LDS per tile (0 = automatic), 17 = cap on the steps its loader keeps in flight (-1 = automatic),
- * 18 = tile shapes: 1 (default) pencils on three-band grid stencils, 0 contiguous chunks of the visit order always;
- * 19 = 16-bit windowed column stream of the whole-operator kernels (default 1; 0 = 32-bit columns);
- * 20 = entries per row range of the level schedules of the order-exact sweeps (0 = automatic: key 0's value, 512 where the
- * multi-XCD granular sweep runs SA-like rows; else 64..2048);
- * 21 = 8-bit value codes of the whole-operator kernels (default 1): an operator with at most 256 distinct values
- * (the stencils of pyamg.gallery: 2) streams one byte per value, the kernel looks the value up in an LDS copy of
- * the dictionary -- same bits, same products; needs key 19;
- * 22 = row-gather form of the whole-operator kernels on operators with value codes (default 1 there): lane = row, the j-th
- * entries of 64 consecutive rows in one gather instruction (coalesced on stencils), products summed in storage order in
- * registers; 0 = the LDS-staged kernel on the codes;
- * 23 = row-pattern form where plan_rowpat found a table (see pamg_matrix_row_patterns): 1 (default) the fastest form the rows
- * allow -- the row-MASK kernels when every list is the longest list with entries left out (a constant-coefficient stencil: one
- * mask byte per row, offsets and values are launch constants, no table, no prologue; on a 7-point lattice whose extents fit
- * 64 x 4 x kz tiles the lattice form csr_rowmask3d_kernel), else the table kernel --, 3 the table kernel (one row per lane)
- * always, 4 the linear row-mask kernel instead of the lattice form, 0 off (2, two consecutive rows per lane, measured 28 % slower --
- * profiles/r04_microbench_rowpat_two_rows_per_lane_slower.json -- and retired in round 5);
- * 31 = planes per lane of the lattice form (2 | 4 | 8, default 8); 32 = flags of the row-mask kernels (default 3): bit 0 (the
- * streams touched once -- mask, b, result -- nontemporal) is always on since round 5 and ignored, bit 1 plane-by-plane XCD order (XCD j takes the j-th eighth of
- * every plane), bit 2 XCD-contiguous eighths of the rows instead.
- * NOT speed-only -- 24 = ORDER of the row sums of the scalar Gauss-Seidel / SOR sweeps: 0 (default of a bare operator) =
- * order-exact, every sum runs in storage order with an IEEE division, results are the reference's bit for bit
- * (amg_core/relaxation.h:48-76,116-145,185-266); 1 = FAST order: the same sweep order over the rows (same dependency
- * DAG, same iterates in exact arithmetic), but L lanes of a wave share a row, add their products in parallel (DPP
- * butterfly) and finish with (b - sum) * (1 / a_ii) -- agrees with the reference to rounding (a few ulp per sweep), which
- * is what BASELINE's "residual norms within 1e-10" asks for; schedules the lane form cannot hold (rows with more than
- * 256 off-diagonal entries, padding above 4x) keep the exact kernels.  25 = lanes per row of the fast order (0 = automatic,
- * else 4|8|16|32|64), 26 = its persistent workgroups (0 = automatic), 27 = 1: the fast order also takes wide schedules
- * (>= 2048 rows per dependency level), which the tiled exact sweep keeps by default, 28 = flags of the fast order (bit 0, default
- * on: a wave that runs ahead of the sweep polls ONE gate operand instead of all its operands until the sweep is one
- * dependency level away; bit 3: the same in the line scan, off; bits 1, 2 retired with the slab form in round 5),
- * 30 = line-scan form of the fast order (default 1) where consecutive swept rows are coupled AND
- * enough lines run side by side to beat the lane form by the planner's estimate (3-D grids; not 2-D grids in natural order); 2 = wherever it applies.
- * 33 = MERGED fast order (round 6; f64 Gauss-Seidel): dependency levels of the sweep eliminated algebraically into one super-level at most -- 0 (default)
- * automatic (3 on levels above 131 072 rows, 6 below, off under 12 entries per row or 8 dependency levels), 1 never, 2..8; the sweep then pays one
- * hand-off per super-level; same iterates in exact arithmetic, another association in floating point; groups are closed early where a merged row would
- * exceed 512 operands (256 with two rows per wave) or its growth factor 1e3 (csrc/pamg_lanem_plan.h; pamg_matrix_lanem_info); 34 = its persistent waves
- * as tenths of the rows of an average super-level (default 40); 35 = its rows per wave: 1 (64 lanes per row), 2 (32 lanes per row, rows of a
- * super-level paired by length), 0 (default) = 2 on levels above 131 072 rows; 38 = its CLUSTER layout: 4 / 8 = up to that many rows of a
- * super-level, consecutive in row-index order, share a wave, which loads the union of their operands once and forms the row sums from LDS (static
- * chip-wide form only); 1 = off; 0 (default) = automatic: 8 on levels above 131 072 rows, where key 33's automatic choice is then 4.
- * 36 = unused dynamic LDS (bytes) added to the launches of the staged whole-operator kernel: caps its workgroups per CU (a measurement knob: on the SA-level
- * operators the instantiation choice of key 8 bit 5 already sits at the best occupancy, profiles/r06_microbench_sa_ops_lds_pad.json).
- * Key 8, bit 5 (round 6): an operator WITHOUT 8-bit value codes through the kernel instantiation that carries their paths (same arithmetic, another
- * instruction schedule; pamg_matrix_autotune times both).
- * 37 = fused symmetric sweep (default 1): a symmetric Gauss-Seidel sweep in fast order is ONE persistent launch (forward schedule, completion
- * barrier, backward schedule) where both schedules take the merged lane form or both the line form (f64); 0 = two directional launches.  Same bits.
- * 39 = ZERO-ITERATE plans (round 9): a symmetric sweep announced to start from x = 0 (pamg_matrix_gauss_seidel_x0, a cycle's pre-smoothing below the
- * finest level) runs the merged forward plan of tril(A), which also stores the numerators w_r = b_r - s_r, then the merged backward plan of triu(A)
- * with w as right-hand side -- half the operands per row, fused or as two launches alike; equal to the general plans in exact arithmetic, to rounding
- * in floating point.  0 (default) = automatic: pamg_solver_finalize builds them on every level below the finest whose pre-smoother takes the merged
- * form in both directions, a bare operator has none; 1 = off; 2 = on (a solver: the finest level too; a bare operator builds them at its first such
- * sweep outside a graph capture).  40 = their merge depth (2..16; 0 = automatic).
- * 41 = CORRECTION FORM of a solver's symmetric Gauss-Seidel smoothing steps that start from x != 0 (round 10: post-smoothing, the re-entries of W and F
- * cycles, iterations 2.. of a smoother): Gauss-Seidel is affine, sweep(x, b) = x + sweep(0, b - A x), so such a step runs as r = b - A x followed by the
- * launch announced from zero on the zero-iterate plans of key 39, whose backward half adds to x.  Equal to the direct sweep in exact arithmetic, to
- * rounding in floating point.  0 (default) = automatic: levels that hold the plans and have at least 16 384 rows; 1 = off; 2 = on wherever the plans
- * exist.  A bare operator's sweeps never take it (pamg_matrix_gauss_seidel_correction asks for it by name).
- * Returns PAMG_E_STATE while a solver holds the operator (captured graphs point into the plans). */
+/* Tuning knobs of an operator: pamg_matrix_tune(A, PAMG_TUNE_<NAME>, value).  They are speed only -- every setting computes the same
+ * bits -- except GS_ORDER.  PAMG_E_ARG for an unknown key or a value outside the key's range; PAMG_E_STATE while a solver holds the operator
+ * (captured graphs point into the plans and schedules these calls drop), except VAL8, ROWGATHER and ROWPAT, which are read at launch time
+ * only.  The numbers are part of the ABI and never change; the holes are retired knobs ("retired knobs"). */
+/* the whole-operator kernels (SpMV, residual, Jacobi, polynomial) */
+#define PAMG_TUNE_LDS_ENTRIES 0    /* 64..12288, stored as a multiple of 4; default 1536 (2048 with value codes): LDS entries per row range; re-plans the operator */
+#define PAMG_TUNE_MAX_ROWS 2       /* >= 1; default 1024: rows per row range at most; re-plans the operator */
+#define PAMG_TUNE_STREAM_FLAGS 8   /* 0..63 without bits 2, 3; default 0: bit 0 non-temporal loads of the operator stream, bit 1 XCD-aware row-range order,
+                                    * bit 4 value codes staged by six chains per lane, bit 5 the value-code instantiation also on operators without value
+                                    * codes (same arithmetic, another instruction schedule; pamg_matrix_autotune times both) */
+#define PAMG_TUNE_IDX16 19         /* 0 | non-zero; default 1: 16-bit windowed column stream instead of 32-bit columns */
+#define PAMG_TUNE_VAL8 21          /* 0 | non-zero; default 1: an operator with at most 256 distinct values (the stencils of pyamg.gallery: 2) streams one
+                                    * byte per value and looks it up in an LDS copy of the dictionary -- same bits, same products; needs IDX16 */
+#define PAMG_TUNE_ROWGATHER 22     /* 0 | non-zero; default 1 on operators with value codes: lane = row, the j-th entries of 64 consecutive rows in one
+                                    * gather, products summed in storage order in registers; 0 = the LDS-staged kernel on the codes */
+#define PAMG_TUNE_ROWPAT 23        /* 0 | 1 | 3 | 4; default 1: the row-pattern form where the operator has a table (pamg_matrix_row_patterns).  1 = the fastest
+                                    * form the rows allow: the row-MASK kernels when every list is the longest list with entries left out (a constant-
+                                    * coefficient stencil: one mask byte per row, offsets and values are launch constants; on a 7-point lattice whose
+                                    * extents fit 64 x 4 x kz tiles the lattice form), else the table kernel; 3 = the table kernel (one row per lane)
+                                    * always; 4 = the linear row-mask kernel instead of the lattice form; 0 = off */
+#define PAMG_TUNE_ROWMASK_KZ 31    /* 2 | 4 | 8; default 8: planes per lane of the lattice form */
+#define PAMG_TUNE_ROWMASK_FLAGS 32 /* 0..7; default 3: bit 0 ignored (the streams touched once are always non-temporal), bit 1 plane-by-plane XCD order
+                                    * (XCD j takes the j-th eighth of every plane), bit 2 XCD-contiguous eighths of the rows instead */
+#define PAMG_TUNE_LDS_PAD 36       /* 0..98304, stored as a multiple of 16; default 0: unused dynamic LDS (bytes) added to the launches of the staged
+                                    * kernel: caps its workgroups per CU (a measurement knob) */
+/* the order-exact Gauss-Seidel / SOR sweeps */
+#define PAMG_TUNE_FLOW_CAP 3       /* 0..256; default 32: a sweep whose schedule averages <= flow_cap / 16 row ranges per dependency level runs as ONE
+                                    * persistent single-workgroup launch */
+#define PAMG_TUNE_GS_MODE 5        /* 0..5; default 0: scheduler of the scalar sweeps.  0 = automatic (narrow -> single workgroup, else the granular
+                                    * sweep; tiles where they measured faster), 1 = one launch per dependency level, 2 = granular sync-free sweep (one
+                                    * persistent launch, element-level hand-off, no barriers), 3 = single workgroup, 5 = TILED sweep (one persistent
+                                    * workgroup per contiguous chunk of rows; dependency chains stay in LDS, only chunk-crossing edges use the global
+                                    * hand-off).  Block sweeps read 2 as "grid with a barrier per level".  (4 is accepted and selects nothing.) */
+#define PAMG_TUNE_GRAN_CAP 6       /* >= 0; default 0 = automatic: cap on the persistent grid of the granular sweep */
+#define PAMG_TUNE_GRAN_XCD 7       /* 0..2; default 0: granular sweep inside one XCD's L2 -- 0 = automatic (small operators), 1 = always, 2 = never */
+#define PAMG_TUNE_GS_PROF 11       /* 0 | non-zero; default 0: record time stamps of the granular / tiled / lane sweeps (pamg_matrix_gs_profile,
+                                    * pamg_matrix_lane_profile) */
+#define PAMG_TUNE_TILE_G 12        /* >= 0; default 0 = automatic: tiles of the tiled sweep */
+#define PAMG_TUNE_TILE_W 13        /* 0 | a power of two in 64..8192; default 0 = automatic: its LDS ring slots */
+#define PAMG_TUNE_TILE_CAP 14      /* 0..2048; default 0 = automatic: its entries per step */
+#define PAMG_TUNE_TILE_DEFAULT 15  /* 0 | non-zero; default 0: the automatic scheduler prefers the tiled sweep everywhere */
+#define PAMG_TUNE_TILE_D 16        /* 0..32; default 0 = automatic: cap on the steps resident in LDS per tile */
+#define PAMG_TUNE_TILE_Q 17        /* -1..4; default -1 = automatic: cap on the steps its loader keeps in flight */
+#define PAMG_TUNE_TILE_PART 18     /* 0 | 1; default 1: pencil tiles on three-band grid stencils; 0 = contiguous chunks of the visit order always */
+#define PAMG_TUNE_GS_CAP 20        /* 0 | 64..2048, stored as a multiple of 4; default 0 = automatic (LDS_ENTRIES, 512 where the multi-XCD granular sweep
+                                    * runs SA-like rows): entries per row range of the level schedules.  Read when a schedule is built */
+/* NOT speed-only: the ORDER of the row sums of the scalar Gauss-Seidel / SOR sweeps */
+#define PAMG_TUNE_GS_ORDER 24      /* 0 | 1; default 0 on a bare operator.  0 = order-exact: every sum runs in storage order with an IEEE division, results are
+                                    * the reference's bit for bit (amg_core/relaxation.h:48-76,116-145,185-266).  1 = FAST order: the same sweep order over
+                                    * the rows (same dependency DAG, same iterates in exact arithmetic), but the lanes of a wave share a row, add their
+                                    * products in parallel and finish with (b - sum) * (1 / a_ii): agrees with the reference to rounding (a few ulp per
+                                    * sweep); schedules the lane form cannot hold (rows with more than 256 off-diagonal entries, padding above 4x) keep
+                                    * the exact kernels */
+/* the fast order */
+#define PAMG_TUNE_LANE_L 25        /* 0 | 4 | 8 | 16 | 32 | 64; default 0 = automatic: lanes per row */
+#define PAMG_TUNE_LANE_G 26        /* >= 0; default 0 = automatic: persistent workgroups */
+#define PAMG_TUNE_LANE_WIDE 27     /* 0 | 1; default 0: 1 = the fast order also takes wide schedules (>= 2048 rows per dependency level), which the tiled
+                                    * exact sweep keeps otherwise */
+#define PAMG_TUNE_LANE_FLAGS 28    /* 0..15 without bits 1, 2; default 1: bit 0 a wave that runs ahead of the sweep polls ONE gate operand instead of all
+                                    * its operands until the sweep is one dependency level away, bit 3 the same in the line scan */
+#define PAMG_TUNE_LINE_SCAN 30     /* 0..2; default 1: line-scan form where consecutive swept rows are coupled AND enough lines run side by side to beat
+                                    * the lane form by the planner's estimate (3-D grids; not 2-D grids in natural order); 2 = wherever it applies;
+                                    * 0 = off */
+#define PAMG_TUNE_LANE_MERGE 33    /* 0..8; default 0: MERGED fast order (f64 Gauss-Seidel), that many dependency levels at most eliminated algebraically
+                                    * into one super-level, for which the sweep pays one hand-off.  0 = automatic (3 on levels above 131 072 rows, 6
+                                    * below, off under 12 entries per row or 8 dependency levels), 1 = never.  Same iterates in exact arithmetic, another
+                                    * association in floating point; groups are closed early where a merged row would exceed 512 operands (256 with two
+                                    * rows per wave) or its growth factor 1e3 (pamg_matrix_lanem_info) */
+#define PAMG_TUNE_LANEM_AHEAD 34   /* 1..400; default 40: persistent waves of the merged form, as tenths of the rows of an average super-level */
+#define PAMG_TUNE_LANEM_RPW 35     /* 0..2; default 0 = 2 on levels above 131 072 rows: rows per wave of the merged form -- 1 (64 lanes per row), 2 (32
+                                    * lanes per row, rows of a super-level paired by length) */
+#define PAMG_TUNE_SYM_FUSED 37     /* 0 | 1; default 1: a symmetric sweep in fast order is ONE persistent launch (forward schedule, completion barrier,
+                                    * backward schedule) where both schedules take the merged form or both the line form (f64); 0 = two directional
+                                    * launches.  Same bits */
+#define PAMG_TUNE_LANEM_CLUSTER 38 /* 0 | 1 | 4 | 8; default 0: CLUSTER layout of the merged form -- up to 4 / 8 rows of a super-level, consecutive in
+                                    * row-index order, share a wave, which loads the union of their operands once and forms the row sums from LDS (static
+                                    * chip-wide form only); 1 = off; 0 = automatic: 8 on levels above 131 072 rows, where LANE_MERGE's automatic choice
+                                    * is then 4 */
+#define PAMG_TUNE_ZERO_PLANS 39    /* 0..2; default 0: ZERO-ITERATE plans.  A symmetric sweep announced to start from x = 0 (pamg_matrix_gauss_seidel_x0, a
+                                    * cycle's pre-smoothing below the finest level) runs the merged forward plan of tril(A), which also stores the
+                                    * numerators w_r = b_r - s_r, then the merged backward plan of triu(A) with w as right-hand side: half the operands
+                                    * per row, fused or as two launches alike; equal to the general plans in exact arithmetic, to rounding in floating
+                                    * point.  0 = automatic (pamg_solver_finalize builds them on every level below the finest whose pre-smoother takes
+                                    * the merged form in both directions, a bare operator has none), 1 = off, 2 = on (a solver: the finest level too; a
+                                    * bare operator builds them at its first such sweep outside a graph capture) */
+#define PAMG_TUNE_ZERO_MERGE 40    /* 0 | 2..16; default 0 = automatic: merge depth of the zero-iterate plans */
+#define PAMG_TUNE_GS_CORRECTION 41 /* 0..2; default 0: CORRECTION FORM of a solver's symmetric Gauss-Seidel steps that start from x != 0 (post-smoothing, the
+                                    * re-entries of W and F cycles, iterations 2.. of a smoother).  Gauss-Seidel is affine, sweep(x, b) = x + sweep(0,
+                                    * b - A x), so such a step runs as r = b - A x followed by the launch announced from zero on the zero-iterate plans,
+                                    * whose backward half adds to x; equal to the direct sweep in exact arithmetic, to rounding in floating point.
+                                    * 0 = automatic (levels that hold the plans and have at least 16 384 rows), 1 = off, 2 = on wherever the plans
+                                    * exist.  A bare operator's sweeps never take it (pamg_matrix_gauss_seidel_correction asks for it by name) */
 int pamg_matrix_tune(pamg_matrix_t A, int key, int value);
 /* n_values = size of the operator's value dictionary when the whole-operator kernels stream 8-bit value codes
- * (tune key 21), 0 when they stream the values themselves. */
+ * (PAMG_TUNE_VAL8), 0 when they stream the values themselves. */
 int pamg_matrix_value_codes(pamg_matrix_t A, int *n_values);
-/* n_patterns = size of the operator's row-pattern table when the whole-operator kernels run in the row-pattern form (tune
- * key 23: square operators with value codes whose rows are mostly one of <= 255 lists of (column - row, value) pairs --
+/* n_patterns = size of the operator's row-pattern table when the whole-operator kernels run in the row-pattern form
+ * (PAMG_TUNE_ROWPAT: square operators with value codes whose rows are mostly one of <= 255 lists of (column - row, value) pairs --
  * constant-coefficient stencils; one byte per such row instead of the row's codes), 0 otherwise. */
 int pamg_matrix_row_patterns(pamg_matrix_t A, int *n_patterns);
-/* The row-mask form of the row patterns (tune key 23 = 1 or 4 where every list is one list with entries left out):
+/* The row-mask form of the row patterns (PAMG_TUNE_ROWPAT = 1 or 4 where every list is one list with entries left out):
  * info[0] entries of that list (0 = the operator has no mask form, or another form is selected), [1] rows that walk the CSR
  * arrays, [2] 1 = the lattice kernel runs (64 x 4 x kz tiles), [3] rows per lattice line, [4] rows per plane, [5] planes
- * per lane (key 31), [6] flags (key 32), [7] workgroups launched per whole-operator kernel. */
+ * per lane (PAMG_TUNE_ROWMASK_KZ), [6] flags (PAMG_TUNE_ROWMASK_FLAGS), [7] workgroups launched per whole-operator kernel. */
 int pamg_matrix_row_masks(pamg_matrix_t A, long long info[8]);
-/* Pick the LDS window (key 0) and streaming flags (key 8) of the whole-operator kernels by timing
+/* Pick the LDS window (PAMG_TUNE_LDS_ENTRIES) and streaming flags (PAMG_TUNE_STREAM_FLAGS) of the whole-operator kernels by timing
  * y = A x on the device with a few candidates (results are bit-identical for every choice; this
  * is speed only).  allow_cap = 0 keeps the LDS window (level schedules depend on it).  Operators
  * below 4M stored entries are left alone.  Synchronises. */
 int pamg_matrix_autotune(pamg_matrix_t A, int allow_cap);
-/* Diagnostics of the granular sweep (tune key 11): per row range of schedule `which` (0 forward,
+/* Diagnostics of the granular sweep (PAMG_TUNE_GS_PROF): per row range of schedule `which` (0 forward,
  * 1 backward) eight 64-bit words {arrival, gate open, polled, staged, finished (wall clock, 10 ns),
  * XCD id, workgroup id, dependency level}.  out == NULL: only *count.  Synchronises. */
 int pamg_matrix_gs_profile(pamg_matrix_t A, int which, long long *out, int64_t capacity, int64_t *count);
@@ -573,41 +588,41 @@ int pamg_matrix_gs_profile(pamg_matrix_t A, int which, long long *out, int64_t c
  * flight << 24, steps, early entries served from LDS, early entries served by the global hand-off, publishing
  * rows, LDS bytes}; all zero when that schedule has no tile plan. */
 int pamg_matrix_tile_info(pamg_matrix_t A, int which, int64_t info[8]);
-/* Layout of the lane-parallel fast-order sweep (tune key 24) for schedule `which`: {lanes per row, entry slots per lane,
+/* Layout of the lane-parallel fast-order sweep (PAMG_TUNE_GS_ORDER) for schedule `which`: {lanes per row, entry slots per lane,
  * groups (one wave each), entry slots, entries that wait for a new value, workgroups of the last launch (the one-XCD form
- * launches 8x what stays), groups of the widest dependency level, bytes}; all zero when that schedule has no lane layout.  pamg_matrix_lane_profile: with tune
- * key 11, per group four 64-bit words {start, last operand seen, published (wall clock, 10 ns), XCD | workgroup << 4}.
+ * launches 8x what stays), groups of the widest dependency level, bytes}; all zero when that schedule has no lane layout.  pamg_matrix_lane_profile: with
+ * PAMG_TUNE_GS_PROF, per group four 64-bit words {start, last operand seen, published (wall clock, 10 ns), XCD | workgroup << 4}.
  * Block operators (bs > 1): the same fields for the block-row lane form of pamg_matrix_block_gauss_seidel (csrc/pamg_blane.hip: lanes per BLOCK row,
  * BLOCKS per lane, block slots, blocks that wait for a new x_j). */
 int pamg_matrix_lane_info(pamg_matrix_t A, int which, int64_t info[8]);
-/* Plan of the MERGED lane-parallel sweep (round 6; tune key 33: dependency levels eliminated into one super-level at most -- 0 automatic, 1 never;
- * key 34: waves per average super-level x 10; csrc/pamg_lanem_plan.h) for schedule `which`: {super-levels (hand-offs of this form), dependency
+/* Plan of the MERGED lane-parallel sweep (round 6; PAMG_TUNE_LANE_MERGE: dependency levels eliminated into one super-level at most -- 0 automatic, 1 never;
+ * PAMG_TUNE_LANEM_AHEAD: waves per average super-level x 10; csrc/pamg_lanem_plan.h) for schedule `which`: {super-levels (hand-offs of this form), dependency
  * levels (hand-offs of the unmerged form), rows, 64-slot operand units, operands polled from earlier super-levels, operands read from the snapshot
  * of x, operands read from b, longest merged row, levels merged at most, groups closed early by row length, closed early by the growth bound,
  * workgroups of the last launch}; *growth (may be NULL) = the largest accepted growth factor sum_r |T_ir| |a_ii|.  All zero when the schedule
  * runs unmerged.  The merged sweep computes the reference's Gauss-Seidel iterates (amg_core::gauss_seidel, relaxation.h:48-76) in another
  * association: equal in exact arithmetic, to rounding in floating point.
- * info[12..19] (round 8): rows per wave of the CLUSTER layout (tune key 38; 0 = the row / pair layout), groups (one wave's work item: a row, a pair
+ * info[12..19] (round 8): rows per wave of the CLUSTER layout (PAMG_TUNE_LANEM_CLUSTER; 0 = the row / pair layout), groups (one wave's work item: a row, a pair
  * or a cluster), padded slots (64 x info[3]; over info[4] + info[5] + info[6] it is the layout's padding factor), 64-code units of unique operands,
  * unique operands polled / read from the snapshot / read from b and distinct 64-byte lines of the unique polled operands, each counted per group and
  * summed (what a wave really loads where the rows of a group share operands; the row / pair layouts share nothing: their counts repeat
  * info[4..6] and no lines are counted).
- * which = 4 / 5 (round 9): the operator's zero-iterate plans (tune key 39), the forward plan of tril(A) / the backward plan of triu(A). */
+ * which = 4 / 5 (round 9): the operator's zero-iterate plans (PAMG_TUNE_ZERO_PLANS), the forward plan of tril(A) / the backward plan of triu(A). */
 int pamg_matrix_lanem_info(pamg_matrix_t A, int which, int64_t info[20], double *growth);
-/* Fast order (tune key 24 = 1) of the BSR POINT sweep (amg_core::bsr_gauss_seidel, relaxation.h:185-266: what relaxation.gauss_seidel runs on a
+/* Fast order (PAMG_TUNE_GS_ORDER = 1) of the BSR POINT sweep (amg_core::bsr_gauss_seidel, relaxation.h:185-266: what relaxation.gauss_seidel runs on a
  * block operator): the same rows in the same order are the scalar Gauss-Seidel sweep of the flattened operator, so the block operator builds a
  * scalar CSR twin of itself with its schedules and sweeps it in the lane-parallel / merged / line-scan form (same iterates to rounding, like every
  * fast-order sweep; order 'exact' keeps the block kernels and the reference's bits).  state: 0 = no twin (exact order, or not swept yet),
  * 1 = the twin carries the point sweeps, 2 = no fast-order form fits the flattened rows: the exact block kernels sweep. */
 int pamg_matrix_point_twin(pamg_matrix_t A, int *state);
-/* First row (in the merged plan's order) of every super-level, nsuper + 1 values; out == NULL: only *count.  With tune key 11 the merged sweep records per row
+/* First row (in the merged plan's order) of every super-level, nsuper + 1 values; out == NULL: only *count.  With PAMG_TUNE_GS_PROF the merged sweep records per row
  * {arrival | polling rounds << 52, operand slots arrived, all operands present, published} (pamg_matrix_lane_profile, 10 ns ticks). */
 int pamg_matrix_lanem_levels(pamg_matrix_t A, int which, int64_t *out, int64_t capacity, int64_t *count);
-/* Layout of the lane-parallel fast-order Kaczmarz sweep (tune key 24 = 1 on the operator handed to pamg_matrix_kaczmarz; csrc/pamg_kz_plan.h)
+/* Layout of the lane-parallel fast-order Kaczmarz sweep (PAMG_TUNE_GS_ORDER = 1 on the operator handed to pamg_matrix_kaczmarz; csrc/pamg_kz_plan.h)
  * of the operator's `which`-th cached line schedule (0 .. 3, in the order the sweep ranges were first used): {lanes per line, entry slots per
  * lane, groups, dependency levels, groups of the widest level, workgroups of the last launch, bytes, 0}; all zero when that schedule has none. */
 int pamg_matrix_kz_info(pamg_matrix_t A, int which, int64_t info[8]);
-/* Layout of the line-scan fast-order sweep (tune keys 24 / 30: banded operators swept over consecutive rows, i.e. grid
+/* Layout of the line-scan fast-order sweep (PAMG_TUNE_GS_ORDER / PAMG_TUNE_LINE_SCAN: banded operators swept over consecutive rows, i.e. grid
  * stencils in their natural order -- a run of rows each coupled to its predecessor is a first-order linear recurrence, finished
  * 64 rows at a time by a scan) for schedule `which`: {entry slots per row, chunks (<= 64 rows, one wave step each), lines (chained
  * chunks, one wave each), levels of the line graph, entries that wait for a new value, workgroups of the last launch, lines of
@@ -682,16 +697,16 @@ int pamg_matrix_gauss_seidel(pamg_matrix_t A, void *x, const void *b, int sweep,
  * forward half of a fused symmetric sweep then skips the operands that would multiply zero -- the same bits for finite data. */
 int pamg_matrix_gauss_seidel_x0(pamg_matrix_t A, void *x, const void *b, int sweep, double omega,
                                 int iterations, int x_is_zero, pamg_stream_t s);
-/* The fused symmetric sweep (tune key 37): {fused launches enqueued or captured so far, those with x known to be zero, form of the last one
+/* The fused symmetric sweep (PAMG_TUNE_SYM_FUSED): {fused launches enqueued or captured so far, those with x known to be zero, form of the last one
  * (1 merged lanes across the chip, 2 lines, 3 merged lanes inside one XCD, 0 none yet), the workgroups of the last one on the general plans (a launch on
- * the zero-iterate plans reports its own in pamg_matrix_lanem_info(which = 4)), tune key 37, entries of the forward hand-off buffer that are NOT sentinels (0 between
+ * the zero-iterate plans reports its own in pamg_matrix_lanem_info(which = 4)), PAMG_TUNE_SYM_FUSED, entries of the forward hand-off buffer that are NOT sentinels (0 between
  * launches; -1: no buffers), counters that are not zero (0 between launches), symmetric sweeps (fused or as two launches) that ran on the
- * zero-iterate plans (tune key 39) -- announced from zero, or in correction form --, symmetric smoothing steps that ran in correction form (tune key 41;
+ * zero-iterate plans (PAMG_TUNE_ZERO_PLANS) -- announced from zero, or in correction form --, symmetric smoothing steps that ran in correction form (PAMG_TUNE_GS_CORRECTION;
  * each is also counted as a sweep announced from zero on the zero-iterate plans: it is one, on the residual)}.  Synchronises the device. */
 int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[9]);
-/* One symmetric Gauss-Seidel sweep per iteration in CORRECTION FORM, whatever tune key 41 says: r = b - A x, then x += sweep(0, r) on the operator's
+/* One symmetric Gauss-Seidel sweep per iteration in CORRECTION FORM, whatever PAMG_TUNE_GS_CORRECTION says: r = b - A x, then x += sweep(0, r) on the operator's
  * zero-iterate plans (r: DEVICE scratch vector of the operator's size, overwritten).  PAMG_E_UNSUPPORTED where the operator holds no such plans (a bare
- * operator with key 39 = 2 builds them here, outside a graph capture). */
+ * operator with PAMG_TUNE_ZERO_PLANS = 2 builds them here, outside a graph capture). */
 int pamg_matrix_gauss_seidel_correction(pamg_matrix_t A, void *x, const void *b, void *r, int iterations, pamg_stream_t s);
 /* relaxation.polynomial (relaxation.py:585-659); coeffs is a HOST array; x_is_zero != 0
  * asserts x == 0 on entry (the reference tests norm(x) == 0, relaxation.py:649). */

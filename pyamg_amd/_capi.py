@@ -143,7 +143,7 @@ def _declare(lib):
     f("pamg_matrix_create", P(_vp), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp)
     f("pamg_matrix_destroy", _vp)
     f("pamg_matrix_info", _vp, P(C.c_int64))
-    f("pamg_matrix_tune", _vp, _i, _i)                # keys: include/pyamg_amd.h (39 = zero-iterate plans: 0 automatic / 1 off / 2 on, 40 = their merge depth)
+    f("pamg_matrix_tune", _vp, _i, _i)                # keys: PAMG_TUNE_* of include/pyamg_amd.h = multilevel.TUNE_KEYS
     f("pamg_matrix_value_codes", _vp, P(C.c_int))
     f("pamg_matrix_row_patterns", _vp, P(C.c_int))
     f("pamg_matrix_row_masks", _vp, P(C.c_longlong))

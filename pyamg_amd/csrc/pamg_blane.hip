@@ -42,7 +42,7 @@ struct BlaneArgs {
     double *xs;            // hand-off buffer, sentinel-filled
     const double *b, *Dinv, *zero;
     unsigned *err, *ticket;
-    long long *prof;       // nullptr or [ngroups][4] time stamps (tune key 11): group started, last operand seen, published, XCD | workgroup << 4
+    long long *prof;       // nullptr or [ngroups][4] time stamps (PAMG_TUNE_GS_PROF): group started, last operand seen, published, XCD | workgroup << 4
     int ngroups, nidle;
 };
 

@@ -111,7 +111,7 @@ static int block_sweep_t(pamg_matrix_s *A, GsSchedule *g, int kind, const void *
         return (int)hipGetLastError();
     }
     // small block levels (the iterate fits the LDS next to the range's products): one workgroup, x and b in LDS, the next range's
-    // blocks prefetched -- bit-identical to the kernels below (tune key 5 = 3 keeps bsr_flow_kernel for comparison)
+    // blocks prefetched -- bit-identical to the kernels below (PAMG_TUNE_GS_MODE = 3 keeps bsr_flow_kernel for comparison)
     if (single && A->gs_mode == 0 && A->R <= MAXBS) {
         const int64_t n = A->nrows;
         const size_t need = (size_t)(2 * n + r.capv + SMALL_THREADS) * ts + 64;

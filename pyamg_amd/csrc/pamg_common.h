@@ -134,7 +134,7 @@ struct TileSched {
     int G = 0, W = 0, NCH = 1, NV = 1, wide = 0, xo = 0, D = 0, Q = 0, nsteps = 0, lds = 0;   // wide: kernel variant (0 = small gather lists, several workgroups per CU allowed)
     unsigned char *d_blocks = nullptr;
     int *d_tile_step = nullptr;
-    long long *d_prof = nullptr;     // [nsteps][4] diagnostics (tune key 11)
+    long long *d_prof = nullptr;     // [nsteps][4] diagnostics (PAMG_TUNE_GS_PROF)
     int64_t n_local = 0, n_global = 0, n_publish = 0, max_step_entries = 0;
     size_t bytes = 0;
 };
@@ -150,7 +150,7 @@ struct LineSchedule {
     void *d_ea = nullptr;            //   offset and a dense slab of its first KZ entries (indices / values), schedule order
     std::vector<int> level_ptr;      // [nlevels+1]
     size_t bytes = 0;
-    struct KzLaneSched *kzl = nullptr; // lane-parallel fast-order form of the sweep (pamg_kz_plan.h / pamg_kz.hip), built with the schedule when tune key 24 = 1
+    struct KzLaneSched *kzl = nullptr; // lane-parallel fast-order form of the sweep (pamg_kz_plan.h / pamg_kz.hip), built with the schedule when PAMG_TUNE_GS_ORDER = 1
     bool kzl_unfit = false;          // its planner declined (lines too long, an index twice in a line, not f64)
 };
 
@@ -181,12 +181,12 @@ struct pamg_matrix_s {
     int flow_cap = 32;               // single-workgroup persistent sweep when a schedule averages <= flow_cap/16 row ranges per level
     unsigned short *d_Aj16 = nullptr; // column ids of the scalar view as 16-bit window codes (csr_stream_kernel reads 2 instead of 4 bytes per entry)
     int4 *d_wbase = nullptr;         //   window bases per row range; both null when some range needs more than four 16 K-column windows
-    int use_idx16 = 1;               // tune key 19
+    int use_idx16 = 1;               // PAMG_TUNE_IDX16
     unsigned char *d_Ax8 = nullptr;  // values of the scalar view as 8-bit codes into d_vdict: operators with <= 256 distinct values (stencils)
     void *d_vdict = nullptr;         //   stream 1 instead of 8 bytes per value; needs the 16-bit column stream; null otherwise
     int nvdict = 0;
-    int use_val8 = 1;                // tune key 21
-    int use_rowg = 0;                // tune key 22: row-gather form of the whole-operator kernels (value-code operators; set with the codes)
+    int use_val8 = 1;                // PAMG_TUNE_VAL8
+    int use_rowg = 0;                // PAMG_TUNE_ROWGATHER: row-gather form of the whole-operator kernels (value-code operators; set with the codes)
     unsigned char *d_pid = nullptr;  // row patterns (plan_rowpat): list number per row, 255 = walk the row through the code arrays
     void *d_ptab = nullptr;          //   [256] lengths | [npat * pat_lmax] column offsets | [npat * pat_lmax] values
     int npat = 0, pat_lmax = 0;
@@ -196,10 +196,10 @@ struct pamg_matrix_s {
     long long rm_walked = 0;
     int rowmask_kz = 8;              // planes per lane of csr_rowmask3d_kernel (2, 4, 8)
     int rowmask_flags = 3;           // row-mask kernels: (bit 0: nontemporal b / mask / result -- always on since round 5, ignored) bit 1 plane-by-plane XCD order, bit 2 XCD-contiguous eighths
-    int use_rowpat = 1;              // tune key 23: 0 off, 1 the row-mask kernels where the operator has the form, else the table kernel (default), 3 the table kernel always, 4 the linear row-mask kernel instead of the lattice form
+    int use_rowpat = 1;              // PAMG_TUNE_ROWPAT: 0 off, 1 the row-mask kernels where the operator has the form, else the table kernel (default), 3 the table kernel always, 4 the linear row-mask kernel instead of the lattice form
     int cap_from_val8 = 0;           // cap was raised to 2048 because the operator streams value codes (level schedules keep 1536)
     int stream_flags = 0;            // StreamArgs::flags for the whole-operator launches
-    int lds_pad = 0;                 // extra (unused) dynamic LDS of the staged whole-operator kernel: fewer workgroups per CU   (tune key 36, autotune)
+    int lds_pad = 0;                 // extra (unused) dynamic LDS of the staged whole-operator kernel: fewer workgroups per CU   (PAMG_TUNE_LDS_PAD, autotune)
     int gran_xcd = 0;                // granular sweep inside one XCD's L2: 0 auto (small operators), 1 always, 2 never
     int gran_cap = 0;                // granular sweep: cap on the persistent grid (0 = auto)
     int gs_mode = 0;                 // scalar sweep scheduler: 0 auto, 1 one launch per level, 2 granular, 3 single workgroup, 5 tiled
@@ -208,21 +208,21 @@ struct pamg_matrix_s {
     int tile_cap = 0;                // tiled sweep: scheduled entries per step (0 = auto)
     int tile_D = 0, tile_Q = -1;     // tiled sweep: LDS slots per tile / steps in flight behind the landed mark (0 / -1 = auto)
     int tile_part = 1;               // tiled sweep: 1 = pencil tiles when the operator is a three-band grid stencil, 0 = contiguous chunks always
-    bool tile_default = false;       // auto mode (gs_mode 0) prefers the tiled sweep everywhere (default: only where it measured faster)
+    int tile_default = 0;            // auto mode (gs_mode 0) prefers the tiled sweep everywhere (default: only where it measured faster)
     int max_row_len = 0;             // longest row of the scalar view
     int borrowed = 0;                // solvers holding this operator (tuning is refused while > 0: captured graphs point into the schedules)
-    int gs_prof = 0;                 // granular sweep: record per-range time stamps (tune key 11, diagnostics)
-    int gs_order = 0;                // tune key 24: 0 = order-exact row sums (bit-identical to the reference), 1 = fast order: lane-parallel row
+    int gs_prof = 0;                 // granular sweep: record per-range time stamps (PAMG_TUNE_GS_PROF, diagnostics)
+    int gs_order = 0;                // PAMG_TUNE_GS_ORDER: 0 = order-exact row sums (bit-identical to the reference), 1 = fast order: lane-parallel row
                                      //   sums and multiplication by 1/a_ii (same sweep order; agrees to rounding) where the schedule fits that form
-    int lane_L = 0, lane_G = 0;      // fast order: lanes per row (0 = automatic) / persistent workgroups (0 = automatic)   (tune keys 25, 26)
-    int lane_flags = 1;              // fast order: bit 0 = gate operand (a wave that runs ahead polls one value instead of all its operands), bit 3 = gate in the line scan   (tune key 28)
-    int line_scan = 1;               // fast order: line-scan sweep where consecutive rows are coupled (grid stencils), tried before the lane form   (tune key 30)
-    int lane_merge = 0;              // fast order: dependency levels merged into one super-level at most (0 = automatic, 1 = never, 2..8)   (tune key 33)
-    int lanem_rpw = 0;               // merged form: rows per wave (0 = automatic: 2 on levels above 131 072 rows, 1 below)   (tune key 35)
-    int lanem_cluster = 0;           // merged form: cluster layout, rows of a super-level per wave sharing their operands (4 / 8; 1 = off; 0 = automatic: 8 on levels above 131 072 rows)   (tune key 38)
-    int lanem_ahead10 = 40;          // merged form: waves launched = this / 10 x the rows of an average super-level   (tune key 34)
-    int lane_wide = 0;               // fast order on wide schedules (>= 2048 rows per dependency level): 0 = the tiled exact sweep keeps them, 1 = lane form   (tune key 27)
-    int gs_cap = 0;                  // entries per row range of the level schedules (tune key 20; 0 = automatic: `cap`, 512 on the multi-XCD granular sweep of SA-like rows)
+    int lane_L = 0, lane_G = 0;      // fast order: lanes per row (0 = automatic) / persistent workgroups (0 = automatic)   (PAMG_TUNE_LANE_L, PAMG_TUNE_LANE_G)
+    int lane_flags = 1;              // fast order: bit 0 = gate operand (a wave that runs ahead polls one value instead of all its operands), bit 3 = gate in the line scan   (PAMG_TUNE_LANE_FLAGS)
+    int line_scan = 1;               // fast order: line-scan sweep where consecutive rows are coupled (grid stencils), tried before the lane form   (PAMG_TUNE_LINE_SCAN)
+    int lane_merge = 0;              // fast order: dependency levels merged into one super-level at most (0 = automatic, 1 = never, 2..8)   (PAMG_TUNE_LANE_MERGE)
+    int lanem_rpw = 0;               // merged form: rows per wave (0 = automatic: 2 on levels above 131 072 rows, 1 below)   (PAMG_TUNE_LANEM_RPW)
+    int lanem_cluster = 0;           // merged form: cluster layout, rows of a super-level per wave sharing their operands (4 / 8; 1 = off; 0 = automatic: 8 on levels above 131 072 rows)   (PAMG_TUNE_LANEM_CLUSTER)
+    int lanem_ahead10 = 40;          // merged form: waves launched = this / 10 x the rows of an average super-level   (PAMG_TUNE_LANEM_AHEAD)
+    int lane_wide = 0;               // fast order on wide schedules (>= 2048 rows per dependency level): 0 = the tiled exact sweep keeps them, 1 = lane form   (PAMG_TUNE_LANE_WIDE)
+    int gs_cap = 0;                  // entries per row range of the level schedules (PAMG_TUNE_GS_CAP; 0 = automatic: `cap`, 512 on the multi-XCD granular sweep of SA-like rows)
     int nblk = 0;
     int *d_part[2] = {nullptr, nullptr};   // row shards (pamg_dist.hip): row ranges that read owned columns only / that read the halo
     int npart[2] = {0, 0};
@@ -239,7 +239,7 @@ struct pamg_matrix_s {
     pamg::LineSchedule *ls[4] = {nullptr, nullptr, nullptr, nullptr};  // Kaczmarz sweeps over this operator's rows
     // fused symmetric sweep (forward and backward schedule in ONE launch; pamg_lane.hip / pamg_line.hip): the operator's own pair of
     // hand-off buffers and counters.  Between launches d_sym_hf[parity] is all sentinels, the other two hold anything, the counters are zero.
-    int sym_fused = 1;               // tune key 37: 1 = a symmetric Gauss-Seidel sweep is one launch where both schedules take the merged or the line form, 0 = two launches
+    int sym_fused = 1;               // PAMG_TUNE_SYM_FUSED: 1 = a symmetric Gauss-Seidel sweep is one launch where both schedules take the merged or the line form, 0 = two launches
     void *d_sym_hf[2] = {nullptr, nullptr}, *d_sym_hb = nullptr;
     unsigned *d_sym_sync = nullptr;  // [0] finished groups of phase 1, [1] workgroups that left, [2] / [3] tickets of phase 1 / 2, [4] home XCD + 1, [5] parity: the forward buffer of the next launch
     int sym_cap = 0;                 // co-resident workgroups per CU of the fused kernel (queried once per kernel)
@@ -253,14 +253,14 @@ struct pamg_matrix_s {
     long long sym_launches = 0, sym_zero_launches = 0;   // fused launches enqueued or captured / those with x known to be zero
     // zero-iterate plans (pamg_lane.hip): merged plans of tril(A) forward / triu(A) backward for symmetric sweeps that start from x = 0, and the
     // vector of numerators the forward half hands to the backward half
-    int zero_plans = 0;              // tune key 39: 0 = automatic (a solver builds them on the levels below its finest; a bare operator has none), 1 = off, 2 = on
-    int zero_merge = 0;              // tune key 40: dependency levels merged per super-level in those plans (0 = automatic, 2..16)
+    int zero_plans = 0;              // PAMG_TUNE_ZERO_PLANS: 0 = automatic (a solver builds them on the levels below its finest; a bare operator has none), 1 = off, 2 = on
+    int zero_merge = 0;              // PAMG_TUNE_ZERO_MERGE: dependency levels merged per super-level in those plans (0 = automatic, 2..16)
     struct pamg::LaneMSched *zplan[2] = {nullptr, nullptr};
     void *d_zw = nullptr;
     size_t zero_bytes = 0;           // what the plans and d_zw added to `bytes`
     long long zero_plan_launches = 0;   // symmetric sweeps (fused or as two launches) that ran on the zero-iterate plans: announced from x = 0, or in correction form
     // correction form of a symmetric sweep from x != 0 (a solver's cycle driver): r = b - A x, then x += sweep(0, r) on the zero-iterate plans
-    int gs_correction = 0;           // tune key 41: 0 = automatic (levels of at least GS_CORRECTION_MIN_ROWS rows), 1 = off, 2 = on wherever the plans exist
+    int gs_correction = 0;           // PAMG_TUNE_GS_CORRECTION: 0 = automatic (levels of at least GS_CORRECTION_MIN_ROWS rows), 1 = off, 2 = on wherever the plans exist
     long long correction_launches = 0;  // symmetric smoothing steps that ran in correction form (fused or as two launches)
     size_t bytes = 0;
 };
@@ -397,10 +397,10 @@ int ensure_zero_parts(pamg_matrix_s *A, bool build);   // pamg_matrix.hip: compl
 void matrix_drop_zero_plans(pamg_matrix_s *A);
 int gs_sweep_zero_pair(pamg_matrix_s *A, void *x, const void *b, hipStream_t s, bool *ran);   // symmetric sweep from x = 0 as two launches on the zero-iterate plans
 // a symmetric sweep from x != 0 in correction form: r = b - A x (r: a scratch vector of the operator's size), then x += sweep(0, r) on the zero-iterate
-// plans, fused or as two launches.  *ran = false: not applicable (no plans, switched off by tune key 41, or a level below the automatic threshold
+// plans, fused or as two launches.  *ran = false: not applicable (no plans, switched off by PAMG_TUNE_GS_CORRECTION, or a level below the automatic threshold
 // unless `force`) -- nothing was enqueued
 int gs_sweep_correction(pamg_matrix_s *A, void *x, const void *b, void *r, bool force, hipStream_t s, bool *ran);
-// tune key 41 = 0: the correction form runs on levels of at least this many rows (the two extra small launches cost a small level more than the
+// PAMG_TUNE_GS_CORRECTION = 0: the correction form runs on levels of at least this many rows (the two extra small launches cost a small level more than the
 // triangular plans save).  A placeholder from round 9's kernel times until tools/microbench_gs_correction.py has been run
 constexpr int64_t GS_CORRECTION_MIN_ROWS = 16384;
 int sym_fill_sentinels(void *p, int64_t n);      // n f64 sentinels on the null stream, synchronised

@@ -303,7 +303,7 @@ struct LaneMArgs {
     unsigned *err;
     unsigned *ticket;
     int ngroups, nidle, use_gate;
-    long long *prof;       // nullptr or [ngroups][4] time stamps (tune key 11; the unpipelined kernel, static form)
+    long long *prof;       // nullptr or [ngroups][4] time stamps (PAMG_TUNE_GS_PROF; the unpipelined kernel, static form)
     const unsigned short *sidx;   // cluster layout only: slot codes, rows of the groups, 1 / a_ii, rows per group at most (rec: one int4 per group)
     const int *crid;
     const double *crd;
@@ -1118,7 +1118,7 @@ void free_lanem_part(LaneMSched *t)
 
 size_t lanem_part_bytes(const GsSchedule *g) { return (g && g->lanem) ? g->lanem->bytes : 0; }
 
-// rows per wave of the cluster layout: tune key 38 (4 / 8; 1 = off), 0 = automatic -- 8 on the large levels.  Level 1 of the 256^3 hierarchy, fused
+// rows per wave of the cluster layout: PAMG_TUNE_LANEM_CLUSTER (4 / 8; 1 = off), 0 = automatic -- 8 on the large levels.  Level 1 of the 256^3 hierarchy, fused
 // symmetric launch, 512 workgroups (profiles/r08_lanem_cluster_ab.txt): 3.61 ms in the pair layout at s = 3 (4.31 at s = 4); clusters of 4 / 8 rows
 // 3.40 / 3.36 ms at s = 3, 3.15 / 2.95 at s = 4, 3.35 / 3.14 at s = 5 -- a wave that loads 46 unique operands per row instead of 60 affords the longer
 // rows of a deeper merge.  The small levels are bound by their hand-offs and keep one row per wave (and the one-XCD ticket form).
@@ -1131,7 +1131,7 @@ int lanem_cluster_rows(const pamg_matrix_s *A)
     return env == 4 ? 4 : 8;
 }
 
-// levels merged per super-level: tune key 33 (1 = unmerged form, >= 2 = that many), 0 = automatic -- rows long enough to fill a wave
+// levels merged per super-level: PAMG_TUNE_LANE_MERGE (1 = unmerged form, >= 2 = that many), 0 = automatic -- rows long enough to fill a wave
 // (the SA coarse levels: >= 12 entries per row on average), f64
 int lanem_smax(const pamg_matrix_s *A, const GsSchedule *g)
 {
@@ -1163,7 +1163,7 @@ int build_lanem_part(pamg_matrix_s *A, GsSchedule *g)
     // two rows per wave (32 lanes each, rows of a super-level paired by length) on the large levels: a fifth fewer padded slots (1.14 instead of 1.44
     // units per row on level 1 of the 256^3 hierarchy) and 1.74 instead of 1.81 ms -- the sweep there is bound by what the memory system delivers per
     // row, not by waves or hand-offs (profiles/r06_microbench_lanem_rows_per_wave.json); small levels are bound by their hand-offs: a wave that waits
-    // for ITS row only (tune key 35: 1 / 2, 0 = this rule)
+    // for ITS row only (PAMG_TUNE_LANEM_RPW: 1 / 2, 0 = this rule)
     const int rpw = A->lanem_rpw ? A->lanem_rpw : (A->nrows > 131072 ? 2 : 1);
     const int cluster = lanem_cluster_rows(A);
     if (build_lanem_plan((int)A->nrows, A->h_Ap.data(), A->h_Aj.data(), hAx.data(), g->row_start, g->row_step, (int)g->nrows, g->nlevels, g->h_vis, g->h_lvl,
@@ -1236,7 +1236,7 @@ static int lanem_to_device(const LaneMPlan &P, int s_max, LaneMSched **out)
     return PAMG_OK;
 }
 
-// =================================================================== zero-iterate plans (tune key 39)
+// =================================================================== zero-iterate plans (PAMG_TUNE_ZERO_PLANS)
 // A cycle enters every coarse level with x = 0 (cycle_rec), and a symmetric sweep from zero needs half the operator in each direction:
 //   forward : (D + L) y = b -- the strictly upper entries multiply zeros;
 //   backward: after the forward sweep b_r - sum_{j<r} a_rj y_j = a_rr y_r for every updated row r, so the backward half is the backward sweep of
@@ -1244,7 +1244,7 @@ static int lanem_to_device(const LaneMPlan &P, int s_max, LaneMSched **out)
 // The planner is linear in the operator's entries: Zf = the forward plan of tril(A), Zb = the backward plan of triu(A), same layouts and gates as the
 // general plans, built from host copies of the triangles (no second device copy of the operator).  Rows without a usable diagonal keep their old
 // value; they are the only source of OLD operands in these plans.  The forward kernel stores w (LaneMArgs::w), the backward kernel runs with b = w.
-// Depth: tune key 40 (2..16), 0 = automatic -- what won the scan of the 256^3 hierarchy by more than the spread of three repetitions (0.1 - 0.2 %),
+// Depth: PAMG_TUNE_ZERO_MERGE (2..16), 0 = automatic -- what won the scan of the 256^3 hierarchy by more than the spread of three repetitions (0.1 - 0.2 %),
 // fused launch announced to start from zero (profiles/r09_microbench_zero_plan_scan.json; the general plans in the same session: level 1 2.92 ms, level 2 0.924):
 //   level 1 (2.03 M rows, cluster layout, 512 workgroups): s = 4 2.556 ms, 5 2.298, 6 2.269, 8 2.804 (2.448 with 768 workgroups; s = 4 / 5 / 6 lose 2 - 5 %
 //            with 768) -- a triangular row at s = 6 carries 62.5 operands, 30 unique per row: less than the full plan at s = 4 (78.6 / 46.2), with 374
@@ -1420,7 +1420,7 @@ static int lanem_launch_plan(pamg_matrix_s *A, GsSchedule *g, LaneMSched *t, voi
 
 int lanem_launch(pamg_matrix_s *A, GsSchedule *g, void *x, const void *b, hipStream_t s) { return lanem_launch_plan(A, g, g->lanem, x, b, nullptr, s); }
 
-// the symmetric sweep from x = 0 as two launches on the zero-iterate plans (tune key 37 = 0, or where the fused kernel does not apply): what the
+// the symmetric sweep from x = 0 as two launches on the zero-iterate plans (PAMG_TUNE_SYM_FUSED = 0, or where the fused kernel does not apply): what the
 // fused launch computes, bit for bit -- the same plans, the same row sums, w across the kernel boundary
 // acc: the correction form, x += sweep(0, b).  The forward half sweeps a zeroed vector -- the backward schedule's snapshot buffer, which the backward
 // half would otherwise fill with a copy of exactly these values -- and the backward half adds what it computes to x: no scratch vector, no copy, no add pass

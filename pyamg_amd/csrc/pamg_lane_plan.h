@@ -8,7 +8,7 @@
 // row sum and the IEEE division: L lanes share a row, every lane adds its K products, a butterfly adds the lanes, and
 // the row is finished with (b - sum) * (1 / a_ii).  Results agree with the reference to rounding (a few ulp per
 // sweep; tests hold 1e-13 per sweep and the north star's 1e-10 on residual norms), not bit for bit -- the
-// order-exact schedulers remain available (tune key 24 = 0).
+// order-exact schedulers remain available (PAMG_TUNE_GS_ORDER = 0).
 //
 // Layout ("groups").  The rows of one dependency level are cut into groups of RPW = 64 / L rows; a group is the work
 // of ONE wave.  Every level is padded to whole groups with dummy rows, every row to K * L entry slots, so the

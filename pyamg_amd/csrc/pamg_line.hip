@@ -6,7 +6,7 @@
 // the sweep is the first-order linear recurrence x_t = B_t + A_t x_{t-1}.  One wave takes 64 consecutive rows (one per lane),
 // forms B_t = (b_t - sum of the OTHER entries) * (1 / a_tt) and A_t = - a_{t,t-1} / a_tt, and finishes the 64 rows with an
 // inclusive scan of the pairs (six combining steps) -- the same algebra in another association: the reference's iterates
-// up to rounding (fast order, tune key 24 = 1; the order-exact schedulers remain).  A LINE (chunks chained by the coupling)
+// up to rounding (fast order, PAMG_TUNE_GS_ORDER = 1; the order-exact schedulers remain).  A LINE (chunks chained by the coupling)
 // belongs to one wave, the running value stays in a register; between lines the hand-off is the sentinel protocol of the
 // other persistent sweeps (the published 8-byte value is the flag).  Lines are taken in the order of their dependency level
 // over the line graph: wave w takes lines w, w + W, ... -- all W waves co-resident, a line only waits for lines of lower

@@ -9,7 +9,7 @@
 //     x_t = B_t + A_t x_{t-1},   B_t = (b_t - sum over the OTHER entries) / a_tt,   A_t = - a_{t,t-1} / a_tt,
 // and a linear recurrence is a SCAN: 64 consecutive rows are finished by one wave in log2(64) combining steps
 // ((A2, B2) o (A1, B1) = (A2 A1, B2 + A2 B1)), exactly the same algebra evaluated in another association -- the reference's
-// iterates up to rounding, like the lane-parallel row sums of pamg_lane.hip (fast order, tune key 24 = 1).  What remains
+// iterates up to rounding, like the lane-parallel row sums of pamg_lane.hip (fast order, PAMG_TUNE_GS_ORDER = 1).  What remains
 // sequential is the dependency between LINES (a line waits for the lines its other early operands live in): 2 n levels of
 // n lines on an n^3 grid instead of 3 n levels, and -- the point -- a whole line of work per hand-off instead of a plane
 // diagonal's worth of scattered rows.

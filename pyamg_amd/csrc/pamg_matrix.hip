@@ -989,7 +989,7 @@ int stream_launch_part(pamg_matrix_s *A, int part, int epi, const void *x, const
         if (rowg) { const int st = launch_rowgather<float>(epi, n, A->cap, A->nvdict, s, a); if (st != 1) return st; }
         return launch_any<float>(epi, n, lds, s, a);
     }
-    int lds = lds_bytes(A->dtype, epi, A->cap) + A->lds_pad;        // lds_pad (tune key 36): unused LDS that caps the workgroups per CU of the staged kernel
+    int lds = lds_bytes(A->dtype, epi, A->cap) + A->lds_pad;        // lds_pad (PAMG_TUNE_LDS_PAD): unused LDS that caps the workgroups per CU of the staged kernel
     const int grid = (A->stream_flags & 2) ? 8 * ((A->nblk + 7) / 8) : A->nblk;
     const bool idx16 = A->use_idx16 && A->d_Aj16;
     const bool val8 = idx16 && A->use_val8 && A->d_Ax8;
@@ -1089,6 +1089,8 @@ int tile_occupancy(int dtype, int wide, int lds)
         }
     return best;
 }
+
+void tune_inherit(pamg_matrix_s *T, const pamg_matrix_s *A);      // the tuning table, ahead of pamg_matrix_tune
 }  // namespace
 
 namespace pamg {
@@ -1162,8 +1164,8 @@ static bool want_tiles(const pamg_matrix_s *A, const GsSchedule *g)
     return A->gs_mode == 5 || (A->gs_mode == 0 && tile_auto(A, g));
 }
 
-// Fast order (tune key 24 = 1): the lane-parallel sweep wherever the schedule fits its form; wide schedules (the fine levels of
-// 3-D problems) stay with the tiled sweep unless tune key 27 says otherwise.
+// Fast order (PAMG_TUNE_GS_ORDER = 1): the lane-parallel sweep wherever the schedule fits its form; wide schedules (the fine levels of
+// 3-D problems) stay with the tiled sweep unless PAMG_TUNE_LANE_WIDE says otherwise.
 static bool want_lanes(const pamg_matrix_s *A, const GsSchedule *g)
 {
     if (A->gs_order != 1 || !lane_eligible(A, g)) return false;
@@ -1208,8 +1210,7 @@ int ensure_point_twin(pamg_matrix_s *A, GsSchedule *g)
             const int st = pamg_matrix_create(&T, A->dtype, PAMG_CSR, (int)A->nrows, (int)A->ncols, 1, 1, A->h_Ap.data(), A->h_Aj.data(), hAx.data());
             if (st != PAMG_OK) { A->point_twin_unfit = true; return st == PAMG_E_UNSUPPORTED || st == PAMG_E_ARG ? PAMG_OK : st; }
             T->gs_order = 1;
-            T->lane_L = A->lane_L; T->lane_G = A->lane_G; T->lane_flags = A->lane_flags; T->lane_merge = A->lane_merge; T->line_scan = A->line_scan;
-            T->lane_wide = A->lane_wide; T->lanem_rpw = A->lanem_rpw; T->lanem_cluster = A->lanem_cluster; T->lanem_ahead10 = A->lanem_ahead10; T->gran_xcd = A->gran_xcd;
+            tune_inherit(T, A);
             A->point_twin = T;
             { std::lock_guard<std::mutex> lk2(g_sched_mu); A->bytes += T->bytes; A->point_twin_bytes = T->bytes; }
         }
@@ -1249,7 +1250,7 @@ int ensure_parts(pamg_matrix_s *A, GsSchedule *g, bool block_gs)
     }
     if (want_lanes(A, g) && g->lanem) return PAMG_OK;     // the merged form is there (a second call fell through to the level-permuted copy: 0.4 s and 0.8 GB per direction of level 1 at 256^3)
     if (want_lanes(A, g) && !g->lanem && !g->lanem_unfit && !g->lane && lanem_smax(A, g) >= 2) {
-        // the merged form first (f64 Gauss-Seidel; an SOR smoother on this operator sets tune key 33 = 1 before its schedules are built)
+        // the merged form first (f64 Gauss-Seidel; an SOR smoother on this operator sets PAMG_TUNE_LANE_MERGE = 1 before its schedules are built)
         const size_t before = g->bytes;
         const int st = build_lanem_part(A, g);
         if (st == PAMG_OK) { std::lock_guard<std::mutex> lk(g_sched_mu); A->bytes += g->bytes - before; return PAMG_OK; }
@@ -1454,7 +1455,7 @@ int gs_sweep_symmetric(pamg_matrix_s *A, void *x, const void *b, bool x_zero, hi
         if (!A->d_sym_hf[0]) return PAMG_OK;
     }
     if (form == 1 && x_zero && A->zero_plans == 2 && !A->zplan[0] && !A->zplan[1]) {
-        // a bare operator with tune key 39 = 2: its first sweep from zero builds the zero-iterate plans (a solver built them with its schedules)
+        // a bare operator with PAMG_TUNE_ZERO_PLANS = 2: its first sweep from zero builds the zero-iterate plans (a solver built them with its schedules)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         PAMG_HIP(hipStreamIsCapturing(s, &cs));
         if (cs == hipStreamCaptureStatusNone) {
@@ -1468,7 +1469,7 @@ int gs_sweep_symmetric(pamg_matrix_s *A, void *x, const void *b, bool x_zero, hi
     return st;
 }
 
-// ---- zero-iterate plans (pamg_lane.hip, tune key 39).  The plans are used where a symmetric sweep is announced to start from x = 0 and BOTH schedules
+// ---- zero-iterate plans (pamg_lane.hip, PAMG_TUNE_ZERO_PLANS).  The plans are used where a symmetric sweep is announced to start from x = 0 and BOTH schedules
 // take the merged lane form; whatever is missing is built here when `build` says so (a solver, per level; a bare operator with key = 2 at its first
 // such sweep), and plans that cannot be used are dropped.
 void matrix_drop_zero_plans(pamg_matrix_s *A)
@@ -1544,7 +1545,7 @@ int gs_sweep_zero_pair(pamg_matrix_s *A, void *x, const void *b, hipStream_t s, 
     return st;
 }
 
-// ---- the correction form (tune key 41).  Gauss-Seidel is an affine iteration: sweep(x, b) = x + sweep(0, b - A x), for the symmetric sweep as for
+// ---- the correction form (PAMG_TUNE_GS_CORRECTION).  Gauss-Seidel is an affine iteration: sweep(x, b) = x + sweep(0, b - A x), for the symmetric sweep as for
 // each half.  A symmetric sweep from x != 0 can therefore run on the zero-iterate plans: one residual launch, then the launch announced from zero on
 // r whose backward half ADDS to x (the accumulating instantiation of the kernels, pamg_lane.hip).  Only a solver's cycle driver asks for it (it owns
 // the scratch vector); a bare operator's sweeps keep the general plans unless the caller asks by name (pamg_matrix_gauss_seidel_correction).
@@ -1555,7 +1556,7 @@ int gs_sweep_correction(pamg_matrix_s *A, void *x, const void *b, void *r, bool 
     if (!force && (A->gs_correction == 1 || (A->gs_correction == 0 && A->nrows < GS_CORRECTION_MIN_ROWS))) return PAMG_OK;
     if (!A->zplan[0] || !A->zplan[1] || !A->d_zw) {
         if (!force || A->zero_plans != 2 || A->zplan[0] || A->zplan[1]) return PAMG_OK;
-        // a bare operator with key 39 = 2, asked by name: the plans are built here -- allocations, so never inside a graph capture
+        // a bare operator with PAMG_TUNE_ZERO_PLANS = 2, asked by name: the plans are built here -- allocations, so never inside a graph capture
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         PAMG_HIP(hipStreamIsCapturing(s, &cs));
         if (cs != hipStreamCaptureStatusNone) return PAMG_OK;
@@ -1573,7 +1574,7 @@ int gs_sweep_correction(pamg_matrix_s *A, void *x, const void *b, void *r, bool 
     }
     PAMG_TRY(stream_launch(A, EPI_RESID, x, b, r, 0.0, 0.0, nullptr, s));                     // r = b - A x
     int st = fused ? lanem_sym_launch(A, gf, gb, x, r, true, s, true) : PAMG_E_UNSUPPORTED;
-    if (st == PAMG_E_UNSUPPORTED) st = lanem_zero_pair_launch(A, gf, gb, x, r, true, s);     // (the two directions would not run the same fused kernel, or key 37 = 0)
+    if (st == PAMG_E_UNSUPPORTED) st = lanem_zero_pair_launch(A, gf, gb, x, r, true, s);     // (the two directions would not run the same fused kernel, or PAMG_TUNE_SYM_FUSED = 0)
     if (st != PAMG_OK) return st;
     A->correction_launches++;
     *ran = true;
@@ -1731,7 +1732,7 @@ int kaczmarz_sweep(pamg_matrix_s *L, bool nr, void *v, const void *b, const void
     if (L->R != 1 || L->C != 1) return PAMG_E_UNSUPPORTED;
     LineSchedule *g = nullptr;
     PAMG_TRY(get_line_schedule(L, start, stop, step, &g));
-    // fast order (tune key 24 = 1): ONE persistent launch, lanes share a line, versioned 16-byte slots hand the vector over (pamg_kz.hip)
+    // fast order (PAMG_TUNE_GS_ORDER = 1): ONE persistent launch, lanes share a line, versioned 16-byte slots hand the vector over (pamg_kz.hip)
     if (L->gs_order == 1 && g->kzl && L->gs_mode == 0) return kz_lane_launch(L, g, nr, v, b, Dinv, omega, xout, s);
     // narrow schedules (on average <= 512 lines per level: 2-D operators): ONE persistent workgroup walks the levels
     // (about 2 us per level instead of a launch per level); gs_mode 1 keeps the per-level launches
@@ -2149,83 +2150,154 @@ int pamg_matrix_row_masks(pamg_matrix_t A, long long info[8])
     return PAMG_OK;
 }
 
+}  // extern "C"
+
+// ---- the tuning knobs: ONE row per key.  include/pyamg_amd.h names the keys and says what each chooses; here is what pamg_matrix_tune does
+// with one: the field it sets, the values it takes, how the value is stored, what the call invalidates, and whether the scalar twin of a block
+// operator (ensure_point_twin) takes the field over.
+namespace {
+
+enum TuneStore { AS_IS, NONZERO, ALIGN4, ALIGN16 };      // value, value != 0, value & ~3, value & ~15
+enum TuneEffect {
+    KEEP,              // nothing is dropped: the field is read at launch time, or when the next schedule is built
+    DROP_TWIN,         // the point twin copied the field: it goes
+    DROP_TWIN_LINE,    //   ... and a schedule whose line planner declined on its estimate is asked again
+    DROP_ZERO,         // the zero-iterate plans go
+    DROP_ZERO_IF_OFF,  //   ... for value 1 only
+    DROP_LANES,        // lane geometry / merging: the lane, merged-lane and block-lane parts go, with them the twin and the zero-iterate plans
+                       // (they follow the layout of the merged parts); every schedule's planners are asked again
+    DROP_TILES,        // tile plan parameters: the tile parts go
+    REPLAN,            // every schedule, the zero-iterate plans and the twin go; the operator is planned again
+    REPLAN_WINDOW      //   ... and the LDS window is the caller's from now on (cap_from_val8)
+};
+enum : unsigned { HELD_OK = 1, TWIN = 2 };      // may be set while a solver holds the operator; the point twin inherits the field
+
+template <int lo, int hi> bool in(int v) { return v >= lo && v <= hi; }
+template <int lo, int hi> bool zero_or_in(int v) { return v == 0 || in<lo, hi>(v); }
+template <int... vs> bool one_of(int v) { return ((v == vs) || ...); }
+template <int lo, int hi, int retired> bool flags_in(int v) { return in<lo, hi>(v) && !(v & retired); }
+bool any(int) { return true; }
+bool pow2_or_zero_64_8192(int v) { return zero_or_in<64, 8192>(v) && !(v & (v - 1)); }
+
+struct TuneKey {
+    int key;
+    int pamg_matrix_s::*field;
+    bool (*accepts)(int);
+    TuneEffect effect;
+    TuneStore store;
+    unsigned flags;
+};
+using M = pamg_matrix_s;
+constexpr TuneKey TUNE_KEYS[] = {
+    {PAMG_TUNE_LDS_ENTRIES,   &M::cap,           in<64, 12288>,          REPLAN_WINDOW,    ALIGN4,  0},
+    {PAMG_TUNE_MAX_ROWS,      &M::max_rows,      in<1, INT_MAX>,         REPLAN,           AS_IS,   0},
+    {PAMG_TUNE_FLOW_CAP,      &M::flow_cap,      in<0, 256>,             KEEP,             AS_IS,   0},
+    {PAMG_TUNE_GS_MODE,       &M::gs_mode,       in<0, 5>,               KEEP,             AS_IS,   0},
+    {PAMG_TUNE_GRAN_CAP,      &M::gran_cap,      in<0, INT_MAX>,         KEEP,             AS_IS,   0},
+    {PAMG_TUNE_GRAN_XCD,      &M::gran_xcd,      in<0, 2>,               DROP_TWIN,        AS_IS,   TWIN},
+    {PAMG_TUNE_STREAM_FLAGS,  &M::stream_flags,  flags_in<0, 63, 12>,    KEEP,             AS_IS,   0},      // bits 2, 3: retired (ablations that computed wrong results)
+    {PAMG_TUNE_GS_PROF,       &M::gs_prof,       any,                    KEEP,             NONZERO, 0},
+    {PAMG_TUNE_TILE_G,        &M::tile_G,        in<0, INT_MAX>,         DROP_TILES,       AS_IS,   0},
+    {PAMG_TUNE_TILE_W,        &M::tile_W,        pow2_or_zero_64_8192,   DROP_TILES,       AS_IS,   0},
+    {PAMG_TUNE_TILE_CAP,      &M::tile_cap,      in<0, TILE_MAX_ENTRIES>, DROP_TILES,      AS_IS,   0},
+    {PAMG_TUNE_TILE_DEFAULT,  &M::tile_default,  any,                    KEEP,             NONZERO, 0},
+    {PAMG_TUNE_TILE_D,        &M::tile_D,        in<0, 32>,              DROP_TILES,       AS_IS,   0},
+    {PAMG_TUNE_TILE_Q,        &M::tile_Q,        in<-1, 4>,              DROP_TILES,       AS_IS,   0},
+    {PAMG_TUNE_TILE_PART,     &M::tile_part,     in<0, 1>,               DROP_TILES,       AS_IS,   0},
+    {PAMG_TUNE_IDX16,         &M::use_idx16,     any,                    KEEP,             NONZERO, 0},
+    // gs_cap is read by build_level_part only, when a schedule is made.  The key keeps the tile effect, which leaves a schedule that has its level
+    // part as it is: the value takes hold when something else drops the schedule ("retired knobs"); another effect would change behaviour
+    {PAMG_TUNE_GS_CAP,        &M::gs_cap,        zero_or_in<64, 2048>,   DROP_TILES,       ALIGN4,  0},
+    {PAMG_TUNE_VAL8,          &M::use_val8,      any,                    KEEP,             NONZERO, HELD_OK},      // read at launch time only: no plan depends on it
+    {PAMG_TUNE_ROWGATHER,     &M::use_rowg,      any,                    KEEP,             NONZERO, HELD_OK},      // likewise
+    {PAMG_TUNE_ROWPAT,        &M::use_rowpat,    one_of<0, 1, 3, 4>,     KEEP,             AS_IS,   HELD_OK},      // likewise
+    {PAMG_TUNE_GS_ORDER,      &M::gs_order,      in<0, 1>,               KEEP,             AS_IS,   0},
+    {PAMG_TUNE_LANE_L,        &M::lane_L,        one_of<0, 4, 8, 16, 32, 64>, DROP_LANES,  AS_IS,   TWIN},
+    {PAMG_TUNE_LANE_G,        &M::lane_G,        in<0, INT_MAX>,         DROP_TWIN,        AS_IS,   TWIN},
+    {PAMG_TUNE_LANE_WIDE,     &M::lane_wide,     in<0, 1>,               DROP_TWIN,        AS_IS,   TWIN},
+    {PAMG_TUNE_LANE_FLAGS,    &M::lane_flags,    flags_in<0, 15, 6>,     DROP_TWIN,        AS_IS,   TWIN},      // bits 1, 2: retired (slab form, old values through the L1)
+    {PAMG_TUNE_LINE_SCAN,     &M::line_scan,     in<0, 2>,               DROP_TWIN_LINE,   AS_IS,   TWIN},      // 2: also where the estimate favours the lane form
+    {PAMG_TUNE_ROWMASK_KZ,    &M::rowmask_kz,    one_of<2, 4, 8>,        KEEP,             AS_IS,   0},
+    {PAMG_TUNE_ROWMASK_FLAGS, &M::rowmask_flags, in<0, 7>,               KEEP,             AS_IS,   0},
+    {PAMG_TUNE_LANE_MERGE,    &M::lane_merge,    in<0, 8>,               DROP_LANES,       AS_IS,   TWIN},
+    {PAMG_TUNE_LANEM_AHEAD,   &M::lanem_ahead10, in<1, 400>,             DROP_TWIN,        AS_IS,   TWIN},
+    {PAMG_TUNE_LANEM_RPW,     &M::lanem_rpw,     in<0, 2>,               DROP_LANES,       AS_IS,   TWIN},
+    {PAMG_TUNE_LDS_PAD,       &M::lds_pad,       in<0, 98304>,           KEEP,             ALIGN16, 0},
+    {PAMG_TUNE_SYM_FUSED,     &M::sym_fused,     in<0, 1>,               KEEP,             AS_IS,   0},      // read at launch time; refused while a solver's graphs hold the choice
+    {PAMG_TUNE_LANEM_CLUSTER, &M::lanem_cluster, one_of<0, 1, 4, 8>,     DROP_LANES,       AS_IS,   TWIN},
+    {PAMG_TUNE_ZERO_PLANS,    &M::zero_plans,    in<0, 2>,               DROP_ZERO_IF_OFF, AS_IS,   0},
+    {PAMG_TUNE_ZERO_MERGE,    &M::zero_merge,    zero_or_in<2, 16>,      DROP_ZERO,        AS_IS,   0},
+    {PAMG_TUNE_GS_CORRECTION, &M::gs_correction, in<0, 2>,               KEEP,             AS_IS,   0},      // read at launch time; refused while a solver's graphs hold the choice
+};
+
+// what the scalar twin T of a block operator A takes over from it
+void tune_inherit(pamg_matrix_s *T, const pamg_matrix_s *A)
+{
+    for (const TuneKey &t : TUNE_KEYS) if (t.flags & TWIN) T->*(t.field) = A->*(t.field);
+}
+
+int tune_stored(TuneStore store, int value) { return store == NONZERO ? value != 0 : store == ALIGN4 ? (value & ~3) : store == ALIGN16 ? (value & ~15) : value; }
+
+// free a part of a schedule and take its bytes off the schedule's and the operator's account
+template <typename Part>
+void drop_part(pamg_matrix_s *A, GsSchedule *g, Part *&part, size_t bytes, void (*free_part)(Part *))
+{
+    if (!part) return;
+    A->bytes -= bytes; g->bytes -= bytes;
+    free_part(part);
+    part = nullptr;
+}
+
+int tune_effect(pamg_matrix_s *A, TuneEffect effect, int value)
+{
+    switch (effect) {
+        case KEEP: return PAMG_OK;
+        case DROP_ZERO_IF_OFF: if (value != 1) return PAMG_OK; [[fallthrough]];
+        case DROP_ZERO: matrix_drop_zero_plans(A); return PAMG_OK;
+        case DROP_TWIN_LINE: for (GsSchedule *g : A->gs) if (g) g->line_unfit = false; [[fallthrough]];
+        case DROP_TWIN: matrix_drop_point_twin(A); return PAMG_OK;
+        case DROP_LANES:
+            matrix_drop_point_twin(A);
+            matrix_drop_zero_plans(A);
+            for (GsSchedule *g : A->gs) {
+                if (!g) continue;
+                g->lane_unfit = g->lanem_unfit = g->blane_unfit = g->line_unfit = false;
+                drop_part(A, g, g->lane, lane_part_bytes(g), free_lane_part);
+                drop_part(A, g, g->lanem, lanem_part_bytes(g), free_lanem_part);
+                drop_part(A, g, g->blane, blane_part_bytes(g), free_blane_part);
+            }
+            return PAMG_OK;
+        case DROP_TILES:
+            for (GsSchedule *g : A->gs) {
+                if (!g) continue;
+                g->tile_unfit = false;
+                drop_part(A, g, g->tile, g->tile ? g->tile->bytes : 0, free_tile_part);
+            }
+            return PAMG_OK;
+        case REPLAN_WINDOW: A->cap_from_val8 = 0; [[fallthrough]];
+        case REPLAN:
+            for (int k = 0; k < 4; ++k) { if (A->gs[k]) A->bytes -= A->gs[k]->bytes; free_schedule(A->gs[k]); A->gs[k] = nullptr; }
+            matrix_drop_zero_plans(A);
+            matrix_drop_point_twin(A);                          // it sweeps for the schedules just dropped
+            return replan(A);
+    }
+    return PAMG_E_ARG;
+}
+
+}  // namespace
+
+extern "C" {
+
 int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
 {
     if (!A) return PAMG_E_ARG;
+    const TuneKey *t = std::find_if(std::begin(TUNE_KEYS), std::end(TUNE_KEYS), [key](const TuneKey &r) { return r.key == key; });
+    if (t == std::end(TUNE_KEYS)) t = nullptr;
     // a finalised solver's captured graphs point into the schedules and plans this call would free
-    if (key == 21) { A->use_val8 = value != 0; return PAMG_OK; }      // read at launch time only: no plan depends on it
-    if (key == 22) { A->use_rowg = value != 0; return PAMG_OK; }      // likewise
-    if (key == 23) { if (value < 0 || value > 4 || value == 2) return PAMG_E_ARG; A->use_rowpat = value; return PAMG_OK; }
-    if (A->borrowed > 0) return PAMG_E_STATE;
-    switch (key) {
-        case 0: if (value < 64 || value > 12288) return PAMG_E_ARG; A->cap = value & ~3; A->cap_from_val8 = 0; break;
-        case 2: if (value < 1) return PAMG_E_ARG; A->max_rows = value; break;
-        case 3: if (value < 0 || value > 256) return PAMG_E_ARG; A->flow_cap = value; return PAMG_OK;
-        case 5: if (value < 0 || value > 5) return PAMG_E_ARG; A->gs_mode = value; return PAMG_OK;
-        case 6: if (value < 0) return PAMG_E_ARG; A->gran_cap = value; return PAMG_OK;
-        case 7: if (value < 0 || value > 2) return PAMG_E_ARG; A->gran_xcd = value; matrix_drop_point_twin(A); return PAMG_OK;
-        case 8: if (value < 0 || value > 63 || (value & 12)) return PAMG_E_ARG; A->stream_flags = value; return PAMG_OK;      // bits 2, 3: retired (ablations that computed wrong results)
-        case 11: A->gs_prof = value != 0; return PAMG_OK;
-        case 12: if (value < 0) return PAMG_E_ARG; A->tile_G = value; break;
-        case 13: if (value != 0 && (value < 64 || value > 8192 || (value & (value - 1)))) return PAMG_E_ARG; A->tile_W = value; break;
-        case 14: if (value < 0 || value > TILE_MAX_ENTRIES) return PAMG_E_ARG; A->tile_cap = value; break;
-        case 15: A->tile_default = value != 0; return PAMG_OK;
-        case 16: if (value < 0 || value > 32) return PAMG_E_ARG; A->tile_D = value; break;
-        case 17: if (value < -1 || value > 4) return PAMG_E_ARG; A->tile_Q = value; break;
-        case 18: if (value < 0 || value > 1) return PAMG_E_ARG; A->tile_part = value; break;
-        case 19: A->use_idx16 = value != 0; return PAMG_OK;
-        case 20: if (value != 0 && (value < 64 || value > 2048)) return PAMG_E_ARG; A->gs_cap = value & ~3; break;
-        case 24: if (value < 0 || value > 1) return PAMG_E_ARG; A->gs_order = value; return PAMG_OK;
-        case 25: if (value != 0 && value != 4 && value != 8 && value != 16 && value != 32 && value != 64) return PAMG_E_ARG; A->lane_L = value; break;
-        case 26: if (value < 0) return PAMG_E_ARG; A->lane_G = value; matrix_drop_point_twin(A); return PAMG_OK;
-        case 27: if (value < 0 || value > 1) return PAMG_E_ARG; A->lane_wide = value; matrix_drop_point_twin(A); return PAMG_OK;
-        case 33: if (value < 0 || value > 8) return PAMG_E_ARG; A->lane_merge = value; break;
-        case 35: if (value < 0 || value > 2) return PAMG_E_ARG; A->lanem_rpw = value; break;
-        case 38: if (value != 0 && value != 1 && value != 4 && value != 8) return PAMG_E_ARG; A->lanem_cluster = value; break;
-        case 36: if (value < 0 || value > 98304) return PAMG_E_ARG; A->lds_pad = value & ~15; return PAMG_OK;
-        case 34: if (value < 1 || value > 400) return PAMG_E_ARG; A->lanem_ahead10 = value; matrix_drop_point_twin(A); return PAMG_OK;
-        case 37: if (value < 0 || value > 1) return PAMG_E_ARG; A->sym_fused = value; return PAMG_OK;      // read at launch time; refused above while a solver's graphs hold the choice
-        case 39: if (value < 0 || value > 2) return PAMG_E_ARG; A->zero_plans = value; if (value == 1) matrix_drop_zero_plans(A); return PAMG_OK;
-        case 40: if (value != 0 && (value < 2 || value > 16)) return PAMG_E_ARG; A->zero_merge = value; matrix_drop_zero_plans(A); return PAMG_OK;
-        case 41: if (value < 0 || value > 2) return PAMG_E_ARG; A->gs_correction = value; return PAMG_OK;     // read at launch time; refused above while a solver's graphs hold the choice
-        case 30:                                               // 2: also where the estimate favours the lane form
-            if (value < 0 || value > 2) return PAMG_E_ARG;
-            A->line_scan = value;
-            matrix_drop_point_twin(A);
-            for (int k = 0; k < 4; ++k) if (A->gs[k]) A->gs[k]->line_unfit = false;      // a schedule the planner declined on its estimate is asked again
-            return PAMG_OK;
-        case 31: if (value != 2 && value != 4 && value != 8) return PAMG_E_ARG; A->rowmask_kz = value; return PAMG_OK;
-        case 32: if (value < 0 || value > 7) return PAMG_E_ARG; A->rowmask_flags = value; return PAMG_OK;
-        case 28: if (value < 0 || value > 15 || (value & 6)) return PAMG_E_ARG; A->lane_flags = value; matrix_drop_point_twin(A); return PAMG_OK;      // bits 1, 2: retired (slab form, old values through the L1)
-        default: return PAMG_E_ARG;
-    }
-    if (key == 25 || key == 33 || key == 35 || key == 38) {         // lane geometry / merging: drop the lane parts only (and the point twin, which copied the keys)
-        matrix_drop_point_twin(A);
-        matrix_drop_zero_plans(A);                                  // (they follow the layout of the merged parts)
-        for (int k = 0; k < 4; ++k) {
-            GsSchedule *g = A->gs[k];
-            if (g) g->lane_unfit = false;
-            if (g && g->lane) { const size_t lb = lane_part_bytes(g); A->bytes -= lb; g->bytes -= lb; free_lane_part(g->lane); g->lane = nullptr; }
-            if (g) g->lanem_unfit = false;
-            if (g && g->lanem) { const size_t lb = lanem_part_bytes(g); A->bytes -= lb; g->bytes -= lb; free_lanem_part(g->lanem); g->lanem = nullptr; }
-            if (g) g->blane_unfit = false;
-            if (g && g->blane) { const size_t lb = blane_part_bytes(g); A->bytes -= lb; g->bytes -= lb; free_blane_part(g->blane); g->blane = nullptr; }
-            if (g) g->line_unfit = false;
-        }
-        return PAMG_OK;
-    }
-    if (key >= 12) {                                  // tile plan parameters: drop the tile parts only
-        for (int k = 0; k < 4; ++k) {
-            GsSchedule *g = A->gs[k];
-            if (g) g->tile_unfit = false;
-            if (g && g->tile) { A->bytes -= g->tile->bytes; g->bytes -= g->tile->bytes; free_tile_part(g->tile); g->tile = nullptr; }
-        }
-        return PAMG_OK;
-    }
-    for (int k = 0; k < 4; ++k) { if (A->gs[k]) A->bytes -= A->gs[k]->bytes; free_schedule(A->gs[k]); A->gs[k] = nullptr; }
-    matrix_drop_zero_plans(A);
-    matrix_drop_point_twin(A);                          // it sweeps for the schedules just dropped
-    return replan(A);
+    if (A->borrowed > 0 && !(t && (t->flags & HELD_OK))) return PAMG_E_STATE;
+    if (!t || !t->accepts(value)) return PAMG_E_ARG;
+    A->*(t->field) = tune_stored(t->store, value);
+    return tune_effect(A, t->effect, value);
 }
 
 int pamg_matrix_autotune(pamg_matrix_t A, int allow_cap)
@@ -2255,7 +2327,7 @@ int pamg_matrix_autotune(pamg_matrix_t A, int allow_cap)
     // r05_microbench_sa_ops_wide_codes_vs_32bit_not_kept.json: P0 0.219 ms on codes, 0.199 on 32-bit columns, R0 0.204 against 0.211).  Two interleaved
     // rounds, a candidate's better time counts, and anything but the plan's own setting has to win by 2 %: a single round of six launches picked the
     // XCD-contiguous range order (bit 1: measured slower on every SA-level operator, r05_microbench_sa_ops_nontemporal.json) for R0 by noise and cost
-    // 11 % of that product (r05_c4s_kernel_roofline.txt); bit 1 is left to tune key 8: every candidate keeps the caller's setting of it
+    // 11 % of that product (r05_c4s_kernel_roofline.txt); bit 1 is left to PAMG_TUNE_STREAM_FLAGS: every candidate keeps the caller's setting of it
     const int idx0 = A->use_idx16;
     const int nidx = (A->d_Aj16 && !A->d_Ax8 && idx0) ? 2 : 1;
     // timed on what the cycle runs most: r = b - A x for square operators (three vectors in flight: the Horner steps and the residual), y = A x for
@@ -2396,7 +2468,7 @@ int pamg_matrix_kz_info(pamg_matrix_t A, int which, int64_t info[8])
 int pamg_matrix_lanem_info(pamg_matrix_t A, int which, int64_t info[20], double *growth)
 {
     if (!A || !info || which < 0 || which > 5) return PAMG_E_ARG;
-    if (which >= 4) return pamg::lanem_plan_info(A->zplan[which - 4], info, growth);      // 4 / 5: the zero-iterate plans Zf / Zb (tune key 39)
+    if (which >= 4) return pamg::lanem_plan_info(A->zplan[which - 4], info, growth);      // 4 / 5: the zero-iterate plans Zf / Zb (PAMG_TUNE_ZERO_PLANS)
     return pamg::lanem_info(A->gs[which], info, growth);
 }
 

@@ -96,7 +96,7 @@ int block_jacobi_pp(pamg_matrix_s *A, void **px, void **palt, const void *b, con
 // :100-154).  Quirks mirrored on purpose: sweep='symmetric' drops omega (:326-330), the BSR
 // flavour ignores omega (:343-346).
 // r: a scratch vector of the operator's size (a solver's level residual) -- a symmetric sweep that is not announced to start from zero may then run in
-// correction form (gs_sweep_correction, tune key 41); nullptr (a bare operator): never
+// correction form (gs_sweep_correction, PAMG_TUNE_GS_CORRECTION); nullptr (a bare operator): never
 int gs_apply(pamg_matrix_s *A, void *x, const void *b, int sweep, double omega, int its, hipStream_t s, bool x_zero = false, void *r = nullptr)
 {
     if (!square_ok(A)) return PAMG_E_ARG;
@@ -348,7 +348,7 @@ int fall_back_to_level_launches(pamg_solver_s *S)
     for (Level &L : S->levels) {
         if (!L.A) continue;
         L.A->gs_mode = 1;
-        L.A->tile_default = false;
+        L.A->tile_default = 0;
         PAMG_TRY(sym_reset(L.A));                             // (the fused symmetric sweep declines from here on: gs_mode 1)
         matrix_drop_zero_plans(L.A);                          // (so do the zero-iterate plans: every sweep takes the general path)
         for (Smoother *sm : {&L.pre, &L.post}) {
@@ -496,7 +496,7 @@ static bool sor_takes_omega(const pamg_matrix_s *A, const Smoother &sm)
     return sm.kind == PAMG_SMOOTH_SOR && A->R == 1 && A->flavour != PAMG_BSR && sm.sweep != PAMG_SYMMETRIC && sm.omega != 1.0;
 }
 
-// Zero-iterate plans (tune key 39) for the pre-smoother of level l: a cycle enters every level below the finest with x = 0 (cycle_rec), so a
+// Zero-iterate plans (PAMG_TUNE_ZERO_PLANS) for the pre-smoother of level l: a cycle enters every level below the finest with x = 0 (cycle_rec), so a
 // symmetric Gauss-Seidel pre-smoother there sweeps half the operator per direction.  The finest level only on request (key = 2): its pre-smoother
 // starts from zero in the preconditioning cycles alone.
 static bool zero_plans_wanted(const pamg_matrix_s *A, const Smoother &pre, const Smoother &post, int l)

@@ -31,7 +31,7 @@ inline int resident_cap(int &cap, const void *&cap_kernel, const void *k, int ma
     return cap;
 }
 
-// the time stamps of a sweep (tune key 11): four words per group, allocated on the first profiled sweep ...
+// the time stamps of a sweep (PAMG_TUNE_GS_PROF): four words per group, allocated on the first profiled sweep ...
 inline int ensure_profile(long long **d_prof, int64_t ngroups)
 {
     if (*d_prof) return PAMG_OK;

@@ -119,7 +119,7 @@ __device__ __forceinline__ void draw_ticket(unsigned *counter, unsigned &tk, con
 }
 __device__ __forceinline__ int ticket_number(unsigned tk) { return (int)__builtin_amdgcn_readfirstlane(tk); }
 
-// ---- the profile record of a group (tune key 11): started, last operand seen, published, XCD | workgroup << 4.  One lane writes it
+// ---- the profile record of a group (PAMG_TUNE_GS_PROF): started, last operand seen, published, XCD | workgroup << 4.  One lane writes it
 __device__ __forceinline__ void profile_stamp(long long *o, long long t0, long long t1)
 {
     o[0] = t0; o[1] = t1; o[2] = wall_clock64();

@@ -30,7 +30,17 @@ import numpy as np
 from . import _capi as capi
 from .hierarchy import HierarchySpec, SmootherSpec, SparseOp, extract
 
-__all__ = ["DeviceMatrix", "DeviceMultilevelSolver"]
+__all__ = ["DeviceMatrix", "DeviceMultilevelSolver", "TUNE_KEYS"]
+
+
+# the tuning knobs of an operator: name -> key of pamg_matrix_tune (the PAMG_TUNE_<NAME> constants of include/pyamg_amd.h, which documents them),
+# in ascending key order -- the order DeviceMatrix.tune applies them in
+TUNE_KEYS = {
+    "lds_entries": 0, "max_rows": 2, "flow_cap": 3, "gs_mode": 5, "gran_cap": 6, "gran_xcd": 7, "stream_flags": 8, "gs_prof": 11, "tile_G": 12, "tile_W": 13, "tile_cap": 14,
+    "tile_default": 15, "tile_D": 16, "tile_Q": 17, "tile_part": 18, "idx16": 19, "gs_cap": 20, "val8": 21, "rowgather": 22, "rowpat": 23, "gs_order": 24, "lane_L": 25, "lane_G": 26,
+    "lane_wide": 27, "lane_flags": 28, "line_scan": 30, "rowmask_kz": 31, "rowmask_flags": 32, "lane_merge": 33, "lanem_ahead": 34, "lanem_rpw": 35, "lds_pad": 36, "sym_fused": 37,
+    "lanem_cluster": 38, "zero_plans": 39, "zero_merge": 40, "gs_correction": 41,
+}
 
 
 class DeviceMatrix:
@@ -193,25 +203,20 @@ class DeviceMatrix:
             capi.check(lib.pamg_matrix_lane_profile(self.handle, which, C.c_void_p(out.ctypes.data), n.value, C.byref(n)), "pamg_matrix_lane_profile")
         return out
 
-    def tune(self, lds_entries=None, max_rows=None, flow_cap=None, gs_mode=None, gran_cap=None, gran_xcd=None, stream_flags=None, gs_prof=None,
-             tile_G=None, tile_W=None, tile_cap=None, tile_default=None, tile_D=None, tile_Q=None, tile_part=None, idx16=None, gs_cap=None, val8=None, rowgather=None, rowpat=None,
-             gs_order=None, lane_L=None, lane_G=None, lane_wide=None, lane_flags=None, line_scan=None, rowmask_kz=None, rowmask_flags=None, lane_merge=None, lanem_ahead=None, lanem_rpw=None, lds_pad=None, sym_fused=None, lanem_cluster=None, zero_plans=None, zero_merge=None, gs_correction=None):
-        """Speed-only knobs (every setting computes the same bits) -- except gs_order: 0 = order-exact row sums (the reference's
-        bits), 1 = fast order (lane-parallel row sums, same sweep order, agrees to rounding).  Refused (PAMG_E_STATE) once a solver holds the
-        operator: captured graphs point into the plans these calls rebuild.
-        stream_flags (key 8): bit 0 non-temporal operator stream, bit 1 XCD-aware row-range order, bit 4 six-chain value-code staging, bit 5 the
-        value-code instantiation on every operator; bits 2 and 3 are retired and refused (PAMG_E_ARG).
-        zero_plans (key 39): merged plans of tril(A) / triu(A) for symmetric sweeps announced to start from x = 0 -- 0 = automatic (a solver builds
-        them on every level below its finest, a bare operator has none), 1 = off, 2 = on (a bare operator builds them at its first such sweep);
-        zero_merge (key 40): their merge depth (0 = automatic).  Agrees with the general plans to rounding.
-        gs_correction (key 41): a solver's symmetric Gauss-Seidel steps from x != 0 as r = b - A x, x += sweep(0, r) on the zero-iterate plans --
-        0 = automatic (levels of at least 16 384 rows), 1 = off, 2 = on wherever the plans exist.  Agrees with the direct sweep to rounding."""
+    def tune(self, **knobs):
+        """Set tuning knobs by name (TUNE_KEYS; include/pyamg_amd.h says for each its range, its default and what it chooses).  ``None`` leaves
+        a knob alone; the others are applied in ascending key order, whatever order they were written in -- the re-planning keys come first,
+        gs_order before the keys that shape its layouts.
+        Speed only (every setting computes the same bits) -- except gs_order: 0 = order-exact row sums (the reference's bits), 1 = fast
+        order (lane-parallel row sums, same sweep order, agrees to rounding).  Refused (PAMG_E_STATE) once a solver holds the operator:
+        captured graphs point into the plans these calls rebuild.  ``DeviceMultilevelSolver(level_tune=...)`` takes the same names per level."""
+        unknown = [k for k in knobs if k not in TUNE_KEYS]
+        if unknown:
+            raise TypeError(f"tune() got an unexpected keyword argument {unknown[0]!r}")
         lib = capi.lib()
-        for key, v in ((0, lds_entries), (2, max_rows), (3, flow_cap), (5, gs_mode), (6, gran_cap), (7, gran_xcd), (8, stream_flags), (11, gs_prof),
-                       (12, tile_G), (13, tile_W), (14, tile_cap), (15, tile_default), (16, tile_D), (17, tile_Q), (18, tile_part), (19, idx16), (20, gs_cap), (21, val8), (22, rowgather), (23, rowpat),
-                       (24, gs_order), (25, lane_L), (26, lane_G), (27, lane_wide), (28, lane_flags), (30, line_scan), (31, rowmask_kz), (32, rowmask_flags), (33, lane_merge), (34, lanem_ahead), (35, lanem_rpw), (36, lds_pad), (37, sym_fused), (38, lanem_cluster), (39, zero_plans), (40, zero_merge), (41, gs_correction)):
-            if v is not None:
-                capi.check(lib.pamg_matrix_tune(self.handle, key, int(v)), "pamg_matrix_tune")
+        for name, key in TUNE_KEYS.items():
+            if knobs.get(name) is not None:
+                capi.check(lib.pamg_matrix_tune(self.handle, key, int(knobs[name])), "pamg_matrix_tune")
 
     # -- kernels on DeviceArray operands
     def spmv(self, mode, x, y, b=None, c=0.0, stream=None, part=None):

@@ -402,3 +402,27 @@ def test_bench_dump_outputs_seeded_and_small(tmp_path):
     small = np.linspace(0.0, 1.0, 1000)
     bench.dump_outputs(tmp_path / "c", small.astype(np.float32), 1.0)
     assert np.array_equal(np.load(tmp_path / "c" / "x.npy"), small.astype(np.float32).astype(np.float64))
+
+
+def test_tune_keys_are_the_header_constants(monkeypatch):
+    """multilevel.TUNE_KEYS says what the PAMG_TUNE_* constants of include/pyamg_amd.h say, in ascending key order; a name that is no
+    knob is a TypeError before the library is asked anything"""
+    from pyamg_amd import multilevel as ml
+    hdr = (ROOT / "include" / "pyamg_amd.h").read_text()
+    defines = {name.lower(): int(num) for name, num in re.findall(r"^#define PAMG_TUNE_([A-Z0-9_]+)\s+(-?\d+)\b", hdr, flags=re.M)}
+    assert len(defines) == 37 and len(set(defines.values())) == 37
+    assert {k.lower(): v for k, v in ml.TUNE_KEYS.items()} == defines
+    assert len({k.lower() for k in ml.TUNE_KEYS}) == len(ml.TUNE_KEYS)
+    assert list(ml.TUNE_KEYS.values()) == sorted(ml.TUNE_KEYS.values())
+
+    def no_library():
+        raise AssertionError("the library was asked")
+    monkeypatch.setattr(ml.capi, "lib", no_library)
+    A = ml.DeviceMatrix.__new__(ml.DeviceMatrix)
+    A.handle = None
+    with pytest.raises(TypeError, match="nonsense"):
+        A.tune(nonsense=1)
+    with pytest.raises(TypeError, match="nonsense"):
+        A.tune(gs_order=1, nonsense=1)
+    with pytest.raises(AssertionError, match="the library was asked"):
+        A.tune(gs_order=1)
