@@ -414,7 +414,7 @@ int pamg_min_blocks_f64(int32_t n_blocks, int32_t blocksize, const double *Sx, i
 int pamg_evolution_strength_vector_f64(double *Sx, int Sx_size, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,
                                        int32_t nrows, const double *d, int d_size, const double *b, int b_size);
 
-/* Energy-minimisation prolongation smoothing with CG (csrc/pamg_energy.hip, the arithmetic in csrc/pamg_energy.h).  float64, HOST
+/* Energy-minimisation prolongation smoothing with CG and GMRES (csrc/pamg_energy.hip, the arithmetic in csrc/pamg_energy.h).  float64, HOST
  * arrays; blocks are row-major and at most 6 x 6, at most 6 candidates (beyond: PAMG_E_UNSUPPORTED).  Patterns are checked as above
  * before anything is written.
  *
@@ -451,6 +451,20 @@ int pamg_energy_cg_f64(int32_t n_brow, int32_t n_bcol, int32_t r, int32_t c, int
                        const int32_t *Sj, int Sj_size, double *Tx, int64_t Tx_size, const double *B, int B_size,
                        const double *BtBinv, int64_t BtBinv_size, const double *Dinv, int Dinv_size, const unsigned char *cmask,
                        const double *PIx, int32_t maxiter, double tol, int32_t *iterations, double *newsums, int32_t *n_newsums);
+/* The loop of gmres_prolongation_smoothing (smooth.py:700-872) resident on the device, for the non-symmetric operators the CG above
+ * does not take; the arguments up to tol as for pamg_energy_cg_f64.  The Krylov basis V_0 .. V_maxiter stays in HBM (maxiter + 1 arrays
+ * of the pattern's size: maxiter > 32 is PAMG_E_UNSUPPORTED); modified Gram-Schmidt, the Hessenberg column, the Givens rotations and g
+ * run on the device, the triangular solve (at most maxiter x maxiter) on the host, one last kernel forms T and resets the C-point
+ * rows -- also when no iteration ran.  iterations <- the columns built; normrs[0 .. *n_normrs) <- the initial residual norm and the one
+ * after every iteration (room for maxiter + 1 values); H (may be NULL) <- the rotated Hessenberg matrix, (maxiter + 1)^2 row-major.
+ * The Frobenius inner products are summed by the fixed tree of the CG driver: the result depends on the operands alone and agrees
+ * with the reference's summation order to rounding.  Per iteration one int is read back. */
+int pamg_energy_gmres_f64(int32_t n_brow, int32_t n_bcol, int32_t r, int32_t c, int32_t NullDim, const int32_t *Ap, int Ap_size,
+                          const int32_t *Aj, int Aj_size, const double *Ax, int64_t Ax_size, const int32_t *Sp, int Sp_size,
+                          const int32_t *Sj, int Sj_size, double *Tx, int64_t Tx_size, const double *B, int B_size,
+                          const double *BtBinv, int64_t BtBinv_size, const double *Dinv, int Dinv_size, const unsigned char *cmask,
+                          const double *PIx, int32_t maxiter, double tol, int32_t *iterations, double *normrs, int32_t *n_normrs,
+                          double *H);
 
 /* ------------------------------------------------------ Layer 2: resident engine (HBM) */
 /* Operator handle: uploads CSR/BSR arrays (HOST pointers) to HBM once and analyses them

@@ -138,6 +138,8 @@ def _declare(lib):
     f("pamg_satisfy_constraints_f64", _i, _i, _i, _i, *(_vp, _i) * 5)
     f("pamg_energy_cg_f64", _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, C.c_int64, _vp, _i, _vp, _i, _vp, C.c_int64, _vp, _i, _vp, C.c_int64,
       _vp, _i, _vp, _vp, _i, _d, P(_i), _vp, P(_i))
+    f("pamg_energy_gmres_f64", _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, C.c_int64, _vp, _i, _vp, _i, _vp, C.c_int64, _vp, _i, _vp, C.c_int64,
+      _vp, _i, _vp, _vp, _i, _d, P(_i), _vp, P(_i), _vp)
     f("pamg_fit_tentative_f64", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d)
     f("pamg_fit_tentative_f32", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float)
     f("pamg_matrix_create", P(_vp), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp)

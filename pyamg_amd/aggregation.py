@@ -762,7 +762,7 @@ _CLASSICAL_NAMES = ("classical_strength_of_connection", "direct_interpolation", 
 
 @contextlib.contextmanager
 def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False, evolution=False,
-                 energy=False):
+                 energy=False, energy_gmres=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -801,8 +801,15 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     where ``energy_prolongation_smoother`` -- the only smoother ``rootnode_solver`` accepts -- resolves them: the CG loop then runs resident
     on the device.  ``satisfy_constraints`` is the reference's bit for bit; the CG result agrees to rounding (its two inner products are
     summed in a fixed tree, not in SciPy's order: ``pyamg_amd.energy``).  ``weighting='block'``, complex or float32 operands and whatever
-    else the device path does not take go to the function that was patched out; the CGNR and GMRES variants are not touched.  Off by
-    default for the reason given for ``classical``.  With ``energy=False`` nothing changes and ``pyamg_amd.energy`` is not imported."""
+    else the device path does not take go to the function that was patched out; the CGNR variant is not touched, the GMRES one only
+    by ``energy_gmres``.  Off by default for the reason given for ``classical``.
+    ``energy_gmres=True`` routes ``gmres_prolongation_smoothing`` and ``satisfy_constraints`` to ``pyamg_amd.energy`` in the same module: the
+    GMRES loop that ``energy_prolongation_smoother`` runs for non-symmetric operators (``krylov='gmres'``, with ``symmetry='nonsymmetric'``
+    once on A for P and once on ``A^H`` for R) then keeps its Krylov basis, the modified Gram-Schmidt passes, the Hessenberg column and the
+    rotations on the device; the triangular solve stays on the host.  The result agrees with the reference to rounding, for the reason
+    given for CG.  ``weighting='block'``, ``maxiter`` above 32 and whatever else CG refuses go to the function that was patched out; CGNR
+    is not touched.  It is a keyword of its own so that ``energy=True`` keeps patching exactly its two names; both together patch three.
+    With both off nothing of ``<pyamg>.aggregation.smooth`` is touched on their account and ``pyamg_amd.energy`` is not imported."""
     import importlib
     from . import air as _air
     from . import classical as _cls
@@ -819,10 +826,11 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                           for mod in ("strength", "aggregation.aggregation", "aggregation.rootnode", "aggregation.adaptive",
                                       "classical.classical", "classical.air"))
     energy_table = ()
-    if energy:
+    if energy or energy_gmres:
         from . import energy as _en
-        energy_table = (("aggregation.smooth", "cg_prolongation_smoothing", _en.cg_prolongation_smoothing),
-                        ("aggregation.smooth", "satisfy_constraints", _en.satisfy_constraints))
+        energy_table = ((("aggregation.smooth", "cg_prolongation_smoothing", _en.cg_prolongation_smoothing),) if energy else ()) + \
+                       ((("aggregation.smooth", "gmres_prolongation_smoothing", _en.gmres_prolongation_smoothing),) if energy_gmres else ()) + \
+                       (("aggregation.smooth", "satisfy_constraints", _en.satisfy_constraints),)
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
                           ("aggregation.aggregation", "richardson_prolongation_smoother", richardson_prolongation_smoother),

@@ -21,7 +21,7 @@ __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_
            "rs_classical_interpolation_pass1", "rs_classical_interpolation_pass2",
            "one_point_interpolation", "approx_ideal_restriction_pass1", "approx_ideal_restriction_pass2",
            "incomplete_mat_mult_csr", "evolution_strength_helper", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
-           "evolution_strength_vector", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "satisfy_constraints", "energy_cg"]
+           "evolution_strength_vector", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "satisfy_constraints", "energy_cg", "energy_gmres"]
 
 
 def _sfx(Ax, *vals):
@@ -420,10 +420,7 @@ def satisfy_constraints(rows_per_block, cols_per_block, num_block_rows, NullDim,
                                                       *_pairs(B, BtBinv, Sp, Sj, Sx)), "satisfy_constraints")
 
 
-def energy_cg(n_brow, n_bcol, r, c, NullDim, Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, Dinv, cmask, PIx, maxiter, tol):
-    """The loop of cg_prolongation_smoothing resident on the device (pamg_energy_cg_f64): Tx, T expanded onto the pattern Sp / Sj, is
-    smoothed in place; returns (iterations done, the newsum of every iteration)."""
-    import ctypes
+def _energy_driver_arguments(n_brow, r, Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, Dinv, cmask, PIx):
     _idx(Ap, Aj, Sp, Sj)
     _f64(Ax, Tx, B, BtBinv, Dinv)
     if (cmask is None) != (PIx is None):
@@ -432,9 +429,35 @@ def energy_cg(n_brow, n_bcol, r, c, NullDim, Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, 
         _f64(PIx)
         if not isinstance(cmask, np.ndarray) or cmask.dtype != np.uint8 or not cmask.flags.c_contiguous or cmask.size != n_brow * r or PIx.size != Tx.size:
             raise TypeError("incompatible function arguments (cmask: contiguous uint8 per row, PIx: like Tx)")
+
+
+def energy_cg(n_brow, n_bcol, r, c, NullDim, Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, Dinv, cmask, PIx, maxiter, tol):
+    """The loop of cg_prolongation_smoothing resident on the device (pamg_energy_cg_f64): Tx, T expanded onto the pattern Sp / Sj, is
+    smoothed in place; returns (iterations done, the newsum of every iteration)."""
+    import ctypes
+    _energy_driver_arguments(n_brow, r, Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, Dinv, cmask, PIx)
     its, ns = ctypes.c_int(0), ctypes.c_int(0)
     sums = np.zeros(max(int(maxiter), 1))
     p = capi.ptr
     capi.check(capi.lib().pamg_energy_cg_f64(int(n_brow), int(n_bcol), int(r), int(c), int(NullDim), *_pairs(Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, Dinv),
                                             p(cmask), p(PIx), int(maxiter), float(tol), ctypes.byref(its), p(sums), ctypes.byref(ns)), "energy_cg")
     return int(its.value), sums[:int(ns.value)].copy()
+
+
+def energy_gmres(n_brow, n_bcol, r, c, NullDim, Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, Dinv, cmask, PIx, maxiter, tol, H=None):
+    """The loop of gmres_prolongation_smoothing resident on the device (pamg_energy_gmres_f64), the arguments as for ``energy_cg``: Tx is
+    smoothed in place; returns (iterations done, the normr history: the initial norm first, then the one after every iteration).
+    ``H``, a contiguous float64 array of (maxiter + 1)^2 values, receives the rotated Hessenberg matrix."""
+    import ctypes
+    _energy_driver_arguments(n_brow, r, Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, Dinv, cmask, PIx)
+    if H is not None:
+        _f64(H)
+        if H.size != (max(int(maxiter), 0) + 1) ** 2:
+            raise TypeError("incompatible function arguments (H: (maxiter + 1)^2 values)")
+    its, ns = ctypes.c_int(0), ctypes.c_int(0)
+    normrs = np.zeros(max(int(maxiter), 0) + 1)
+    p = capi.ptr
+    capi.check(capi.lib().pamg_energy_gmres_f64(int(n_brow), int(n_bcol), int(r), int(c), int(NullDim), *_pairs(Ap, Aj, Ax, Sp, Sj, Tx, B, BtBinv, Dinv),
+                                               p(cmask), p(PIx), int(maxiter), float(tol), ctypes.byref(its), p(normrs), ctypes.byref(ns), p(H)),
+               "energy_gmres")
+    return int(its.value), normrs[:int(ns.value)].copy()

@@ -291,5 +291,23 @@ PYBIND11_MODULE(_amg_core_pybind, m)
     }, py::arg("n_brow"), py::arg("n_bcol"), py::arg("r"), py::arg("c"), py::arg("NullDim"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Sp"), nc("Sj"), nc("Tx"),
        nc("B"), nc("BtBinv"), nc("Dinv"), py::arg("cmask").noconvert().none(true), py::arg("PIx").noconvert().none(true), py::arg("maxiter"),
        py::arg("tol"));
+    // Returns (iterations, the normr history: the initial norm first); H, if given, receives the rotated Hessenberg matrix
+    m.def("energy_gmres", [](int n_brow, int n_bcol, int r, int c, int NullDim, Idx &Ap, Idx &Aj, D &Ax, Idx &Sp, Idx &Sj, D &Tx, D &B, D &BtBinv, D &Dinv,
+                             std::optional<py::array_t<unsigned char, py::array::c_style>> cmask, std::optional<D> PIx, int maxiter, double tol,
+                             std::optional<D> H) {
+        if (cmask.has_value() != PIx.has_value() || (cmask && (cmask->size() != (py::ssize_t)n_brow * r || PIx->size() != Tx.size())))
+            throw py::type_error("energy_gmres(): cmask (one byte per row) and PIx (like Tx) go together");
+        const py::ssize_t ld = std::max(maxiter, 0) + 1;
+        if (H && H->size() != ld * ld) throw py::type_error("energy_gmres(): H takes (maxiter + 1)^2 values");
+        std::vector<double> normrs((size_t)ld);
+        int its = 0, ns = 0;
+        done(pamg_energy_gmres_f64(n_brow, n_bcol, r, c, NullDim, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), (int64_t)Ax.size(), Sp.data(),
+                                   len(Sp), Sj.data(), len(Sj), Tx.mutable_data(), (int64_t)Tx.size(), B.data(), len(B), BtBinv.data(),
+                                   (int64_t)BtBinv.size(), Dinv.data(), len(Dinv), cmask ? cmask->data() : nullptr, PIx ? PIx->data() : nullptr, maxiter,
+                                   tol, &its, normrs.data(), &ns, H ? H->mutable_data() : nullptr), "energy_gmres");
+        return py::make_tuple(its, py::array_t<double>(ns, normrs.data()));
+    }, py::arg("n_brow"), py::arg("n_bcol"), py::arg("r"), py::arg("c"), py::arg("NullDim"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Sp"), nc("Sj"), nc("Tx"),
+       nc("B"), nc("BtBinv"), nc("Dinv"), py::arg("cmask").noconvert().none(true), py::arg("PIx").noconvert().none(true), py::arg("maxiter"),
+       py::arg("tol"), py::arg("H").noconvert().none(true) = py::none());
     m.def("version", [] { return std::string(pamg_version()); });
 }

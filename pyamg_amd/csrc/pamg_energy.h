@@ -1,5 +1,5 @@
-// pamg_energy.h -- the per-element arithmetic of energy-minimisation prolongation smoothing (CG), shared by the kernels of
-// pamg_energy.hip and the host replay tests/energy_emul.cpp (lanes, groups and workgroups as loops), as pamg_air.h is shared by the AIR
+// pamg_energy.h -- the per-element arithmetic of energy-minimisation prolongation smoothing (CG, GMRES), shared by the kernels of
+// pamg_energy.hip and the host replays tests/energy_emul.cpp and tests/energy_gmres_emul.cpp (lanes, groups and workgroups as loops), as pamg_air.h is shared by the AIR
 // setup.  Blocks are row-major: A r x m, B (the operand, T or P) m x c, S r x c; the candidates Bc are [n_bcol * c] x K row-major.
 //
 //   imm_entry      element (a, d) of the block S(i, col) of incomplete_mat_mult_bsr (smoothed_aggregation.h:970-1042): the contributions
@@ -17,6 +17,7 @@
 //
 // Every sum runs serially in the reference's order, so with -ffp-contract=off the first three are the reference's bit for bit.
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -234,6 +235,153 @@ inline int64_t chunks(int64_t n) { return (n + RED_CHUNK - 1) / RED_CHUNK; }
 // what the loop of cg_prolongation_smoothing does at its head (smooth.py:381-392) with the reduced values: 2 = `resid > tol` fails
 // (resid: the stored size of R, zero blocks dropped as SciPy's subtraction drops them), 1 = newsum < tol, 0 = go on
 PAMG_EN_HD int cg_stop(double resid, double newsum, double tol) { return !(resid > tol) ? 2 : (newsum < tol ? 1 : 0); }
+
+// ---- GMRES (gmres_prolongation_smoothing, smooth.py:648-872).  Local to a block row it is the CG driver's arithmetic with the row
+// weights applied where scale_rows applies them (on the product, before the projection); the element-wise updates are the
+// reference's expressions; the Frobenius inner products go through the tree above; the Hessenberg column, the rotations and g are one
+// function that a single lane runs on the device and the replay calls as it is.
+constexpr int GMRES_MAXITER = 32, GMRES_LD = GMRES_MAXITER + 1;
+
+// the row of Dinv (A V) on the pattern from 0.0 (negate: Dinv (-(A T)), the initial residual), not yet projected
+template <class BV>
+PAMG_EN_HD void imm_scaled_lane(int lane, int gw, int i, const int *Ap, const int *Aj, const double *Ax, BV bval, const int *Sp, const int *Sj,
+                                const double *Dinv, double *Sout, bool negate, int r, int c)
+{
+    const int rc = r * c, len = (Sp[i + 1] - Sp[i]) * rc;
+    for (int e = lane; e < len; e += gw) {
+        const int p = Sp[i] + e / rc, a = (e % rc) / c, d = e % c;
+        double v = imm_entry(0.0, i, Sj[p], a, d, Ap, Aj, Ax, Sp, Sj, bval, r, r);
+        if (negate) v *= -1.0;
+        Sout[(int64_t)Sp[i] * rc + e] = v * Dinv[(int64_t)i * r + a];
+    }
+}
+
+// W -= h V (modified Gram-Schmidt: h was taken on the W that comes in)
+PAMG_EN_HD void mgs_lane(int lane, int gw, int i, const int *Sp, double *W, const double *V, double h, int r, int c)
+{
+    const int rc = r * c, len = (Sp[i + 1] - Sp[i]) * rc;
+    for (int e = lane; e < len; e += gw) {
+        const int64_t at = (int64_t)Sp[i] * rc + e;
+        const double hv = h * V[at];
+        W[at] = W[at] - hv;
+    }
+}
+
+// V = s V: the first basis vector (s = 1.0 / normr) and the normalisation (s = 1.0 / H[i+1, i])
+PAMG_EN_HD void scale_lane(int lane, int gw, int i, const int *Sp, double *V, double s, int r, int c)
+{
+    const int rc = r * c, len = (Sp[i + 1] - Sp[i]) * rc;
+    for (int e = lane; e < len; e += gw) {
+        const int64_t at = (int64_t)Sp[i] * rc + e;
+        V[at] = s * V[at];
+    }
+}
+
+// T = T + y[j] V_j for j ascending (V_j = V + j * stride), then the C-point rows reset to the injection's (T = I_F T + P_I)
+PAMG_EN_HD void combine_lane(int lane, int gw, int i, const int *Sp, double *T, const double *V, int64_t stride, const double *y, int ny,
+                             const unsigned char *cmask, const double *PI, int r, int c)
+{
+    const int rc = r * c, len = (Sp[i + 1] - Sp[i]) * rc;
+    for (int e = lane; e < len; e += gw) {
+        const int64_t at = (int64_t)Sp[i] * rc + e;
+        double t = T[at];
+        for (int j = 0; j < ny; ++j) {
+            const double yv = y[j] * V[(int64_t)j * stride + at];
+            t = t + yv;
+        }
+        if (cmask && cmask[(int64_t)i * r + (e % rc) / c]) t = PI[at];
+        T[at] = t;
+    }
+}
+
+// the Krylov side's scalars: H as the reference holds it (row-major, leading dimension GMRES_LD), the rotations, g, the normr history
+struct GmresState {
+    double H[GMRES_LD * GMRES_LD], g[GMRES_LD], normr[GMRES_LD], Qc[GMRES_MAXITER], Qs[GMRES_MAXITER];
+    double h;                                               // the coefficient of the next Gram-Schmidt pass
+    double scale;                                           // what the newest basis vector is multiplied by, if `scaled`
+    int scaled, nq, iterations, stop;
+};
+
+// after the initial residual: total = <R, R>.  g[0] = normr; V_0 = (1.0 / normr) R if normr > 0.0; the loop's head
+PAMG_EN_HD void gmres_start(GmresState &S, double total, int maxiter, double tol)
+{
+    const double normr = std::sqrt(total);
+    S.g[0] = normr;
+    S.normr[0] = normr;
+    S.scaled = normr > 0.0;
+    S.scale = S.scaled ? 1.0 / normr : 0.0;
+    S.nq = 0;
+    S.iterations = 0;
+    S.stop = !(0 < maxiter && normr > tol && S.scaled);
+}
+
+// H[j, i] = <V_j, W>: kept, and handed to the pass that subtracts with it
+PAMG_EN_HD void gmres_coefficient(GmresState &S, int j, int i, double total)
+{
+    S.H[j * GMRES_LD + i] = total;
+    S.h = total;
+}
+
+// the end of iteration i (smooth.py:816-854): total = <W, W> after the last Gram-Schmidt pass
+PAMG_EN_HD void gmres_column(GmresState &S, int i, double total, int maxiter, double tol)
+{
+    double *H = S.H;
+    const int L = GMRES_LD;
+    H[(i + 1) * L + i] = std::sqrt(total);
+    S.scaled = H[(i + 1) * L + i] != 0.0;                   // the breakdown check
+    S.scale = S.scaled ? 1.0 / H[(i + 1) * L + i] : 0.0;
+    for (int j = 0; j < S.nq && j < i; ++j) {               // apply_givens(Q, H[:, i], i)
+        const double v0 = H[j * L + i], v1 = H[(j + 1) * L + i];
+        const double a0 = S.Qc[j] * v0, a1 = S.Qs[j] * v1, b0 = -S.Qs[j] * v0, b1 = S.Qc[j] * v1;
+        H[j * L + i] = a0 + a1;
+        H[(j + 1) * L + i] = b0 + b1;
+    }
+    if (H[(i + 1) * L + i] != 0.0) {
+        const double h1 = H[i * L + i], h2 = H[(i + 1) * L + i];
+        const double h1_mag = std::fabs(h1), h2_mag = std::fabs(h2);
+        double mu, tau;
+        if (h1_mag < h2_mag) {
+            mu = h1 / h2;
+            tau = mu / std::fabs(mu);
+        } else {
+            mu = h2 / h1;
+            tau = mu / std::fabs(mu);
+        }
+        const double q1 = h1_mag * h1_mag, q2 = h2_mag * h2_mag;
+        const double denom = std::sqrt(q1 + q2);
+        const double c = h1_mag / denom;
+        const double st = h2_mag * tau;
+        const double s = st / denom;
+        S.Qc[S.nq] = c;
+        S.Qs[S.nq] = s;
+        ++S.nq;
+        const double g0 = S.g[i], g1 = S.g[i + 1];
+        const double a0 = c * g0, a1 = s * g1, b0 = -s * g0, b1 = c * g1;
+        S.g[i] = a0 + a1;
+        S.g[i + 1] = b0 + b1;
+        const double c0 = c * h1, c1 = s * h2;
+        H[i * L + i] = c0 + c1;
+        H[(i + 1) * L + i] = 0.0;
+    }
+    const double normr = std::fabs(S.g[i + 1]);
+    S.normr[i + 1] = normr;
+    S.iterations = i + 1;
+    S.stop = !(i + 1 < maxiter && normr > tol);
+}
+
+// y = H[0:k, 0:k]^-1 g[0:k] for the upper triangular H the rotations leave (what la.solve's LU without a row exchange comes to):
+// back substitution, column by column
+inline void gmres_solve(const GmresState &S, int k, double *y)
+{
+    for (int j = 0; j < k; ++j) y[j] = S.g[j];
+    for (int j = k - 1; j >= 0; --j) {
+        y[j] = y[j] / S.H[j * GMRES_LD + j];
+        for (int q = 0; q < j; ++q) {
+            const double t = y[j] * S.H[q * GMRES_LD + j];
+            y[q] = y[q] - t;
+        }
+    }
+}
 
 }  // namespace energy
 }  // namespace pamg

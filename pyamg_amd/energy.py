@@ -1,7 +1,8 @@
-"""Energy-minimisation prolongation smoothing with CG on the device: drop-ins for the reference's
+"""Energy-minimisation prolongation smoothing with CG and GMRES on the device: drop-ins for the reference's
 
-* ``satisfy_constraints``          -- pyamg/aggregation/smooth.py:17-58
-* ``cg_prolongation_smoothing``    -- pyamg/aggregation/smooth.py:275-442
+* ``satisfy_constraints``             -- pyamg/aggregation/smooth.py:17-58
+* ``cg_prolongation_smoothing``       -- pyamg/aggregation/smooth.py:275-442
+* ``gmres_prolongation_smoothing``    -- pyamg/aggregation/smooth.py:648-872
 
 with the reference's signatures.  The kernels are csrc/pamg_energy.hip, their arithmetic csrc/pamg_energy.h.
 
@@ -17,10 +18,19 @@ bit.  The row weights ``Dinv`` are formed on the host with the reference's own e
 The loop's head is the reference's: it runs while ``i < maxiter`` and the stored size of R exceeds ``tol`` (R's all-zero blocks not
 counted, as SciPy's subtraction drops them), and leaves at the first ``newsum < tol``.
 
+``gmres_prolongation_smoothing`` is the same for non-symmetric operators: the Krylov basis ``V_0 .. V_maxiter`` lives on the pattern's
+structure in HBM, the modified Gram-Schmidt coefficients ``H[j, i] = <V_j, W>`` are taken one after the other on the already updated W
+through the same fixed tree, the Hessenberg column, the Givens rotations, ``g`` and ``normr`` are the reference's real-arithmetic
+statements run by one lane, and one int comes back per iteration.  The triangular solve (at most ``maxiter x maxiter``) is done on
+the host, ``y`` goes up, and one kernel forms ``T + sum y[j] V_j`` and resets the C-point rows -- also when no iteration ran
+(``normr <= tol``).  It runs ``while i < maxiter - 1 and normr > tol`` from ``i = -1``; the breakdown branch (``H[i+1, i] == 0.0``: no
+normalisation, no rotation, ``normr = 0``) is the reference's.  T and the ``normr`` history agree with the reference to rounding.
+
 What the device path does not take raises ``NotImplementedError`` before a device call: ``weighting='block'``, non-float64 or complex
 operands, inputs that are not BSR / CSR, a pattern that does not contain T's structure (or, with root nodes, the injection's), index
-arrays beyond int32, blocks larger than 6 x 6 or more than 6 candidates.  ``aggregation.device_setup(pyamg, energy=True)`` then
-hands the call to the reference function it patched out.
+arrays beyond int32, blocks larger than 6 x 6 or more than 6 candidates, and for GMRES ``maxiter`` above 32 (the basis).
+``aggregation.device_setup(pyamg, energy=True)`` / ``(pyamg, energy_gmres=True)`` then hands the call to the reference function it
+patched out.
 """
 from __future__ import annotations
 
@@ -30,10 +40,11 @@ import scipy.sparse as sp
 from . import amg_core
 from .classical import _i32
 
-__all__ = ["satisfy_constraints", "cg_prolongation_smoothing"]
+__all__ = ["satisfy_constraints", "cg_prolongation_smoothing", "gmres_prolongation_smoothing"]
 
 MAX_BLOCK = 6
 MAX_NULLDIM = 6
+GMRES_MAXITER = 32                                          # the basis is maxiter + 1 arrays of the pattern's size
 
 
 def _bsr(M, what):
@@ -78,29 +89,26 @@ def satisfy_constraints(U, B, BtBinv):
     return U
 
 
-def _expand(M, pattern, keys, order, what):
+def _expand(M, pattern, keys, order, what, fn):
     """the block values of M on the pattern's structure (zero blocks where M stores nothing); M's structure must lie inside"""
     r, c = pattern.blocksize
     if M.blocksize != (r, c) or M.shape != pattern.shape:
-        raise NotImplementedError(f"cg_prolongation_smoothing on the device: {what} and the pattern differ in shape or block size")
+        raise NotImplementedError(f"{fn} on the device: {what} and the pattern differ in shape or block size")
     nbc = pattern.shape[1] // c
     rows = np.repeat(np.arange(M.indptr.size - 1, dtype=np.int64), np.diff(M.indptr))
     mk = rows * nbc + M.indices
     at = np.searchsorted(keys, mk)
     if mk.size and (at.max(initial=0) >= keys.size or not np.array_equal(keys[np.minimum(at, keys.size - 1)], mk)):
-        raise NotImplementedError(f"cg_prolongation_smoothing on the device: the pattern does not contain the structure of {what}")
+        raise NotImplementedError(f"{fn} on the device: the pattern does not contain the structure of {what}")
     out = np.zeros(pattern.data.shape, dtype=np.float64)
     out[order[at]] = M.data
     return out
 
 
-def cg_prolongation_smoothing(A, T, B, BtBinv, pattern, maxiter, tol, weighting="local", Cpt_params=None):
-    """pyamg.aggregation.smooth.cg_prolongation_smoothing: smooth T with CG on ``A T = 0`` inside ``pattern``, keeping ``T @ B``.
-
-    Returns a ``bsr_array`` with T's block size on the pattern's structure.  The reference's SciPy additions drop all-zero blocks;
-    this one may hold explicit zero blocks, which the caller's ``T.eliminate_zeros()`` removes (``energy_prolongation_smoother`` calls
-    it right after).  The module docstring says what is bit for bit and what agrees to rounding."""
-    what = "cg_prolongation_smoothing"
+def _prepare(what, A, T, B, BtBinv, pattern, weighting, Cpt_params):
+    """what the Krylov drop-ins share before their device call: the checks, T (and with root nodes the injection P_I) expanded onto the
+    pattern, the C-point byte per row.  Returns the arguments of ``amg_core.energy_cg`` / ``energy_gmres`` up to PIx (Dinv left out: it
+    is formed after this, as the reference forms it after its allocations), the pattern and T as BSR"""
     if weighting == "block":
         raise NotImplementedError(f"{what}(weighting='block') is not on the device path")
     if weighting not in ("diagonal", "local"):
@@ -130,20 +138,25 @@ def cg_prolongation_smoothing(A, T, B, BtBinv, pattern, maxiter, tol, weighting=
         keys = keys[order]
         if np.any(keys[1:] == keys[:-1]):
             raise NotImplementedError(f"{what} on the device: the pattern stores a block twice")
-    Tx = _expand(T_, pat, keys, order, "T")
+    Tx = _expand(T_, pat, keys, order, "T", what)
     cmask = PIx = None
     if Cpt_params is not None and Cpt_params[0]:
         P_I = Cpt_params[1]["P_I"]
         I_F = Cpt_params[1]["I_F"]
-        PIx = _expand(_bsr(sp.bsr_array(P_I, blocksize=(r, c)) if sp.issparse(P_I) else P_I, what), pat, keys, order, "P_I").ravel()
+        PIx = _expand(_bsr(sp.bsr_array(P_I, blocksize=(r, c)) if sp.issparse(P_I) else P_I, what), pat, keys, order, "P_I", what).ravel()
         if not sp.issparse(I_F) or I_F.dtype != np.float64:
             raise NotImplementedError(f"{what} on the device takes I_F as a float64 sparse matrix")
         dF = I_F.diagonal()
         if I_F.count_nonzero() != np.count_nonzero(dF) or np.any((dF != 0.0) & (dF != 1.0)):        # I_F must be the identity on the F rows and nothing else
             raise NotImplementedError(f"{what} on the device takes I_F as an identity with the C-point rows removed")
         cmask = np.ascontiguousarray(dF == 0.0, dtype=np.uint8)
+    head = (n, nbc, r, c, K, Ap, Aj, np.ascontiguousarray(np.ravel(A_.data)), Sp, Sj, Tx.ravel(), np.ascontiguousarray(np.ravel(B)),
+            np.ascontiguousarray(np.ravel(BtBinv)))
+    return head, (cmask, PIx), pat, T_
 
-    # the row weights, with the reference's expressions (smooth.py:332-343, util.utils.get_diagonal)
+
+def _row_weights(A, weighting):
+    """Dinv with the reference's expressions (smooth.py:332-343 and :717-728, util.utils.get_diagonal)"""
     if weighting == "diagonal":
         A.sort_indices()
         D = A.diagonal()
@@ -154,14 +167,44 @@ def cg_prolongation_smoothing(A, T, B, BtBinv, pattern, maxiter, tol, weighting=
         D = np.abs(A) @ np.ones((A.shape[0], 1), dtype=A.dtype)
         Dinv = np.zeros_like(D)
         Dinv[D != 0] = 1.0 / np.abs(D[D != 0])
-    Dinv = np.ascontiguousarray(np.ravel(Dinv), dtype=np.float64)
+    return np.ascontiguousarray(np.ravel(Dinv), dtype=np.float64)
 
-    if pat.indices.size == 0:                               # R.nnz == 0: R lives on the pattern, explicit zeros included
-        print("Error in sa_energy_min(..).  Initial R no nonzeros on a level. "
-              "Returning tentative prolongator\n")
+
+def _empty_pattern(pat):
+    """R.nnz == 0 (R lives on the pattern, explicit zeros included): the reference's message; the caller returns the tentative T"""
+    if pat.indices.size:
+        return False
+    print("Error in sa_energy_min(..).  Initial R no nonzeros on a level. "
+          "Returning tentative prolongator\n")
+    return True
+
+
+def _smooth(what, driver, cap, A, T, B, BtBinv, pattern, maxiter, tol, weighting, Cpt_params):
+    """a Krylov drop-in: the preparation, ``amg_core.<driver>`` on T expanded onto the pattern, and the result on the pattern's structure"""
+    head, rooted, pat, T_ = _prepare(what, A, T, B, BtBinv, pattern, weighting, Cpt_params)
+    if cap is not None and int(maxiter) > cap:
+        raise NotImplementedError(f"{what} on the device keeps at most {cap} + 1 basis vectors (maxiter {maxiter})")
+    Dinv = _row_weights(A, weighting)
+    if _empty_pattern(pat):
         return T
+    getattr(amg_core, driver)(*head, Dinv, *rooted, int(maxiter), float(tol))
+    Tx = head[10]                                           # smoothed in place
+    return sp.bsr_array((Tx.reshape(-1, *T_.blocksize), pat.indices.copy(), pat.indptr.copy()), shape=T_.shape)
 
-    Tx = Tx.ravel()
-    amg_core.energy_cg(n, nbc, r, c, K, Ap, Aj, np.ascontiguousarray(np.ravel(A_.data)), Sp, Sj, Tx, np.ascontiguousarray(np.ravel(B)),
-                       np.ascontiguousarray(np.ravel(BtBinv)), Dinv, cmask, PIx, int(maxiter), float(tol))
-    return sp.bsr_array((Tx.reshape(-1, r, c), pat.indices.copy(), pat.indptr.copy()), shape=T_.shape)
+
+def cg_prolongation_smoothing(A, T, B, BtBinv, pattern, maxiter, tol, weighting="local", Cpt_params=None):
+    """pyamg.aggregation.smooth.cg_prolongation_smoothing: smooth T with CG on ``A T = 0`` inside ``pattern``, keeping ``T @ B``.
+
+    Returns a ``bsr_array`` with T's block size on the pattern's structure.  The reference's SciPy additions drop all-zero blocks;
+    this one may hold explicit zero blocks, which the caller's ``T.eliminate_zeros()`` removes (``energy_prolongation_smoother`` calls
+    it right after).  The module docstring says what is bit for bit and what agrees to rounding."""
+    return _smooth("cg_prolongation_smoothing", "energy_cg", None, A, T, B, BtBinv, pattern, maxiter, tol, weighting, Cpt_params)
+
+
+def gmres_prolongation_smoothing(A, T, B, BtBinv, pattern, maxiter, tol, weighting="local", Cpt_params=None):
+    """pyamg.aggregation.smooth.gmres_prolongation_smoothing: smooth T with GMRES on ``A T = 0`` inside ``pattern``, keeping ``T @ B`` --
+    what ``energy_prolongation_smoother`` runs for non-symmetric operators, once on A for P and once on ``A^H`` for R.
+
+    Returns a ``bsr_array`` on the pattern's structure, explicit zero blocks possible, as ``cg_prolongation_smoothing`` does.  The Krylov
+    basis costs ``maxiter + 1`` arrays of the pattern's size in HBM; more than ``GMRES_MAXITER`` iterations are not on the device path."""
+    return _smooth("gmres_prolongation_smoothing", "energy_gmres", GMRES_MAXITER, A, T, B, BtBinv, pattern, maxiter, tol, weighting, Cpt_params)

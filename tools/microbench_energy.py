@@ -5,6 +5,10 @@ downloads included: ``pyamg_amd.energy`` on the device, or the reference's funct
   poisson   : the 7-point Laplacian on 128^3, one candidate, root nodes (C-point rows reset)
   elasticity: 3-D linear elasticity (P1 tets, tools/problems.py) on 64^3 vertices, six rigid-body modes, (3,6) blocks
 
+``--krylov gmres`` measures ``gmres_prolongation_smoothing`` instead (maxiter 3, as blackbox.py sets it), on
+
+  convdiff  : first-order upwind convection-diffusion on 1024^2 (epsilon 0.01, flow at 36 degrees: not symmetric), one candidate
+
 The arguments are built here the way ``energy_prolongation_smoother`` builds them (degree 1) -- symmetric strength (theta 0),
 standard aggregation, the tentative prolongator, the pattern ``C @ T``, ``BtBinv`` -- from this package's device functions where
 there is a GPU and from the reference's where there is oracle/_ref; the aggregates and T are the same arrays on either side.  A
@@ -13,6 +17,7 @@ columns then come from two hosts and no ratio is recorded.  Medians of --runs ca
 
     python tools/microbench_energy.py [--small]              # -> profiles/r15_energy_cg.json  (--out DIR: somewhere else)
     python tools/microbench_energy.py --once poisson         # one device call and nothing else: the command to put under rocprofv3
+    python tools/microbench_energy.py --krylov gmres [--small | --once convdiff]         # -> profiles/r16_energy_gmres.json
 
 Not product code."""
 import argparse
@@ -30,12 +35,14 @@ sys.path.insert(0, str(ROOT))
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--runs", type=int, default=5)
-ap.add_argument("--small", action="store_true", help="24^3 and 10^3: a rehearsal of the code path, not a measurement")
-ap.add_argument("--once", choices=["poisson", "elasticity"])
+ap.add_argument("--small", action="store_true", help="24^3, 10^3 and 48^2: a rehearsal of the code path, not a measurement")
+ap.add_argument("--krylov", choices=["cg", "gmres"], default="cg")
+ap.add_argument("--once", choices=["poisson", "elasticity", "convdiff"])
 ap.add_argument("--side", choices=["device", "reference"])
 ap.add_argument("--out", default=str(ROOT / "profiles"))
 a = ap.parse_args()
-OUT = Path(a.out) / "r15_energy_cg.json"
+OUT = Path(a.out) / ("r15_energy_cg.json" if a.krylov == "cg" else "r16_energy_gmres.json")
+MAXITER = 4 if a.krylov == "cg" else 3
 
 from pyamg_amd import _capi as capi  # noqa: E402
 import oracle.refimport as ri  # noqa: E402
@@ -67,8 +74,22 @@ def btbinv(B, pattern):
     return np.linalg.pinv((rows @ BtB).reshape(-1, K, K), hermitian=True)
 
 
+def upwind2d(n, epsilon=0.01, degrees=36.0):
+    """-epsilon Laplace(u) + w . grad(u) on n x n points, w = (cos, sin) of the flow angle, backward differences for the convection"""
+    h = 1.0 / (n + 1)
+    e = np.ones(n)
+    lap = sp.diags_array([-e[:-1], 2 * e, -e[:-1]], offsets=[-1, 0, 1]) * (epsilon / h**2)
+    back = sp.diags_array([-e[:-1], e], offsets=[-1, 0]) / h
+    one = [lap + back * w for w in (np.cos(np.deg2rad(degrees)), np.sin(np.deg2rad(degrees)))]
+    return sp.csr_array(sp.kron(sp.eye_array(n), one[0]) + sp.kron(one[1], sp.eye_array(n)))
+
+
 def arguments(name, device):
-    if name == "poisson":
+    if name == "convdiff":
+        A = upwind2d(48 if a.small else 1024)
+        A = sp.bsr_array((A.data.reshape(-1, 1, 1), A.indices, A.indptr), shape=A.shape)
+        B = np.ones((A.shape[0], 1))
+    elif name == "poisson":
         n = 24 if a.small else 128
         A = sp.csr_array(poisson_csr((n, n, n)))
         A = sp.bsr_array((A.data.reshape(-1, 1, 1), A.indices, A.indptr), shape=A.shape)
@@ -105,19 +126,21 @@ def arguments(name, device):
     T.sort_indices()
     for M in (A, T):
         M.indices, M.indptr = M.indices.astype(np.int32), M.indptr.astype(np.int32)
-    return (A, T, np.ascontiguousarray(Bc), btbinv(np.ascontiguousarray(Bc), pattern), pattern, 4, 1e-8, "local", params)
+    return (A, T, np.ascontiguousarray(Bc), btbinv(np.ascontiguousarray(Bc), pattern), pattern, MAXITER, 1e-8, "local", params)
 
 
-LAYER2 = []                                                 # seconds inside amg_core.energy_cg (uploads, kernels, download) per device call
+LAYER2 = []                                                 # seconds inside amg_core.energy_cg / energy_gmres (uploads, kernels, download) per device call
+ITERATIONS = []                                             # what that call returned first: the iterations done
 if have_gpu:
-    _energy_cg = den.amg_core.energy_cg
-
-    def _timed_energy_cg(*x, **k):
-        t0 = time.perf_counter()
-        out = _energy_cg(*x, **k)
-        LAYER2.append(time.perf_counter() - t0)
-        return out
-    den.amg_core = type("Core", (), {"energy_cg": staticmethod(_timed_energy_cg)})
+    def _timed(driver):
+        def call(*x, **k):
+            t0 = time.perf_counter()
+            out = driver(*x, **k)
+            LAYER2.append(time.perf_counter() - t0)
+            ITERATIONS.append(int(out[0]))
+            return out
+        return staticmethod(call)
+    den.amg_core = type("Core", (), {"energy_cg": _timed(den.amg_core.energy_cg), "energy_gmres": _timed(den.amg_core.energy_gmres)})
 
 
 def timed(fn, args):
@@ -131,8 +154,9 @@ def timed(fn, args):
 
 def measure(name):
     rec = {}
-    for side, have, fn in (("device", have_gpu, den.cg_prolongation_smoothing if have_gpu else None),
-                           ("reference", have_ref, rsm.cg_prolongation_smoothing if have_ref else None)):
+    smoother = f"{a.krylov}_prolongation_smoothing"
+    for side, have, fn in (("device", have_gpu, getattr(den, smoother) if have_gpu else None),
+                           ("reference", have_ref, getattr(rsm, smoother) if have_ref else None)):
         if not have:
             continue
         args = arguments(name, side == "device")
@@ -149,11 +173,12 @@ def measure(name):
                      "abs_sum_T_in": float(np.abs(T.data).sum())}
         if side == "device":
             rec[side]["seconds_in_layer2_call_median"] = statistics.median(LAYER2[-len(times):])
+            rec[side]["iterations"] = ITERATIONS[-1]
         print(name, side, json.dumps(rec[side]), flush=True)
     return rec
 
 
-names = [a.once] if a.once else ["poisson", "elasticity"]
+names = [a.once] if a.once else (["poisson", "elasticity"] if a.krylov == "cg" else ["convdiff"])
 result = {n: measure(n) for n in names}
 if not a.once:
     OUT.parent.mkdir(parents=True, exist_ok=True)
