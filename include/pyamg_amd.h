@@ -545,7 +545,9 @@ int pamg_matrix_info(pamg_matrix_t A, int64_t info[8]);
                                     * its operands until the sweep is one dependency level away, bit 3 the same in the line scan */
 #define PAMG_TUNE_LINE_SCAN 30     /* 0..2; default 1: line-scan form where consecutive swept rows are coupled AND enough lines run side by side to beat
                                     * the lane form by the planner's estimate (3-D grids; not 2-D grids in natural order); 2 = wherever it applies;
-                                    * 0 = off */
+                                    * 0 = off (line layouts already built are freed: pamg_matrix_line_info reports what the next sweep runs; a later 2
+                                    * plans and fills them again).  A change between 1 and 2 keeps layouts that exist, also ones the estimate of 1
+                                    * would decline: the estimate is asked only when a layout is built */
 #define PAMG_TUNE_LANE_MERGE 33    /* 0..8; default 0: MERGED fast order (f64 Gauss-Seidel), that many dependency levels at most eliminated algebraically
                                     * into one super-level, for which the sweep pays one hand-off.  0 = automatic (3 on levels above 131 072 rows, 6
                                     * below, off under 12 entries per row or 8 dependency levels), 1 = never.  Same iterates in exact arithmetic, another

@@ -501,7 +501,9 @@ static int line_launch_t(pamg_matrix_s *A, GsSchedule *g, int epi, void *x, cons
 }
 
 // The fused symmetric sweep (f64 Gauss-Seidel).  No vector is read and written in the same phase, so it would order a structurally
-// non-symmetric pattern too; those keep the two launches with their snapshots all the same, because no test sweeps one through the line form.  PAMG_E_UNSUPPORTED: not applicable.  Grid: the larger of the two directional wishes under the fused kernel's co-residency cap.
+// non-symmetric pattern too; those keep the two launches with their snapshots all the same -- a choice, not an untested corner: the families `k8`
+// and `nonsym_pattern` of tests/line_families.py run the line form as two launches and are held to the reference there.  PAMG_E_UNSUPPORTED: not
+// applicable.  Grid: the larger of the two directional wishes under the fused kernel's co-residency cap.
 int line_sym_launch(pamg_matrix_s *A, GsSchedule *gf, GsSchedule *gb, void *x, const void *b, hipStream_t s)
 {
     LineSched *tf = gf->line, *tb = gb->line;

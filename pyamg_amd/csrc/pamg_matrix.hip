@@ -1404,7 +1404,8 @@ static int sym_form_of(pamg_matrix_s *A, GsSchedule **pf, GsSchedule **pb)
     *pf = gf; *pb = gb;
     const bool lf = want_lines(A, gf), lb = want_lines(A, gb);
     if (lf != lb) return 0;
-    // lines: structurally symmetric patterns only (line_sym_launch says why); the others keep the two launches and their snapshots
+    // lines: structurally symmetric patterns only, by choice (line_sym_launch); the others keep the two launches and their snapshots, which
+    // tests/test_gpu_line_families.py sweeps through the line form (`k8`, `nonsym_pattern`) and asserts to be two launches
     if (lf) return (gf->line && gb->line && gf->symmetric && gb->symmetric) ? 2 : 0;
     if (want_lanes(A, gf) && want_lanes(A, gb) && gf->lanem && gb->lanem) return 1;
     return 0;
@@ -2254,7 +2255,13 @@ int tune_effect(pamg_matrix_s *A, TuneEffect effect, int value)
         case KEEP: return PAMG_OK;
         case DROP_ZERO_IF_OFF: if (value != 1) return PAMG_OK; [[fallthrough]];
         case DROP_ZERO: matrix_drop_zero_plans(A); return PAMG_OK;
-        case DROP_TWIN_LINE: for (GsSchedule *g : A->gs) if (g) g->line_unfit = false; [[fallthrough]];
+        case DROP_TWIN_LINE:                                    // switched off, the line layouts go too: line_info reports what the next sweep runs
+            for (GsSchedule *g : A->gs) {
+                if (!g) continue;
+                g->line_unfit = false;
+                if (value == 0) drop_part(A, g, g->line, line_part_bytes(g), free_line_part);
+            }
+            [[fallthrough]];
         case DROP_TWIN: matrix_drop_point_twin(A); return PAMG_OK;
         case DROP_LANES:
             matrix_drop_point_twin(A);

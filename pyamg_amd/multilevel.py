@@ -174,7 +174,8 @@ class DeviceMatrix:
         return out
 
     def sym_info(self):
-        """the fused symmetric sweep (tune(sym_fused=...)): launches so far, the form of the last one, the state of its buffers between launches"""
+        """the fused symmetric sweep (tune(sym_fused=...)): launches so far, the form of the last one (it keeps that name until another fused launch,
+        also after a tune change that ends the form), the state of its buffers between launches"""
         a = (C.c_int64 * 9)()
         capi.check(capi.lib().pamg_matrix_sym_info(self.handle, a), "pamg_matrix_sym_info")
         d = dict(zip(("launches", "zero_launches", "form", "launch_grid", "enabled", "handoff_not_sentinel", "counters_not_zero", "zero_plan_launches", "correction_launches"), list(a)))

@@ -2,7 +2,7 @@
 // Builds the layout with the product's own planner (pyamg_amd/csrc/pamg_line_plan.h) and consumes it the way gs_line_kernel
 // does: `waves` waves take the lines statically (wave w: lines w, w + waves, ...), every wave walks the chunks of its line in
 // order; a chunk step = for every lane B = (b - sum of the other entries) * rdiag, A = acoef, an inclusive scan of the pairs
-// over the lanes (Hillis-Steele: distance 1, 2, 4, ... -- the association of the device's shuffles), x = B + A * carry, publish.
+// over the lanes (in the association of the device's DPP steps: rows of 16 lanes, then across the rows), x = B + A * carry, publish.
 // A chunk runs only when every early operand has been published (else the wave "polls": skipped this round); a round without
 // progress is a deadlock (error 20).  Old operands must still be old when read (error 13, unless a snapshot is used).
 #include "../pyamg_amd/csrc/pamg_line_plan.h"
@@ -69,14 +69,21 @@ extern "C" int line_emul_sweep_f64(int n, const int *Ap, const int *Aj, const do
                 if (P.nodiag[rs]) { Bv = xsrc[row]; Av = 0.0; }
                 A[lane] = Av; B[lane] = Bv;
             }
-            for (int d = 1; d < 64; d *= 2) {                 // inclusive scan of (A, B) under (A2, B2) o (A1, B1) = (A2 A1, B2 + A2 B1)
+            // inclusive scan of (A, B) under (A2, B2) o (A1, B1) = (A2 A1, B2 + A2 B1) in the association of line_scan (pamg_line.hip): distance
+            // 1, 2, 4, 8 inside the rows of 16 lanes, then rows 1 and 3 take the total of the row before them (its lane 15), then rows 2 and 3
+            // the total of the first half (lane 31); src = the lane whose pair is taken, or -1
+            auto step = [&](auto src) {
                 double A2[64], B2[64];
                 for (int lane = 0; lane < 64; ++lane) {
-                    if (lane >= d) { A2[lane] = A[lane] * A[lane - d]; B2[lane] = B[lane] + A[lane] * B[lane - d]; }
+                    const int u = src(lane);
+                    if (u >= 0) { B2[lane] = B[lane] + A[lane] * B[u]; A2[lane] = A[lane] * A[u]; }
                     else { A2[lane] = A[lane]; B2[lane] = B[lane]; }
                 }
                 for (int lane = 0; lane < 64; ++lane) { A[lane] = A2[lane]; B[lane] = B2[lane]; }
-            }
+            };
+            for (int d = 1; d < 16; d *= 2) step([d](int lane) { return (lane & 15) >= d ? lane - d : -1; });
+            step([](int lane) { return (lane & 16) ? (lane & 48) - 1 : -1; });
+            step([](int lane) { return (lane & 32) ? 31 : -1; });
             double last = 0.0;
             for (int lane = 0; lane < cnt; ++lane) {
                 const int row = r0 + lane * P.step;

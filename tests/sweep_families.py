@@ -338,3 +338,37 @@ def dependency_levels(A, direction):
         if after.size:
             pend[after] = np.maximum(pend[after], lvl[i] + 1)
     return int(lvl.max()) + 1 if n else 0
+
+
+# ----------------------------------------------------------------- solver level (device)
+def solve_three_ways(spec, k, cycle, cpl, tune):
+    """graph replay, a second replay, eager (bit for bit the same); returns (solver, x, residuals, sym_info per level before and after the eager solve)"""
+    from pyamg_amd import DeviceMultilevelSolver
+    from pyamg_amd import _capi as capi
+    n = spec.levels[0].A.shape[0]
+    x0 = np.random.RandomState(77).rand(n)
+    b = np.zeros_like(x0)
+    dml = DeviceMultilevelSolver(spec, graph=True, order="fast", level_tune=tune)
+    r1, r2, r3 = [], [], []
+    kw = dict(x0=x0, tol=1e-30, maxiter=k, cycle=cycle, cycles_per_level=cpl)
+    x1 = dml.solve(b, residuals=r1, **kw)
+    x2 = dml.solve(b, residuals=r2, **kw)
+    capi.check(capi.lib().pamg_solver_set_graph(dml.handle, 0), "pamg_solver_set_graph")
+    before = [A.sym_info() for A in dml.A]
+    x3 = dml.solve(b, residuals=r3, **kw)
+    after = [A.sym_info() for A in dml.A]
+    assert np.array_equal(x1, x2) and r1 == r2, "a second solve must give the same bits"
+    assert np.array_equal(x1, x3) and r1 == r3, "graph replay and eager launches must give the same bits"
+    for i, A in enumerate(dml.A):
+        assert not A.flow_error(), f"flow error on level {i}"
+    return dml, x1, r1, (b, x0), before, after
+
+
+def parity(tag, x, r, xo, ro):
+    r = np.array(r)
+    assert r.shape == ro.shape
+    rel = float(np.max(np.abs(r - ro) / ro))
+    dx = float(np.linalg.norm(x - xo) / np.linalg.norm(xo))
+    print(f"[families] solver {tag}: residual norms {rel:.2e}, iterate {dx:.2e} against the oracle; {ro[0]:.3e} -> {ro[-1]:.3e}")
+    assert rel <= 1e-10, (tag, rel)
+    assert dx <= 1e-12, (tag, dx)

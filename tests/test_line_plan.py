@@ -3,47 +3,23 @@ by tests/line_emul.cpp the way gs_line_kernel consumes it (waves take lines stat
 inclusive scan of the recurrence x_t = B_t + A_t x_{t-1} over the lanes) and must agree with the oracle's sequential sweep
 (amg_core::gauss_seidel / sor_gauss_seidel, relaxation.h:48-76,116-145) to rounding -- 1e-13 relative per sweep -- while the
 replay asserts what the device relies on (no deadlock for any number of waves, old operands still old)."""
-import ctypes
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from line_families import build_emul, run_emul
 from oracle import oracle as orc
 from tools.problems import poisson_csr
 
 HERE = Path(__file__).resolve().parent
-ROOT = HERE.parent
 TOL = 1e-13
 
 
 @pytest.fixture(scope="module")
 def emul():
-    out = HERE / "build"
-    out.mkdir(exist_ok=True)
-    so = out / "line_emul.so"
-    src = HERE / "line_emul.cpp"
-    hdr = ROOT / "pyamg_amd" / "csrc" / "pamg_line_plan.h"
-    if not so.exists() or so.stat().st_mtime < max(src.stat().st_mtime, hdr.stat().st_mtime):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", "-shared", "-fPIC", str(src), "-o", str(so)], check=True)
-    lib = ctypes.CDLL(str(so))
-    lib.line_emul_sweep_f64.restype = ctypes.c_int
-    return lib
-
-
-def run_emul(lib, A, x, b, start, stop, step, sor=0, omega=1.0, snapshot=0, waves=7):
-    A = sp.csr_array(A)
-    Ap = np.ascontiguousarray(A.indptr, dtype=np.int32)
-    Aj = np.ascontiguousarray(A.indices, dtype=np.int32)
-    Ax = np.ascontiguousarray(A.data, dtype=np.float64)
-    xx = np.array(x, dtype=np.float64)
-    stats = np.zeros(8, dtype=np.int64)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    rc = lib.line_emul_sweep_f64(ctypes.c_int(A.shape[0]), p(Ap), p(Aj), p(Ax), p(xx), p(np.ascontiguousarray(b, dtype=np.float64)),
-                                 start, stop, step, sor, ctypes.c_double(omega), snapshot, waves, p(stats))
-    return rc, xx, stats
+    return build_emul(HERE / "build")
 
 
 def ref_sweep(A, x, b, start, stop, step, sor=0, omega=1.0):
