@@ -724,6 +724,21 @@ int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[9]);
  * zero-iterate plans (r: DEVICE scratch vector of the operator's size, overwritten).  PAMG_E_UNSUPPORTED where the operator holds no such plans (a bare
  * operator with PAMG_TUNE_ZERO_PLANS = 2 builds them here, outside a graph capture). */
 int pamg_matrix_gauss_seidel_correction(pamg_matrix_t A, void *x, const void *b, void *r, int iterations, pamg_stream_t s);
+/* The DENSE BLOCK-TRIANGULAR form of the symmetric Gauss-Seidel sweep from zero (f64, scalar rows, fast order; pamg_dtri_plan.h): the rows are cut into
+ * contiguous blocks of `block_rows` rows (0 = default, at most 8192) whose triangular diagonal blocks are inverted once, on the device, into dense packed
+ * triangles; x = S b then runs as 4 blocks - 2 plain launches (off-block sparse products and dense triangular mat-vecs) with no hand-off inside a launch.
+ * A solver runs both sweeps of a level that holds the form through it: the pre-smoothing from zero, the post-smoothing as r = b - A x, x += S r; so does
+ * pamg_matrix_gauss_seidel_correction.  Results agree with the merged plans to rounding.
+ * mode 0 = automatic: a solver's levels below the finest with symmetric Gauss-Seidel before and after, more than 8192 rows, the triangles of one direction
+ * at most 16 x the bytes of the CSR arrays and both at most 2 GB, the planner not declining (every row one non-zero finite diagonal entry, the growth factor
+ * max_i sum_j |W_ij| |a_jj| of the inverse blocks at most 1e3); a bare operator never.  1 = off.  2 = on wherever the form fits (a solver builds it on levels with a symmetric Gauss-Seidel smoother, a bare
+ * operator at its first symmetric sweep announced from zero or asked in correction form, outside a graph capture).  Such a level builds no zero-iterate plans.
+ * PAMG_E_STATE once a solver holds the operator. */
+int pamg_matrix_dense_tri(pamg_matrix_t A, int mode, int block_rows);
+/* {built, blocks, rows per block, bytes of both sets of triangles, off-block entries, symmetric sweeps run in this form from zero, in correction form,
+ * the operator's side of the automatic rule holds, the planner declined by growth, microseconds of the inverse kernels, mode, kernel launches per
+ * application, bytes the form added to pamg_matrix_info's resident bytes (triangles, slices, work vectors), 0, 0, 0}; *growth (may be NULL): the growth factor of the last build (0 = none yet). */
+int pamg_matrix_dense_tri_info(pamg_matrix_t A, int64_t info[16], double *growth);
 /* relaxation.polynomial (relaxation.py:585-659); coeffs is a HOST array; x_is_zero != 0
  * asserts x == 0 on entry (the reference tests norm(x) == 0, relaxation.py:649). */
 int pamg_matrix_polynomial(pamg_matrix_t A, void *x, const void *b, void *work,

@@ -185,6 +185,8 @@ def _declare(lib):
     f("pamg_matrix_gauss_seidel", _vp, _vp, _vp, _i, _d, _i, _vp)
     f("pamg_matrix_gauss_seidel_x0", _vp, _vp, _vp, _i, _d, _i, _i, _vp)
     f("pamg_matrix_gauss_seidel_correction", _vp, _vp, _vp, _vp, _i, _vp)
+    f("pamg_matrix_dense_tri", _vp, _i, _i)
+    f("pamg_matrix_dense_tri_info", _vp, P(C.c_int64), P(C.c_double))
     f("pamg_matrix_sym_info", _vp, P(C.c_int64))
     f("pamg_matrix_polynomial", _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp)
     f("pamg_matrix_block_jacobi", _vp, _vp, _vp, _vp, _vp, _d, _i, _vp)

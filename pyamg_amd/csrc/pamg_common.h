@@ -141,6 +141,8 @@ struct TileSched {
 
 // Dependency levels of a Kaczmarz-type sweep over the lines (rows) of an operator: two lines conflict when they
 // share a column index; lines of one level are pairwise conflict-free.
+struct DtriSched;
+
 struct LineSchedule {
     int start = 0, stop = 0, step = 0;
     int nlevels = 0;
@@ -262,6 +264,15 @@ struct pamg_matrix_s {
     // correction form of a symmetric sweep from x != 0 (a solver's cycle driver): r = b - A x, then x += sweep(0, r) on the zero-iterate plans
     int gs_correction = 0;           // PAMG_TUNE_GS_CORRECTION: 0 = automatic (levels of at least GS_CORRECTION_MIN_ROWS rows), 1 = off, 2 = on wherever the plans exist
     long long correction_launches = 0;  // symmetric smoothing steps that ran in correction form (fused or as two launches)
+    // dense block-triangular form of the symmetric sweep from zero (pamg_dtri_plan.h / pamg_dtri.hip; pamg_matrix_dense_tri): x = S b by block inverses
+    int dtri_mode = 0;               // 0 = automatic (a solver's levels that meet the rule: dtri_auto_eligible), 1 = off, 2 = on wherever the form fits
+    int dtri_block_rows = 0;         // rows per block (0 = DTRI_BLOCK_ROWS)
+    struct pamg::DtriSched *dtri = nullptr;
+    bool dtri_unfit = false;         // its planner declined (no unique non-zero diagonal, too large, growth bound)
+    bool dtri_declined_growth = false;
+    double dtri_growth = 0.0;        // the guard's figure of the last build: max_i sum_j |W_ij| |a_jj|
+    size_t dtri_bytes = 0;           // what the form added to `bytes`
+    long long dtri_zero_launches = 0, dtri_correction_launches = 0;   // symmetric sweeps that ran in this form: from zero / in correction form
     size_t bytes = 0;
 };
 
@@ -403,6 +414,28 @@ int gs_sweep_correction(pamg_matrix_s *A, void *x, const void *b, void *r, bool 
 // PAMG_TUNE_GS_CORRECTION = 0: the correction form runs on levels of at least this many rows (the two extra small launches cost a small level more than the
 // triangular plans save).  A placeholder from round 9's kernel times until tools/microbench_gs_correction.py has been run
 constexpr int64_t GS_CORRECTION_MIN_ROWS = 16384;
+// the one-XCD form of the merged lane sweep takes operators of at most this many rows (pamg_lane.hip)
+constexpr int64_t ONE_XCD_MAX_ROWS = 8192;
+// pamg_dtri.hip: the dense block-triangular form of a symmetric sweep from zero.  Automatic rule (operator side): more rows than the one-XCD form
+// takes, the inverse triangles of one direction at most DTRI_AUTO_RATIO x the bytes of the CSR arrays (a memory-proportion bound: it admits the
+// 59 - 68 entries per row of smoothed-aggregation level 2 and excludes the 30 per row of level 1), both directions at most DTRI_MAX_BYTES
+constexpr int64_t DTRI_AUTO_RATIO = 16;
+constexpr int64_t DTRI_MAX_BYTES = (int64_t)2 << 30;
+bool dtri_form_ok(const pamg_matrix_s *A);
+bool dtri_auto_eligible(const pamg_matrix_s *A);
+int build_dtri_part(pamg_matrix_s *A);           // PAMG_E_ARG: the form does not fit (A->dtri_unfit)
+void free_dtri_part(struct DtriSched *t);
+size_t dtri_part_bytes(const pamg_matrix_s *A);
+int dtri_sym_launch(pamg_matrix_s *A, void *x, const void *b, bool acc, hipStream_t s);
+int dtri_info(const pamg_matrix_s *A, int64_t *info, double *growth);
+// pamg_matrix.hip: build or drop the form; allocates, never inside a capture.  The caller's side of the rule: `sweeps` -- symmetric Gauss-Seidel sweeps will run on
+// the operator (a solver: a smoother of the level is one; a bare operator asked by name) --, `automatic` -- the context the automatic mode needs (a solver's level
+// below the finest with symmetric Gauss-Seidel before and after).  The operator's side (dtri_mode, dtri_auto_eligible) is checked here
+bool dtri_claims(const pamg_matrix_s *A, bool sweeps, bool automatic);   // would ensure_dtri try to build (or keep) the form?
+int ensure_dtri(pamg_matrix_s *A, bool sweeps, bool automatic);
+void matrix_drop_dtri(pamg_matrix_s *A);
+// a symmetric sweep in the dense form: from zero x = S b; otherwise, with a scratch vector r, r = b - A x and x += S r.  *ran = false: nothing was enqueued
+int gs_sweep_dtri(pamg_matrix_s *A, void *x, const void *b, void *r, bool x_zero, hipStream_t s, bool *ran);
 int sym_fill_sentinels(void *p, int64_t n);      // n f64 sentinels on the null stream, synchronised
 int sweep_error(pamg_matrix_s *A, bool *error);      // spin bound hit since the last call? (caller has synchronised; clears the flag)
 inline size_t tsize(int dtype) { return dtype == PAMG_F64 ? 8 : 4; }

@@ -1367,7 +1367,7 @@ static bool lanem_all_regs(const pamg_matrix_s *A, const LaneMSched *t)
 // (the cluster layout: static form only)
 static bool lanem_one_xcd(const pamg_matrix_s *A, const GsSchedule *g, const LaneMSched *t)
 {
-    return !t->cluster && (A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= 8192));
+    return !t->cluster && (A->gran_xcd == 1 || (A->gran_xcd == 0 && lane_one_xcd(A, g) && A->nrows <= ONE_XCD_MAX_ROWS));
 }
 
 // workgroups a plan wants, given `cap` co-resident ones per CU on `cus` CUs

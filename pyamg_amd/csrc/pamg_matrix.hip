@@ -12,6 +12,7 @@
 #include "pamg_tile_kernels.h"
 #include "pamg_tile_plan.h"
 #include "pamg_stream_plan.h"
+#include "pamg_dtri_plan.h"
 
 using namespace pamg;
 
@@ -898,6 +899,7 @@ void matrix_drop_schedules(pamg_matrix_s *A)
         if (l) free_line_schedule(l);
     }
     matrix_drop_zero_plans(A);                                 // they hold the operator's values too
+    matrix_drop_dtri(A);                                       // (so do the inverse triangles)
     matrix_drop_point_twin(A);
 }
 
@@ -1582,6 +1584,69 @@ int gs_sweep_correction(pamg_matrix_s *A, void *x, const void *b, void *r, bool 
     return PAMG_OK;
 }
 
+// ---- the dense block-triangular form (pamg_dtri.hip; pamg_matrix_dense_tri).  On a level that holds it, both symmetric sweeps of a cycle run as
+// 4 nb - 2 plain launches: the pre-smoothing from zero x = S b, the post-smoothing in correction form r = b - A x, x += S r.
+bool dtri_claims(const pamg_matrix_s *A, bool sweeps, bool automatic)
+{
+    if (!A || !sweeps || A->dtri_mode == 1 || A->dtri_unfit || !dtri_form_ok(A)) return false;
+    return A->dtri_mode == 2 || (automatic && dtri_auto_eligible(A));
+}
+
+void matrix_drop_dtri(pamg_matrix_s *A)
+{
+    if (!A) return;
+    A->dtri_unfit = A->dtri_declined_growth = false;           // asked again at the next build
+    if (!A->dtri) return;
+    free_dtri_part(A->dtri);
+    A->dtri = nullptr;
+    std::lock_guard<std::mutex> lk(g_sched_mu);
+    A->bytes -= std::min(A->bytes, A->dtri_bytes);
+    A->dtri_bytes = 0;
+}
+
+int ensure_dtri(pamg_matrix_s *A, bool sweeps, bool automatic)
+{
+    if (!A) return PAMG_OK;
+    if (!dtri_claims(A, sweeps, automatic)) {
+        if (A->dtri) { const bool unfit = A->dtri_unfit, grew = A->dtri_declined_growth; matrix_drop_dtri(A); A->dtri_unfit = unfit; A->dtri_declined_growth = grew; }
+        return PAMG_OK;
+    }
+    if (A->dtri) return PAMG_OK;
+    const int st = build_dtri_part(A);
+    if (st == PAMG_E_ARG) return PAMG_OK;                      // declined: the merged plans keep the sweep
+    if (st != PAMG_OK) return st;
+    std::lock_guard<std::mutex> lk(g_sched_mu);
+    A->dtri_bytes = dtri_part_bytes(A);
+    A->bytes += A->dtri_bytes;
+    return PAMG_OK;
+}
+
+int gs_sweep_dtri(pamg_matrix_s *A, void *x, const void *b, void *r, bool x_zero, hipStream_t s, bool *ran)
+{
+    *ran = false;
+    if (A->dtri_mode == 1 || !dtri_form_ok(A)) return PAMG_OK;
+    if (!x_zero && (!r || A->gs_correction == 1)) return PAMG_OK;
+    if (!A->dtri) {
+        if (A->dtri_mode != 2 || A->dtri_unfit) return PAMG_OK;
+        // a bare operator switched on by name: its first such sweep builds the form -- allocations, so never inside a graph capture
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        PAMG_HIP(hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone) return PAMG_OK;
+        PAMG_TRY(ensure_dtri(A, true, false));
+        if (!A->dtri) return PAMG_OK;
+    }
+    if (x_zero) {
+        PAMG_TRY(dtri_sym_launch(A, x, b, false, s));
+        A->dtri_zero_launches++;
+    } else {
+        PAMG_TRY(stream_launch(A, EPI_RESID, x, b, r, 0.0, 0.0, nullptr, s));                 // r = b - A x
+        PAMG_TRY(dtri_sym_launch(A, x, r, true, s));
+        A->dtri_correction_launches++;
+    }
+    *ran = true;
+    return PAMG_OK;
+}
+
 int ensure_schedule(pamg_matrix_s *A, int row_start, int row_stop, int row_step, bool block_gs)
 {
     GsSchedule *g = nullptr;
@@ -2092,6 +2157,7 @@ int pamg_matrix_destroy(pamg_matrix_t A)
     for (int k = 0; k < 4; ++k) pamg::free_line_schedule(A->ls[k]);
     hipFree(A->d_sym_hf[0]); hipFree(A->d_sym_hf[1]); hipFree(A->d_sym_hb); hipFree(A->d_sym_sync);
     pamg::free_zero_plans(A);
+    pamg::free_dtri_part(A->dtri);
     if (A->point_twin) pamg_matrix_destroy(A->point_twin);
     delete A;
     return PAMG_OK;
@@ -2266,6 +2332,7 @@ int tune_effect(pamg_matrix_s *A, TuneEffect effect, int value)
         case DROP_LANES:
             matrix_drop_point_twin(A);
             matrix_drop_zero_plans(A);
+            matrix_drop_dtri(A);
             for (GsSchedule *g : A->gs) {
                 if (!g) continue;
                 g->lane_unfit = g->lanem_unfit = g->blane_unfit = g->line_unfit = false;
@@ -2285,6 +2352,7 @@ int tune_effect(pamg_matrix_s *A, TuneEffect effect, int value)
         case REPLAN:
             for (int k = 0; k < 4; ++k) { if (A->gs[k]) A->bytes -= A->gs[k]->bytes; free_schedule(A->gs[k]); A->gs[k] = nullptr; }
             matrix_drop_zero_plans(A);
+            matrix_drop_dtri(A);
             matrix_drop_point_twin(A);                          // it sweeps for the schedules just dropped
             return replan(A);
     }
@@ -2304,6 +2372,7 @@ int pamg_matrix_tune(pamg_matrix_t A, int key, int value)
     if (A->borrowed > 0 && !(t && (t->flags & HELD_OK))) return PAMG_E_STATE;
     if (!t || !t->accepts(value)) return PAMG_E_ARG;
     A->*(t->field) = tune_stored(t->store, value);
+    if (A->dtri && !pamg::dtri_form_ok(A)) pamg::matrix_drop_dtri(A);      // order / scheduler changed: the dense form no longer applies
     return tune_effect(A, t->effect, value);
 }
 
@@ -2500,6 +2569,22 @@ int pamg_matrix_sym_info(pamg_matrix_t A, int64_t info[9])
     info[6] = 0;
     for (int k = 0; k < 5; ++k) info[6] += w[k] != 0u;
     return PAMG_OK;
+}
+
+int pamg_matrix_dense_tri(pamg_matrix_t A, int mode, int block_rows)
+{
+    if (!A || mode < 0 || mode > 2 || block_rows < 0 || block_rows > pamg::DTRI_MAX_BLOCK_ROWS) return PAMG_E_ARG;
+    if (A->borrowed > 0) return PAMG_E_STATE;                  // a solver's captured graphs point into the triangles
+    if (mode != A->dtri_mode || block_rows != A->dtri_block_rows) pamg::matrix_drop_dtri(A);
+    A->dtri_mode = mode;
+    A->dtri_block_rows = block_rows;
+    return PAMG_OK;
+}
+
+int pamg_matrix_dense_tri_info(pamg_matrix_t A, int64_t info[16], double *growth)
+{
+    if (!A || !info) return PAMG_E_ARG;
+    return pamg::dtri_info(A, info, growth);
 }
 
 int pamg_matrix_lanem_levels(pamg_matrix_t A, int which, int64_t *out, int64_t capacity, int64_t *count)

@@ -113,6 +113,9 @@ int gs_apply(pamg_matrix_s *A, void *x, const void *b, int sweep, double omega, 
         for (int it = 0; it < its; ++it) {
             // one launch where both directions take the same fast form (x_zero holds for the first iteration only)
             bool ran = false;
+            // a level that holds the dense block-triangular form (pamg_dtri.hip): from zero x = S b, else r = b - A x and x += S r
+            PAMG_TRY(gs_sweep_dtri(A, x, b, r, x_zero && it == 0, s, &ran));
+            if (ran) continue;
             // from x != 0 on a level that holds zero-iterate plans: r = b - A x, then x += sweep(0, r) on those plans
             if (r && !(x_zero && it == 0)) PAMG_TRY(gs_sweep_correction(A, x, b, r, false, s, &ran));
             if (ran) continue;
@@ -351,6 +354,7 @@ int fall_back_to_level_launches(pamg_solver_s *S)
         L.A->tile_default = 0;
         PAMG_TRY(sym_reset(L.A));                             // (the fused symmetric sweep declines from here on: gs_mode 1)
         matrix_drop_zero_plans(L.A);                          // (so do the zero-iterate plans: every sweep takes the general path)
+        matrix_drop_dtri(L.A);                                // (and the dense form, which asks for scheduler mode 0)
         for (Smoother *sm : {&L.pre, &L.post}) {
             // kz_lane_launch is gated on gs_mode == 0 of the operator the sweep runs on (pamg_matrix.hip: kaczmarz_sweep)
             if (sm->At) sm->At->gs_mode = 1;
@@ -506,6 +510,13 @@ static bool zero_plans_wanted(const pamg_matrix_s *A, const Smoother &pre, const
     if (sor_takes_omega(A, post)) return false;              // the operator keeps the unmerged layout
     return A->R == 1 && A->dtype == PAMG_F64 && A->gs_order == 1 && A->gs_mode == 0 && A->nrows >= 2;
 }
+
+// The solver's side of the dense block-triangular form (pamg_matrix_dense_tri).  dtri_sweeps: a smoother of the level is symmetric Gauss-Seidel (switched on
+// by name, the form is built only where it would run); dtri_automatic: a level below the finest whose pre- and post-smoother both are.  The operator's side
+// (mode, size, memory proportion, growth) is dtri_claims / ensure_dtri
+static bool dtri_sym_gs(const Smoother &sm) { return sm.kind == PAMG_SMOOTH_GS && sm.sweep == PAMG_SYMMETRIC && sm.iterations >= 1; }
+static bool dtri_sweeps(const Smoother &pre, const Smoother &post) { return dtri_sym_gs(pre) || dtri_sym_gs(post); }
+static bool dtri_automatic(const Smoother &pre, const Smoother &post, int l) { return l >= 1 && dtri_sym_gs(pre) && dtri_sym_gs(post); }
 
 int prebuild_schedules(Level &L, const Smoother &sm, bool zero)
 {
@@ -1295,7 +1306,8 @@ int pamg_matrix_gauss_seidel_correction(pamg_matrix_t A, void *x, const void *b,
     if (!square_ok(A)) return PAMG_E_ARG;
     for (int it = 0; it < iterations; ++it) {
         bool ran = false;
-        PAMG_TRY(gs_sweep_correction(A, x, b, r, true, (hipStream_t)s, &ran));
+        PAMG_TRY(gs_sweep_dtri(A, x, b, r, false, (hipStream_t)s, &ran));
+        if (!ran) PAMG_TRY(gs_sweep_correction(A, x, b, r, true, (hipStream_t)s, &ran));
         if (!ran) return PAMG_E_UNSUPPORTED;
     }
     return PAMG_OK;
@@ -1650,14 +1662,16 @@ int pamg_solver_finalize(pamg_solver_t S)
         std::vector<SchedJob> jobs;
         for (int l = 0; l < nsm; ++l) {
             Level &L = S->levels[l];
-            sched_jobs_of(L, L.pre, jobs, zero_plans_wanted(L.A, L.pre, L.post, l));
+            // a level the dense form claims builds no zero-iterate plans: they would never run
+            sched_jobs_of(L, L.pre, jobs, zero_plans_wanted(L.A, L.pre, L.post, l) && !dtri_claims(L.A, dtri_sweeps(L.pre, L.post), dtri_automatic(L.pre, L.post, l)));
             sched_jobs_of(L, L.post, jobs);
         }
         PAMG_TRY(run_sched_jobs(jobs));
     }
     for (int l = 0; l < nsm; ++l) {            // whatever the jobs did not cover (Kaczmarz line schedules); the rest is found built
         Level &L = S->levels[l];
-        PAMG_TRY(prebuild_schedules(L, L.pre, zero_plans_wanted(L.A, L.pre, L.post, l)));
+        PAMG_TRY(ensure_dtri(L.A, dtri_sweeps(L.pre, L.post), dtri_automatic(L.pre, L.post, l)));        // the block inverses (device kernels; where its planner declines, the zero-iterate plans are built below)
+        PAMG_TRY(prebuild_schedules(L, L.pre, zero_plans_wanted(L.A, L.pre, L.post, l) && !L.A->dtri));
         PAMG_TRY(prebuild_schedules(L, L.post));
     }
     PAMG_TRY(dalloc(S, (void **)&S->d_slot, 16 * sizeof(double)));

@@ -251,6 +251,21 @@ class DeviceMatrix:
         operator holds no such plans"""
         capi.check(capi.lib().pamg_matrix_gauss_seidel_correction(self.handle, x.ptr, b.ptr, r.ptr, int(iterations), stream), "pamg_matrix_gauss_seidel_correction")
 
+    def dense_tri(self, mode, block_rows=0):
+        """the dense block-triangular form of the symmetric sweep from zero (pamg_matrix_dense_tri): mode 0 automatic (a solver decides per level),
+        1 off, 2 on wherever it fits; block_rows 0 = default.  Refused once a solver holds the operator"""
+        capi.check(capi.lib().pamg_matrix_dense_tri(self.handle, int(mode), int(block_rows)), "pamg_matrix_dense_tri")
+
+    def dense_tri_info(self):
+        """state of the dense block-triangular form: dict (built = 0 where the operator does not hold it)"""
+        a = (C.c_int64 * 16)()
+        gr = C.c_double(0.0)
+        capi.check(capi.lib().pamg_matrix_dense_tri_info(self.handle, a, C.byref(gr)), "pamg_matrix_dense_tri_info")
+        d = dict(zip(("built", "blocks", "block_rows", "bytes", "off_block_entries", "zero_launches", "correction_launches", "auto_eligible",
+                      "declined_by_growth", "inverse_us", "mode", "kernel_launches", "resident_bytes"), (int(v) for v in a)))
+        d["growth"] = gr.value
+        return d
+
     def gauss_seidel_x0(self, x, b, sweep="symmetric", omega=1.0, iterations=1, x_is_zero=False, stream=None):
         capi.check(capi.lib().pamg_matrix_gauss_seidel_x0(self.handle, x.ptr, b.ptr, capi.SWEEP[sweep], float(omega), int(iterations),
                                                           int(bool(x_is_zero)), stream), "pamg_matrix_gauss_seidel_x0")
@@ -399,11 +414,14 @@ class DeviceMultilevelSolver:
         hundreds of cycles: DESIGN 3, round 6).  Speed only: rows are moved and columns renamed, row sums keep their stored order, the
         caller never sees a level >= 1 vector -- results are bit-identical.  Levels with order-dependent smoothers (Gauss-Seidel,
         Kaczmarz, Schwarz, block sweeps, Krylov) keep the reference's numbering; ``renumbered`` lists the levels that were changed.
+    dense_tri : None (automatic), False (off on every level) or a dict ``{level: dict(mode=..., block_rows=...)}`` -- the dense block-triangular form
+        of the symmetric Gauss-Seidel sweeps (``DeviceMatrix.dense_tri``; fast order, f64).  Automatic: mid-size coarse levels (more than 8192 rows,
+        inverse triangles at most 16 x the operator's bytes) smoothed by symmetric Gauss-Seidel before and after.  Agrees with the merged form to rounding.
     """
 
     def __init__(self, ml, device: Optional[int] = None, graph: bool = True, autotune: Optional[bool] = None,
                  level_tune=None, order: Optional[str] = None, strict: bool = True, renumber: Optional[bool] = None,
-                 schwarz_setup: str = "reference"):
+                 schwarz_setup: str = "reference", dense_tri=None):
         import os
         self.fallback = None
         if schwarz_setup not in ("reference", "device"):
@@ -415,7 +433,7 @@ class DeviceMultilevelSolver:
             # CPU restatement of ours -- and it is announced once.
             try:
                 self.__init__(ml, device=device, graph=graph, autotune=autotune, level_tune=level_tune, order=order, strict=True, renumber=renumber,
-                              schwarz_setup=schwarz_setup)
+                              schwarz_setup=schwarz_setup, dense_tri=dense_tri)
                 return
             except NotImplementedError as e:
                 if isinstance(ml, HierarchySpec) or not hasattr(ml, "solve"):
@@ -513,6 +531,10 @@ class DeviceMultilevelSolver:
                 kw = level_tune(i) if callable(level_tune) else level_tune
                 if kw:
                     A.tune(**kw)
+            if dense_tri is False:
+                A.dense_tri(1)
+            elif dense_tri is not None and dense_tri.get(i):
+                A.dense_tri(**dense_tri[i])
             capi.check(lib.pamg_solver_add_level(h, A.handle, P.handle if P else None, R.handle if R else None),
                        "pamg_solver_add_level")
             if i < nlev - 1:

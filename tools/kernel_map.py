@@ -72,7 +72,32 @@ def kernel_map(dml, smoother_kind):
                 alg = (vb + 4) * nnz + 4 * (n + 1) + 3 * vb * n
                 sym = A.sym_info()
                 directions = ((0, "forward"), (1, "backward"))
-                if sym["launches"] and sym["form"] != "none":
+                dt = A.dense_tri_info()
+                if dt["built"] and (dt["zero_launches"] or dt["correction_launches"]):
+                    # the dense block-triangular form (csrc/pamg_dtri.hip): both sweeps of the level are 4 blocks - 2 plain launches each, a sparse and a
+                    # dense phase per block step and direction.  One entry per (phase, direction, grid): bytes of ONE launch -- a block's inverse triangle
+                    # resp. its share of the off-block slices, and the vectors; the ragged last block has grids of its own.  A launch IS one step of the
+                    # dependency chain, so a row's dependency_levels is 1 (us per dependency level = the launch's time); the chain of one sweep is `block_steps`
+                    directions = ()
+                    B, nb = dt["block_rows"], dt["blocks"]
+                    sizes = sorted({min(B, n - k * B) for k in range(nb)}, reverse=True)
+                    steps = f"{2 * nb} block steps of <= {B} rows per sweep, {dt['kernel_launches']} launches"
+                    if dt["correction_launches"]:
+                        r_ = _op_entry(i, "A", A, "RESID", "A residual for the post-smoothing correction")
+                        r_["shares_launches_with"] = "residual r = b - A x"
+                        out.append(r_)
+                    for m in sizes:
+                        tri = vb * sum((r + 2) & ~1 for r in range(m))
+                        for dirn in ("forward", "backward"):
+                            out.append({"family": "gs_dtri_dense", "grid": (m + 1) // 2, "level": i, "op": "A",
+                                        "what": f"dense phase, {dirn}: y_k = W_k t_k ({steps})", "rows": int(m), "nnz": int(nnz), "bytes_alg": int(tri + 3 * vb * m),
+                                        "bytes_streamed": int(tri + 4 * vb * m), "format": f"packed inverse triangle of {m} rows, rows padded to 16 bytes", "dependency_levels": 1, "block_steps": int(2 * nb)})
+                            out.append({"family": "gs_dtri_sparse", "grid": (16 * m + 255) // 256, "level": i, "op": "A",
+                                        "what": f"sparse phase, {dirn}: t_k = rhs_k - off-block slice . v ({steps})", "rows": int(m), "nnz": int(dt["off_block_entries"] // 2),
+                                        "bytes_alg": int((vb + 4) * dt["off_block_entries"] // 2 * m // n + 3 * vb * m),
+                                        "bytes_streamed": int((vb + 4) * dt["off_block_entries"] // 2 * m // n + (2 * vb + 8) * m + 64 * dt["off_block_entries"] // 2 * m // n),
+                                        "format": "CSR slice of the off-block entries, 16 lanes per row", "dependency_levels": 1, "block_steps": int(2 * nb)})
+                elif sym["launches"] and sym["form"] != "none":
                     # the fused symmetric sweep: ONE launch walks both schedules (bytes: the two directions' together)
                     directions = ()
                     lm, ln = [A.lanem_info(w) for w in (0, 1)], [A.line_info(w) for w in (0, 1)]

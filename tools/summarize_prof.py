@@ -48,6 +48,9 @@ def short(name):
     m = re.search(r"gs_line_sym_kernel<(\w+), *(\d+)>", name)
     if m:
         return f"gs_line_sym<{m.group(1)},GS,K{m.group(2)}>"
+    m = re.search(r"gs_dtri_(sparse|dense)_kernel<(\w+)>", name)                         # the dense block-triangular form (csrc/pamg_dtri.hip)
+    if m:
+        return f"gs_dtri_{m.group(1)}<double,{'bwd' if m.group(2) in ('true', '1') else 'fwd'}>"
     m = re.search(r"gs_lanem\w*_kernel<(\w+)(?:, *(\d+))?(?:, *(\d+))?(?:, *(\d+))?>", name)
     if m:
         return (f"gs_lanem<double,GS,{'oneXCD' if m.group(1) in ('true', '1') else 'chip'}" + (f",rpw{m.group(2)}" if m.group(2) else "")
@@ -70,6 +73,8 @@ def family(k):
     if k.startswith("csr_"):
         m = re.search(r",(\w+?)(,kz\d|,nu\d)?>", k)
         return "csr", (m.group(1) if m else None)
+    if k.startswith("gs_dtri"):
+        return ("gs_dtri_dense" if k.startswith("gs_dtri_dense") else "gs_dtri_sparse"), None
     if k.startswith("gs_lanem"):
         return ("gs_lanem_zero" if ",zero>" in k else "gs_lanem_corr" if ",corr>" in k else "gs_lanem"), None
     if k.startswith("gs_lane"):
