@@ -414,6 +414,49 @@ int pamg_min_blocks_f64(int32_t n_blocks, int32_t blocksize, const double *Sx, i
 int pamg_evolution_strength_vector_f64(double *Sx, int Sx_size, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,
                                        int32_t nrows, const double *d, int d_size, const double *b, int b_size);
 
+/* The relaxation-vector strength measures -- algebraic distance and affinity, strength.py:860-1072 -- and the vertex-distance measure,
+ * strength.py:24-111 (csrc/pamg_distance.hip, the arithmetic in csrc/pamg_distance.h).  float64, HOST arrays; every result is the
+ * reference's, bit for bit.  Row pointers and sizes are checked first (PAMG_E_ARG, as above) and nothing is written then.
+ *
+ * X is the reference's n x R block of vectors in column-major order (np.reshape(..., order='F')): X[r * n + i].  On the device it is
+ * kept as one record of R doubles per node.  1 <= R <= 32; beyond: PAMG_E_UNSUPPORTED. */
+#define PAMG_DISTANCE_ALGEBRAIC_P1 0   /* S(t_r) / R,              t_r = |xi_r - xj_r| */
+#define PAMG_DISTANCE_ALGEBRAIC_P2 1   /* sqrt(S(t_r * t_r) / R) */
+#define PAMG_DISTANCE_ALGEBRAIC_PINF 2 /* max_r t_r (a NaN propagates) */
+#define PAMG_DISTANCE_AFFINITY 3       /* 1 - (S(xi_r xj_r))^2 / (S(xi_r xi_r) S(xj_r xj_r)), the square one multiplication */
+/* relaxation_vectors, strength.py:888-889: k sweeps of amg_core::jacobi (relaxation.h:310-346) with b = 0 on every column of X, in place.
+ * Per row i and column r: rsum = 0, then rsum += Ax[jj] * old[j][r] over the stored entries with j != i in stored order; diag the LAST
+ * stored entry with j == i; if diag != 0, x = (1 - omega) * old[i][r] + omega * ((0.0 - rsum) / diag), otherwise the value is carried
+ * over (a row without a stored diagonal, with a stored zero diagonal, an empty row).  One launch per sweep reads A once for all R
+ * columns. */
+int pamg_relaxation_vectors_f64(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *Ax, int Ax_size, double *X,
+                                int X_size, int32_t n, int32_t R, int32_t k, double omega);
+/* The distance of every stored entry (i, j) of A from the records xi, xj, on A's pattern: PAMG_DISTANCE_* above, each rounding where
+ * NumPy's elementwise steps put it.  S is NumPy's sum along a contiguous row: left to right for R < 8; for 8 <= R <= 32 eight
+ * accumulators r[k] = a[k], r[k] += a[i + k] over whole groups of eight, ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the
+ * remaining elements left to right.  Entries with j == i or Ax == 0 get 0.0 (A.nonzero() drops stored zeros). */
+int pamg_distance_measure_f64(int32_t measure, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *Ax, int Ax_size,
+                              const double *X, int X_size, int32_t n, int32_t R, double *Dx, int Dx_size);
+/* distance_measure_common, strength.py:1044-1060, resident: A and the random block X up once, k sweeps, the measure, and fused with it
+ * per row the reference's eliminate_zeros + apply_distance_filter -- the minimum of the non-zero entries with j != i (std::min: a NaN
+ * never replaces the running value; DBL_MAX for a row without one), every entry >= epsilon times it made 0.0.  Dx (on A's pattern) and
+ * the relaxed X come back. */
+int pamg_distance_strength_f64(int32_t measure, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *Ax, int Ax_size,
+                               double *X, int X_size, int32_t n, int32_t R, int32_t k, double omega, double epsilon, double *Dx, int Dx_size);
+/* distance_strength_of_connection, strength.py:83-87: per stored entry sqrt(((dx dx) + dy dy) + ...), coordinate after coordinate, values
+ * below 1e-6 made 1e-6.  V is n x dim row-major, 1 <= dim <= 8 (beyond: PAMG_E_UNSUPPORTED).  The two filters it needs are
+ * pamg_apply_distance_filter_f64 and pamg_apply_absolute_distance_filter_f64. */
+int pamg_vertex_distance_f64(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *V, int V_size, int32_t n, int32_t dim,
+                             double *Cx, int Cx_size);
+/* The two device steps of the chain on DEVICE pointers (what the entries above launch between their copies): k sweeps between the two
+ * record buffers dXa and dXb, starting from dXa (the result is in dXa for even k, in dXb for odd k), and the measure kernel on a record
+ * buffer, with the tail fused where filter != 0 (nnz, the number of stored entries, chooses the lanes per row).  Nothing is checked but
+ * the scalars. */
+int pamg_dev_relaxation_sweeps_f64(int32_t n, int32_t R, int32_t k, double omega, const int32_t *dAp, const int32_t *dAj, const double *dAx,
+                                   double *dXa, double *dXb, void *stream);
+int pamg_dev_distance_measure_f64(int32_t measure, int32_t filter, int32_t n, int64_t nnz, int32_t R, double epsilon, const int32_t *dAp,
+                                  const int32_t *dAj, const double *dAx, const double *dX, double *dDx, void *stream);
+
 /* Energy-minimisation prolongation smoothing with CG and GMRES (csrc/pamg_energy.hip, the arithmetic in csrc/pamg_energy.h).  float64, HOST
  * arrays; blocks are row-major and at most 6 x 6, at most 6 candidates (beyond: PAMG_E_UNSUPPORTED).  Patterns are checked as above
  * before anything is written.

@@ -27,6 +27,7 @@ KRYLOV = {"cg": 0, "gmres": 1, "cgne": 2, "cgnr": 3}
 ACCEL = {"bicgstab": 0, "cr": 1, "steepest_descent": 2, "minimal_residual": 3}     # pamg_solver_krylov methods (PAMG_ACCEL_*)
 SWEEP = {"forward": FORWARD, "backward": BACKWARD, "symmetric": SYMMETRIC}
 CYCLE = {"V": 0, "W": 1, "F": 2, "AMLI": 3}
+DISTANCE = {"algebraic_p1": 0, "algebraic_p2": 1, "algebraic_pinf": 2, "affinity": 3}      # PAMG_DISTANCE_* of include/pyamg_amd.h
 
 
 class DeviceUnavailable(RuntimeError):
@@ -133,6 +134,12 @@ def _declare(lib):
     f("pamg_apply_absolute_distance_filter_f64", _i, _d, *(_vp, _i) * 3)
     f("pamg_min_blocks_f64", _i, _i, _vp, _i, _vp, _i)
     f("pamg_evolution_strength_vector_f64", *(_vp, _i) * 3, _i, *(_vp, _i) * 2)
+    f("pamg_relaxation_vectors_f64", *(_vp, _i) * 4, _i, _i, _i, _d)
+    f("pamg_distance_measure_f64", _i, *(_vp, _i) * 4, _i, _i, _vp, _i)
+    f("pamg_distance_strength_f64", _i, *(_vp, _i) * 4, _i, _i, _i, _d, _d, _vp, _i)
+    f("pamg_vertex_distance_f64", *(_vp, _i) * 3, _i, _i, _vp, _i)
+    f("pamg_dev_relaxation_sweeps_f64", _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp)
+    f("pamg_dev_distance_measure_f64", _i, _i, _i, C.c_int64, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp)
     f("pamg_incomplete_mat_mult_bsr_f64", *(_vp, _i) * 9, _i, _i, _i, _i, _i)
     f("pamg_satisfy_constraints_helper_f64", _i, _i, _i, _i, *(_vp, _i) * 6)
     f("pamg_satisfy_constraints_f64", _i, _i, _i, _i, *(_vp, _i) * 5)

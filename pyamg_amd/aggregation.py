@@ -762,7 +762,7 @@ _CLASSICAL_NAMES = ("classical_strength_of_connection", "direct_interpolation", 
 
 @contextlib.contextmanager
 def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False, evolution=False,
-                 energy=False, energy_gmres=False):
+                 energy=False, energy_gmres=False, distance=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -809,7 +809,15 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     rotations on the device; the triangular solve stays on the host.  The result agrees with the reference to rounding, for the reason
     given for CG.  ``weighting='block'``, ``maxiter`` above 32 and whatever else CG refuses go to the function that was patched out; CGNR
     is not touched.  It is a keyword of its own so that ``energy=True`` keeps patching exactly its two names; both together patch three.
-    With both off nothing of ``<pyamg>.aggregation.smooth`` is touched on their account and ``pyamg_amd.energy`` is not imported."""
+    With both off nothing of ``<pyamg>.aggregation.smooth`` is touched on their account and ``pyamg_amd.energy`` is not imported.
+    ``distance=True`` routes ``algebraic_distance``, ``affinity_distance`` and ``distance_strength_of_connection`` to ``pyamg_amd.distance`` in
+    every module that binds them -- ``<pyamg>.strength``, ``.aggregation.aggregation``, ``.aggregation.rootnode``, ``.classical.classical`` and
+    ``.classical.air``, fifteen attributes: the R random vectors are then relaxed together, one launch per sweep, and the measure and its
+    filter come back as one array on A's pattern.  The arrays are the reference's bit for bit, and a call draws the reference's
+    ``np.random.rand(n * R)`` once on the host, so a seeded caller sees the same stream.  A ``p`` other than 1, 2 or inf, more than 32
+    vectors, more than 8 coordinates, float32 or complex data and whatever else the device path does not take go to the function that
+    was patched out.  Off by default for the reason given for ``classical``; with ``distance=False`` nothing is patched on its account and
+    ``pyamg_amd.distance`` is not imported."""
     import importlib
     from . import air as _air
     from . import classical as _cls
@@ -831,6 +839,12 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
         energy_table = ((("aggregation.smooth", "cg_prolongation_smoothing", _en.cg_prolongation_smoothing),) if energy else ()) + \
                        ((("aggregation.smooth", "gmres_prolongation_smoothing", _en.gmres_prolongation_smoothing),) if energy_gmres else ()) + \
                        (("aggregation.smooth", "satisfy_constraints", _en.satisfy_constraints),)
+    distance_table = ()
+    if distance:
+        from . import distance as _dst
+        distance_table = tuple((mod, fn.__name__, fn) for mod in ("strength", "aggregation.aggregation", "aggregation.rootnode",
+                                                                  "classical.classical", "classical.air")
+                               for fn in (_dst.algebraic_distance, _dst.affinity_distance, _dst.distance_strength_of_connection))
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
                           ("aggregation.aggregation", "richardson_prolongation_smoother", richardson_prolongation_smoother),
@@ -851,7 +865,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                           ("classical.classical", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.interpolate", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.split", "PMIS", _cls.PMIS),
-                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table:
+                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table + distance_table:
         of_air = (mod, name, fn) in air_table
         if not classical and name in _CLASSICAL_NAMES and not of_air:
             continue                            # (before the import: with classical=False nothing of <pyamg>.classical is touched)
@@ -873,7 +887,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
             elif name == "schwarz_parameters":
                 setattr(m, name, _schwarz_parameters_or_reference(old))
             elif name in ("standard_aggregation", "fit_candidates", "evolution_strength_of_connection") or name in _CLASSICAL_NAMES or of_air or \
-                    (mod, name, fn) in energy_table:
+                    (mod, name, fn) in energy_table or (mod, name, fn) in distance_table:
                 setattr(m, name, _device_or_reference(fn, old))
             else:
                 setattr(m, name, fn)

@@ -21,7 +21,7 @@ __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_
            "rs_classical_interpolation_pass1", "rs_classical_interpolation_pass2",
            "one_point_interpolation", "approx_ideal_restriction_pass1", "approx_ideal_restriction_pass2",
            "incomplete_mat_mult_csr", "evolution_strength_helper", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
-           "evolution_strength_vector", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "satisfy_constraints", "energy_cg", "energy_gmres"]
+           "evolution_strength_vector", "relaxation_vectors", "distance_measure", "distance_strength", "vertex_distance", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "satisfy_constraints", "energy_cg", "energy_gmres"]
 
 
 def _sfx(Ax, *vals):
@@ -391,6 +391,40 @@ def evolution_strength_vector(Sx, Sp, Sj, nrows, d, b):
     _idx(Sp, Sj)
     _f64(Sx, d, b)
     capi.check(capi.lib().pamg_evolution_strength_vector_f64(*_pairs(Sx, Sp, Sj), int(nrows), *_pairs(d, b)), "evolution_strength_vector")
+
+
+# ------------------------------------------------------------------ relaxation-vector and vertex-distance strength: csrc/pamg_distance.hip
+def relaxation_vectors(Ap, Aj, Ax, X, n, R, k, omega):
+    """relaxation_vectors (strength.py:888-889): k weighted-Jacobi sweeps with b = 0 on every column of the n x R block ``X``
+    (column-major, flat: ``X[r * n + i]``), in place; one launch per sweep for all R columns.  1 <= R <= 32 (beyond: NotImplementedError)."""
+    _idx(Ap, Aj)
+    _f64(Ax, X)
+    capi.check(capi.lib().pamg_relaxation_vectors_f64(*_pairs(Ap, Aj, Ax, X), int(n), int(R), int(k), float(omega)), "relaxation_vectors")
+
+
+def distance_measure(measure, Ap, Aj, Ax, X, n, R, Dx):
+    """The distance of every stored entry of A from the block ``X`` (as above), on A's pattern; ``measure`` is one of ``capi.DISTANCE``:
+    strength.py:945-948 (affinity) and :1008-1014 (algebraic, p = 1, 2, inf).  The diagonal and stored zeros get 0.0."""
+    _idx(Ap, Aj)
+    _f64(Ax, X, Dx)
+    capi.check(capi.lib().pamg_distance_measure_f64(int(measure), *_pairs(Ap, Aj, Ax, X), int(n), int(R), *_pairs(Dx)), "distance_measure")
+
+
+def distance_strength(measure, Ap, Aj, Ax, X, n, R, k, omega, epsilon, Dx):
+    """distance_measure_common (strength.py:1044-1060) resident: one upload of A and of the random block ``X``, k sweeps, the measure and,
+    fused with it, eliminate_zeros + apply_distance_filter; ``Dx`` (on A's pattern, dropped entries 0.0) and the relaxed ``X`` come back."""
+    _idx(Ap, Aj)
+    _f64(Ax, X, Dx)
+    capi.check(capi.lib().pamg_distance_strength_f64(int(measure), *_pairs(Ap, Aj, Ax, X), int(n), int(R), int(k), float(omega), float(epsilon),
+                                                    *_pairs(Dx)), "distance_strength")
+
+
+def vertex_distance(Ap, Aj, V, n, dim, Cx):
+    """distance_strength_of_connection's values (strength.py:83-87): the Euclidean distance of the two vertices of every stored entry,
+    never below 1e-6; ``V`` is n x dim row-major, flat, 1 <= dim <= 8 (beyond: NotImplementedError)."""
+    _idx(Ap, Aj)
+    _f64(V, Cx)
+    capi.check(capi.lib().pamg_vertex_distance_f64(*_pairs(Ap, Aj, V), int(n), int(dim), *_pairs(Cx)), "vertex_distance")
 
 
 # ------------------------------------------------------------------ energy-minimisation prolongation smoothing: csrc/pamg_energy.hip

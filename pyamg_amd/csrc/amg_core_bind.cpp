@@ -255,6 +255,23 @@ PYBIND11_MODULE(_amg_core_pybind, m)
         done(pamg_evolution_strength_vector_f64(Sx.mutable_data(), len(Sx), Sp.data(), len(Sp), Sj.data(), len(Sj), nrows, d.data(), len(d), b.data(),
                                                 len(b)), "evolution_strength_vector");
     }, nc("Sx"), nc("Sp"), nc("Sj"), py::arg("nrows"), nc("d"), nc("b"));
+    // the relaxation-vector and vertex-distance strength measures, float64 (composed in Python by the reference): csrc/pamg_distance.hip
+    m.def("relaxation_vectors", [](Idx &Ap, Idx &Aj, D &Ax, D &X, int n, int R, int k, double omega) {
+        done(pamg_relaxation_vectors_f64(Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), X.mutable_data(), len(X), n, R, k, omega),
+             "relaxation_vectors");
+    }, nc("Ap"), nc("Aj"), nc("Ax"), nc("X"), py::arg("n"), py::arg("R"), py::arg("k"), py::arg("omega"));
+    m.def("distance_measure", [](int measure, Idx &Ap, Idx &Aj, D &Ax, D &X, int n, int R, D &Dx) {
+        done(pamg_distance_measure_f64(measure, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), X.data(), len(X), n, R, Dx.mutable_data(),
+                                       len(Dx)), "distance_measure");
+    }, py::arg("measure"), nc("Ap"), nc("Aj"), nc("Ax"), nc("X"), py::arg("n"), py::arg("R"), nc("Dx"));
+    m.def("distance_strength", [](int measure, Idx &Ap, Idx &Aj, D &Ax, D &X, int n, int R, int k, double omega, double epsilon, D &Dx) {
+        done(pamg_distance_strength_f64(measure, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), X.mutable_data(), len(X), n, R, k, omega,
+                                        epsilon, Dx.mutable_data(), len(Dx)), "distance_strength");
+    }, py::arg("measure"), nc("Ap"), nc("Aj"), nc("Ax"), nc("X"), py::arg("n"), py::arg("R"), py::arg("k"), py::arg("omega"), py::arg("epsilon"),
+       nc("Dx"));
+    m.def("vertex_distance", [](Idx &Ap, Idx &Aj, D &V, int n, int dim, D &Cx) {
+        done(pamg_vertex_distance_f64(Ap.data(), len(Ap), Aj.data(), len(Aj), V.data(), len(V), n, dim, Cx.mutable_data(), len(Cx)), "vertex_distance");
+    }, nc("Ap"), nc("Aj"), nc("V"), py::arg("n"), py::arg("dim"), nc("Cx"));
     // energy-minimisation prolongation smoothing, float64 (smoothed_aggregation_bind.cpp): csrc/pamg_energy.hip
     m.def("incomplete_mat_mult_bsr", [](Idx &Ap, Idx &Aj, D &Ax, Idx &Bp, Idx &Bj, D &Bx, Idx &Sp, Idx &Sj, D &Sx, int n_brow, int n_bcol, int brow_A,
                                         int bcol_A, int bcol_B) {
