@@ -330,6 +330,20 @@ int pamg_maximal_independent_set(int32_t num_rows, const int32_t *Ap, int Ap_siz
  * S union S^T (the transposed pattern is built on the device), nodes without a neighbour set to F.  splitting [n_nodes]: 1 = C, 0 = F. */
 int pamg_pmis_splitting(int32_t n_nodes, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size, const double *rnd,
                         int rnd_size, int32_t *splitting, int splitting_size, int32_t *rounds);
+/* amg_core::cljp_naive_splitting, ruge_stuben.h:577-741 (csrc/pamg_cljp.hip, the rules and the argument in csrc/pamg_cljp.h): the CLJP
+ * splitting (colorflag == 0: weights from srand(2448422) / rand() drawn on the host, which leaves the C library's stream reseeded as the
+ * reference does) or CLJP-c (colorflag == 1: weights from the MIS colouring below).  The selection, P5 and P6 of a pass do not depend on
+ * the order of the C-points for any node that is still undecided when the pass ends, so synchronous passes -- a handful of plain
+ * launches each -- give the reference's array.  The transposed pattern is built on the device; the diagonal is skipped; rows need not be
+ * sorted; no row may hold a column twice.  splitting [n]: 1 = C, 0 = F.  info [4] (may be null): passes, colours, colouring rounds (all
+ * colours together), nodes selected.  At most n passes, n colours and n rounds per colour (more: PAMG_E_NOCONV).  n == 0 returns at once. */
+int pamg_cljp_splitting(int32_t n, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size, int32_t colorflag, int32_t *splitting,
+                        int splitting_size, int32_t *info);
+/* amg_core::vertex_coloring_mis, graph.h:218-235: colour K goes to the greedy independent set, in index order, of the nodes still without
+ * a colour.  Node i takes K exactly when no j < i with i in row(j) takes K, which synchronous rounds decide from the lowest index up.
+ * x [num_rows] receives the colours; info [2] (may be null): colours, rounds.  Self loops are ignored; the pattern need not be symmetric. */
+int pamg_vertex_coloring_mis(int32_t num_rows, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, int32_t *x, int x_size,
+                             int32_t *info);
 /* amg_core::rs_direct_interpolation_pass1 / _pass2, ruge_stuben.h:777-907.  Sx holds the values of A on the pattern of the strength
  * matrix.  Pass 2 checks Pp against pass 1's counts (PAMG_E_ARG).  Rows need not be sorted; no row may hold a column twice. */
 int pamg_rs_direct_interpolation_pass1(int32_t n_nodes, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,

@@ -119,6 +119,8 @@ def _declare(lib):
         f(f"pamg_classical_strength_of_connection_{nm}", _i, _d, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i)
     f("pamg_maximal_independent_set", _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, P(_i), P(_i))
     f("pamg_pmis_splitting", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, P(_i))
+    f("pamg_cljp_splitting", _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp)
+    f("pamg_vertex_coloring_mis", _i, _vp, _i, _vp, _i, _vp, _i, _vp)
     for nm in ("direct", "classical"):
         f(f"pamg_rs_{nm}_interpolation_pass1", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i)
     interp2 = (_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i)

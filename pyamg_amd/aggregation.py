@@ -762,7 +762,7 @@ _CLASSICAL_NAMES = ("classical_strength_of_connection", "direct_interpolation", 
 
 @contextlib.contextmanager
 def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False, evolution=False,
-                 energy=False, energy_gmres=False, distance=False):
+                 energy=False, energy_gmres=False, distance=False, cljp=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -817,7 +817,16 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     ``np.random.rand(n * R)`` once on the host, so a seeded caller sees the same stream.  A ``p`` other than 1, 2 or inf, more than 32
     vectors, more than 8 coordinates, float32 or complex data and whatever else the device path does not take go to the function that
     was patched out.  Off by default for the reason given for ``classical``; with ``distance=False`` nothing is patched on its account and
-    ``pyamg_amd.distance`` is not imported."""
+    ``pyamg_amd.distance`` is not imported.
+    ``cljp=True`` routes ``CLJP`` and ``CLJPc`` (in ``<pyamg>.classical.split``, and as bound by name in ``.classical.air`` when ``air=True``)
+    and ``vertex_coloring`` (in ``.classical.split`` and ``<pyamg>.graph``) to ``pyamg_amd.classical``: ``ruge_stuben_solver(CF='CLJP')`` /
+    ``CF='CLJPc'`` then select their coarse grids on the device, and ``PMISc(method='MIS')`` runs its colouring there (with
+    ``classical=True`` its ``MIS`` too).  The splittings and colourings are the reference's arrays.  CLJP is not an order-dependent sweep:
+    its selection is synchronous, and for every node still undecided when a pass ends the edges removed and the weight decrements of the
+    pass do not depend on the order of the C-points (``pyamg_amd.classical``, csrc/pamg_cljp.h).  The ``JP`` / ``LDF`` colourings and BSR
+    input go to the function that was patched out; the serial ``RS`` splitting and ``CR`` are order-dependent and stay with the reference.
+    A keyword of its own so that ``classical=True`` keeps patching exactly the names it patches today; off by default for the reason
+    given for ``classical``.  With ``cljp=False`` nothing is patched or imported on its account."""
     import importlib
     from . import air as _air
     from . import classical as _cls
@@ -845,6 +854,9 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
         distance_table = tuple((mod, fn.__name__, fn) for mod in ("strength", "aggregation.aggregation", "aggregation.rootnode",
                                                                   "classical.classical", "classical.air")
                                for fn in (_dst.algebraic_distance, _dst.affinity_distance, _dst.distance_strength_of_connection))
+    cljp_table = ((("classical.split", "CLJP", _cls.CLJP), ("classical.split", "CLJPc", _cls.CLJPc),
+                   ("classical.split", "vertex_coloring", _cls.vertex_coloring), ("graph", "vertex_coloring", _cls.vertex_coloring)) +
+                  ((("classical.air", "CLJP", _cls.CLJP), ("classical.air", "CLJPc", _cls.CLJPc)) if air else ())) if cljp else ()
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
                           ("aggregation.aggregation", "richardson_prolongation_smoother", richardson_prolongation_smoother),
@@ -865,7 +877,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                           ("classical.classical", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.interpolate", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.split", "PMIS", _cls.PMIS),
-                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table + distance_table:
+                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table + distance_table + cljp_table:
         of_air = (mod, name, fn) in air_table
         if not classical and name in _CLASSICAL_NAMES and not of_air:
             continue                            # (before the import: with classical=False nothing of <pyamg>.classical is touched)
@@ -887,7 +899,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
             elif name == "schwarz_parameters":
                 setattr(m, name, _schwarz_parameters_or_reference(old))
             elif name in ("standard_aggregation", "fit_candidates", "evolution_strength_of_connection") or name in _CLASSICAL_NAMES or of_air or \
-                    (mod, name, fn) in energy_table or (mod, name, fn) in distance_table:
+                    (mod, name, fn) in energy_table or (mod, name, fn) in distance_table or (mod, name, fn) in cljp_table:
                 setattr(m, name, _device_or_reference(fn, old))
             else:
                 setattr(m, name, fn)

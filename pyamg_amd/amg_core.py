@@ -17,7 +17,7 @@ __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_
            "jacobi", "bsr_jacobi", "block_jacobi", "block_jacobi_indexed", "block_gauss_seidel", "jacobi_indexed", "gauss_seidel_indexed", "overlapping_schwarz_csr", "extract_subblocks", "gauss_seidel_ne",
            "gauss_seidel_nr", "jacobi_ne", "pinv_array", "standard_aggregation", "fit_candidates",
            "classical_strength_of_connection_abs", "classical_strength_of_connection_min", "maximal_independent_set_parallel", "pmis_splitting",
-           "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2", "remove_strong_FF_connections",
+           "cljp_naive_splitting", "vertex_coloring_mis", "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2", "remove_strong_FF_connections",
            "rs_classical_interpolation_pass1", "rs_classical_interpolation_pass2",
            "one_point_interpolation", "approx_ideal_restriction_pass1", "approx_ideal_restriction_pass2",
            "incomplete_mat_mult_csr", "evolution_strength_helper", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
@@ -292,6 +292,26 @@ def pmis_splitting(n_nodes, Sp, Sj, rnd, splitting, rounds=None):
     capi.check(capi.lib().pamg_pmis_splitting(int(n_nodes), *_pairs(Sp, Sj, rnd, splitting), ctypes.byref(nr)), "pmis_splitting")
     if rounds is not None:
         rounds.append(int(nr.value))
+
+
+def cljp_naive_splitting(n, Sp, Sj, Tp, Tj, splitting, colorflag, info=None):
+    """amg_core.cljp_naive_splitting (ruge_stuben.h:577-741), the reference's argument order; ``Tp`` / ``Tj`` are accepted and ignored
+    (the device builds the transposed pattern itself).  ``info``: a list that receives (passes, colours, colouring rounds, nodes selected)."""
+    _idx(Sp, Sj, splitting)
+    out = np.zeros(4, dtype=np.int32)
+    capi.check(capi.lib().pamg_cljp_splitting(int(n), *_pairs(Sp, Sj), int(colorflag), *_pairs(splitting), capi.ptr(out)), "cljp_naive_splitting")
+    if info is not None:
+        info.append(tuple(int(v) for v in out))
+
+
+def vertex_coloring_mis(num_rows, Ap, Aj, x, info=None):
+    """amg_core.vertex_coloring_mis (graph.h:218-235); returns the number of colours.  ``info``: a list that receives (colours, rounds)."""
+    _idx(Ap, Aj, x)
+    out = np.zeros(2, dtype=np.int32)
+    capi.check(capi.lib().pamg_vertex_coloring_mis(int(num_rows), *_pairs(Ap, Aj, x), capi.ptr(out)), "vertex_coloring_mis")
+    if info is not None:
+        info.append(tuple(int(v) for v in out))
+    return int(out[0])
 
 
 def rs_direct_interpolation_pass1(n_nodes, Sp, Sj, splitting, Pp):

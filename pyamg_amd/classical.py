@@ -2,6 +2,8 @@
 
 * ``classical_strength_of_connection``  -- pyamg/strength.py:114-245
 * ``MIS`` / ``PMIS``                    -- pyamg/classical/split.py:336-384, :155-194
+* ``CLJP`` / ``CLJPc``                  -- split.py:243-333 (csrc/pamg_cljp.hip, the rules in csrc/pamg_cljp.h)
+* ``vertex_coloring(method='MIS')``     -- pyamg/graph.py:84-126
 * ``direct_interpolation``              -- pyamg/classical/interpolate.py:12-83
 * ``classical_interpolation``           -- interpolate.py:86-171 (``modified`` True and False)
 
@@ -12,8 +14,15 @@ draws them, so a patched setup consumes the same stream.
 
 Float64 CSR operators.  What the device path does not take (BSR operators, other dtypes, ``norm='fro'``, a bounded ``maxiter``, a
 non-symmetric graph handed to ``MIS``) raises ``NotImplementedError``; ``aggregation.device_setup(pyamg, classical=True)`` then hands
-the call to the reference function it patched out.  The serial ``RS`` splitting, ``CLJP`` and the colouring variants are order-dependent
-sweeps and are not here.
+the call to the reference function it patched out (``CLJP``, ``CLJPc`` and ``vertex_coloring`` under its keyword ``cljp=True``).
+
+``CLJP`` is not an order-dependent sweep although the reference writes it as one.  Its selection is synchronous (``Dlist`` is collected
+against the unchanged splitting); its weight updates P5 and P6 only remove edges into, and decrement, undecided nodes, and once such a
+node drops below 1 and turns F nothing reads its weight or its edges again, so for the nodes still undecided at the end of a pass the
+removed edges and the number of decrements do not depend on the order of the C-points; ``w - count`` is exact.  The MIS colouring gives
+node i the colour K exactly when no lower-index in-neighbour takes K, which rounds decide from the lowest index up.  What remains
+order-dependent and is not here: the serial ``RS`` splitting, the ``JP`` / ``LDF`` colourings (one in-place sweep plus first-fit per
+colour) and ``CR``.
 """
 from __future__ import annotations
 
@@ -22,7 +31,8 @@ import scipy.sparse as sp
 
 from . import amg_core
 
-__all__ = ["classical_strength_of_connection", "MIS", "PMIS", "direct_interpolation", "classical_interpolation"]
+__all__ = ["classical_strength_of_connection", "MIS", "PMIS", "CLJP", "CLJPc", "vertex_coloring", "direct_interpolation",
+           "classical_interpolation"]
 
 
 def _i32(a):
@@ -107,6 +117,55 @@ def PMIS(S, rounds=None):
     splitting = np.empty(n, dtype="intc")
     amg_core.pmis_splitting(n, Sp, Sj, rnd, splitting, rounds=rounds)
     return splitting
+
+
+def _pattern_only(M, what):
+    """what the pattern-only kernels take: no BSR blocks, int32-sized index arrays"""
+    if M.format == "bsr":
+        raise NotImplementedError(f"{what} on the device takes CSR patterns, not BSR blocks")
+    return _i32(M.indptr), _i32(M.indices)
+
+
+def CLJP(S, color=False, info=None):
+    """pyamg.classical.split.CLJP: C/F splitting (1 = coarse, 0 = fine) by the parallel CLJP method, with the reference's weights --
+    ``srand(2448422)`` / ``rand()`` of the C library, or with ``color=True`` the MIS colouring of S -- plus the in-degree.  Only the
+    pattern of S is read; its diagonal is skipped and no transpose is formed on the host.  ``info``: a list that receives
+    (passes, colours, colouring rounds, nodes selected)."""
+    if sp.issparse(S) and S.format == "bsr":
+        raise NotImplementedError("CLJP on the device takes CSR patterns, not BSR blocks")
+    _square_csr(S)
+    n = S.shape[0]
+    Sp, Sj = _pattern_only(S, "CLJP")
+    splitting = np.empty(n, dtype="intc")
+    amg_core.cljp_naive_splitting(n, Sp, Sj, None, None, splitting, 1 if color else 0, info=info)
+    return splitting
+
+
+def CLJPc(S):
+    """pyamg.classical.split.CLJPc: CLJP in colour"""
+    return CLJP(S, color=True)
+
+
+def vertex_coloring(G, method="MIS", info=None):
+    """pyamg.graph.vertex_coloring(method='MIS'): colour K goes to the greedy independent set, in index order, of the vertices without a
+    colour.  Sparse input as ``asgraph`` takes it (CSR or CSC as stored, anything else through CSR).  'JP' and 'LDF' are one in-place
+    sweep plus first-fit per colour, which does depend on the sweep order: NotImplementedError.  ``info``: a list that receives
+    (colours, rounds)."""
+    if not sp.issparse(G) or G.format not in ("csc", "csr"):
+        if sp.issparse(G) and G.format == "bsr":
+            raise NotImplementedError("vertex_coloring on the device takes CSR patterns, not BSR blocks")
+        G = sp.csr_array(G)
+    if G.shape[0] != G.shape[1]:
+        raise ValueError("expected square matrix")
+    if method in ("JP", "LDF"):
+        raise NotImplementedError(f"vertex_coloring(method='{method}') is not on the device path: its in-place sweep depends on the sweep order")
+    if method != "MIS":
+        raise ValueError(f"Unknown method ({method})")
+    n = G.shape[0]
+    Gp, Gj = _pattern_only(G, "vertex_coloring")
+    coloring = np.empty(n, dtype="intc")
+    amg_core.vertex_coloring_mis(n, Gp, Gj, coloring, info=info)
+    return coloring
 
 
 def _pattern_with_values_of(C, A):

@@ -189,6 +189,17 @@ PYBIND11_MODULE(_amg_core_pybind, m)
                                  &rounds), "pmis_splitting");
         return rounds;
     }, py::arg("n_nodes"), nc("Sp"), nc("Sj"), nc("rnd"), nc("splitting"));
+    m.def("cljp_naive_splitting", [](int n, Idx &Sp, Idx &Sj, Idx &Tp, Idx &Tj, Idx &splitting, int colorflag) {
+        int info[4] = {0, 0, 0, 0};                          // Tp / Tj: the reference's argument order; the device builds the transpose itself
+        done(pamg_cljp_splitting(n, Sp.data(), len(Sp), Sj.data(), len(Sj), colorflag, splitting.mutable_data(), len(splitting), info),
+             "cljp_naive_splitting");
+        return py::make_tuple(info[0], info[1], info[2], info[3]);
+    }, py::arg("n"), nc("Sp"), nc("Sj"), nc("Tp"), nc("Tj"), nc("splitting"), py::arg("colorflag"));
+    m.def("vertex_coloring_mis", [](int num_rows, Idx &Ap, Idx &Aj, Idx &x) {
+        int info[2] = {0, 0};
+        done(pamg_vertex_coloring_mis(num_rows, Ap.data(), len(Ap), Aj.data(), len(Aj), x.mutable_data(), len(x), info), "vertex_coloring_mis");
+        return info[0];                                      // the number of colours, as the reference returns it
+    }, py::arg("num_rows"), nc("Ap"), nc("Aj"), nc("x"));
     m.def("rs_direct_interpolation_pass1", [](int n_nodes, Idx &Sp, Idx &Sj, Idx &splitting, Idx &Pp) {
         done(pamg_rs_direct_interpolation_pass1(n_nodes, Sp.data(), len(Sp), Sj.data(), len(Sj), splitting.data(), len(splitting), Pp.mutable_data(),
                                                 len(Pp)), "rs_direct_interpolation_pass1");

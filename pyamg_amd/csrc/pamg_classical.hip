@@ -394,6 +394,21 @@ int interp_pass2(const InterpArgs &a, int modified)
 
 }  // namespace
 
+// declared in pamg_host_call.h: PMIS and the CLJP selection (pamg_cljp.hip) build the same transposed pattern
+int pamg::device_transposed_pattern(int n, int64_t nnz, const int *dSp, const int *dSj, int *ddeg, int *dTp, int *dTj, int *dcur, unsigned *dflag)
+{
+    PAMG_HIP(hipMemset(ddeg, 0, sizeof(int) * (size_t)n));
+    PAMG_HIP(hipMemset(dcur, 0, sizeof(int) * (size_t)n));
+    hipLaunchKernelGGL(indegree_kernel, dim3(cgrid(n)), dim3(BLK), 0, 0, n, dSp, dSj, ddeg);
+    PAMG_HIP(hipGetLastError());
+    int tn = 0;
+    PAMG_TRY(scan_counts(n, ddeg, dTp, dflag, &tn));
+    if (tn > nnz) return PAMG_E_STATE;
+    hipLaunchKernelGGL(transpose_fill_kernel, dim3(cgrid(n)), dim3(BLK), 0, 0, n, dSp, dSj, dTp, dcur, dTj);
+    PAMG_HIP(hipGetLastError());
+    return PAMG_OK;
+}
+
 extern "C" {
 
 int pamg_classical_strength_of_connection_abs(int32_t n_row, double theta, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size,
@@ -459,14 +474,7 @@ int pamg_pmis_splitting(int32_t n_nodes, const int32_t *Sp, int Sp_size, const i
     PAMG_TRY(d.put(&dSp, Sp, (size_t)n + 1)); PAMG_TRY(d.put(&dSj, Sj, (size_t)nnz)); PAMG_TRY(d.put(&drnd, rnd, (size_t)n));
     PAMG_TRY(d.get(&ddeg, (size_t)n)); PAMG_TRY(d.get(&dTp, (size_t)n + 1)); PAMG_TRY(d.get(&dTj, (size_t)nnz)); PAMG_TRY(d.get(&dcur, (size_t)n));
     PAMG_TRY(d.get(&dy, (size_t)n)); PAMG_TRY(d.get(&dx[0], (size_t)n)); PAMG_TRY(d.get(&dx[1], (size_t)n)); PAMG_TRY(d.get(&dflags, MIS_BATCH));
-    PAMG_HIP(hipMemset(ddeg, 0, sizeof(int) * (size_t)n));
-    PAMG_HIP(hipMemset(dcur, 0, sizeof(int) * (size_t)n));
-    hipLaunchKernelGGL(indegree_kernel, dim3(cgrid(n)), dim3(BLK), 0, 0, n, dSp, dSj, ddeg);
-    PAMG_HIP(hipGetLastError());
-    int tn = 0;
-    PAMG_TRY(scan_counts(n, ddeg, dTp, dflags, &tn));
-    if (tn > nnz) return PAMG_E_STATE;
-    hipLaunchKernelGGL(transpose_fill_kernel, dim3(cgrid(n)), dim3(BLK), 0, 0, n, dSp, dSj, dTp, dcur, dTj);
+    PAMG_TRY(device_transposed_pattern(n, nnz, dSp, dSj, ddeg, dTp, dTj, dcur, dflags));
     hipLaunchKernelGGL(pmis_init_kernel, dim3(cgrid(n)), dim3(BLK), 0, 0, n, ddeg, drnd, dy, dx[0]);
     PAMG_HIP(hipGetLastError());
     int fin = 0, nr = 0;

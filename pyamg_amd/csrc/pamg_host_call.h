@@ -58,6 +58,11 @@ inline int check_pattern(int n, int ncol, const int *Ap, int Ap_size, const int 
     return PAMG_OK;
 }
 
+// The transposed off-diagonal pattern of the n-row device pattern dSp / dSj with nnz entries (pamg_classical.hip): ddeg [n] receives the
+// in-degrees, dTp [n + 1] / dTj [nnz] the pattern, dcur [n] and dflag [1] are scratch.  Built with atomics: the order inside a transposed
+// row is not reproducible.
+int device_transposed_pattern(int n, int64_t nnz, const int *dSp, const int *dSj, int *ddeg, int *dTp, int *dTj, int *dcur, unsigned *dflag);
+
 // workgroups of a grid-stride launch over n items, per_block of them per workgroup and pass
 inline int launch_grid(int64_t n, int per_block, int cap) { return (int)std::min<int64_t>(cap, std::max<int64_t>(1, (n + per_block - 1) / per_block)); }
 
