@@ -308,13 +308,12 @@ def _normal_equation_spec(kind, A, iterations, sweep, omega) -> SmootherSpec:
         raise NotImplementedError(f"{kind} on a {A.dtype} level is not on the device path (float64 only)")
     if A.format == "bsr" and tuple(A.blocksize) != (1, 1):
         raise NotImplementedError(f"{kind} on BSR blocks {A.blocksize} is not on the device path")
-    n = A.shape[0]
     if kind == "gauss_seidel_nr":
         Mc = A.tocsc()                                  # matrix_asformat(lvl, 'A', 'csc')
         Mc.sort_indices()
         Mt = Mc.T
-        D = (Mt.multiply(Mt.conjugate())) @ np.ones((Mt.shape[0],))
-        At = SparseOp("csr", (n, n), (1, 1), _as_int32(Mc.indptr, "indptr"), _as_int32(Mc.indices, "indices"),
+        D = (Mt.multiply(Mt.conjugate())) @ np.ones((Mt.shape[1],))      # squared norms of the lines; (the reference writes shape[0]: the same on its square operators)
+        At = SparseOp("csr", tuple(Mc.shape[::-1]), (1, 1), _as_int32(Mc.indptr, "indptr"), _as_int32(Mc.indices, "indices"),
                       np.ascontiguousarray(Mc.data), "csc")
         # the wrapper forms r = b - A @ x with the CSC matrix (relaxation.py:983): per row that is a sum in
         # ascending column order -- the level's own A gives the same bits only if its rows are sorted
@@ -322,7 +321,7 @@ def _normal_equation_spec(kind, A, iterations, sweep, omega) -> SmootherSpec:
         return SmootherSpec(kind, iterations, float(omega), sweep, Dinv=np.ravel(_inv_or_zero(D)), At=At, Ar=Ar, name=kind)
     M = A.tocsr()
     M.sort_indices()
-    D = (M.multiply(M.conjugate())) @ np.ones((M.shape[0],))
+    D = (M.multiply(M.conjugate())) @ np.ones((M.shape[1],))
     Dinv = np.ravel(_inv_or_zero(D))
     # On a BSR(1,1) level (SA coarse levels) the reference smooths with lvl.Acsr = lvl.A.tocsr(), whose rows come out
     # SORTED, while the cycle's own products keep the level's stored order: ship the sorted copy for the smoother when
@@ -333,7 +332,7 @@ def _normal_equation_spec(kind, A, iterations, sweep, omega) -> SmootherSpec:
     Mc = M.tocsc()
     Mc.sort_indices()
     om = A.dtype.type(np.real(omega))                   # type_prep(A.dtype, [omega]); omega2 * Ax[j] in the kernel
-    At = SparseOp("csr", (n, n), (1, 1), _as_int32(Mc.indptr, "indptr"), _as_int32(Mc.indices, "indices"),
+    At = SparseOp("csr", tuple(Mc.shape[::-1]), (1, 1), _as_int32(Mc.indptr, "indptr"), _as_int32(Mc.indices, "indices"),
                   np.ascontiguousarray(om * Mc.data), "csc")
     return SmootherSpec(kind, iterations, float(np.real(omega)), "forward", Dinv=Dinv, At=At, Ar=Ar, name=kind)
 

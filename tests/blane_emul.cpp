@@ -7,6 +7,12 @@
 // Checked: early operands come from groups with smaller numbers (12), old operands are still old (13) unless a snapshot is used,
 // no product in padding (11), every block row once (14, 15); a group whose gate is not published waits for it (a gate that belonged to a LATER
 // group would stop the replay: error 20).
+// want_L: what build_blane_part hands the planner, max(8, lane_L) -- the kernels exist for 8 .. 64 lanes per block row.  Lane q < bs of a block row
+// applies row q of Dinv_i to ITS copy of the sums (every lane of the row holds them after the butterfly): a plan with fewer lanes per row than bs has
+// no lane for the last components, error 16.
+// mode 1: the one-XCD ticket form.  A wave draws a group number from a counter, and the next one as soon as it has requested the operands of the
+// current group (it holds two tickets while it waits); a wave that finishes a group moves on to the ticket it holds and draws the next undrawn
+// number.  The wave holding the highest number is visited first.
 #include "../pyamg_amd/csrc/pamg_blane_plan.h"
 #include <cmath>
 #include <cstdio>
@@ -14,13 +20,14 @@
 using namespace pamg;
 
 extern "C" int blane_emul_sweep_f64(int n_brow, int bs, const int *bAp, const int *bAj, const double *bAx, const double *Dinv, double *x, const double *b,
-                                    int row_start, int row_stop, int row_step, int waves, int snapshot, long long *stats)
+                                    int row_start, int row_stop, int row_step, int waves, int snapshot, int want_L, int mode, long long *stats)
 {
     BlanePlan P;
-    if (build_blane_plan(n_brow, bAp, bAj, reinterpret_cast<const unsigned char *>(bAx), 8, bs, row_start, row_stop, row_step, P)) return 2;
+    if (build_blane_plan(n_brow, bAp, bAj, reinterpret_cast<const unsigned char *>(bAx), 8, bs, row_start, row_stop, row_step, P, want_L)) return 2;
     const int L = P.L, K = P.K, RPW = P.RPW, bs2 = bs * bs;
     stats[0] = L; stats[1] = K; stats[2] = P.ngroups; stats[3] = P.nslots; stats[4] = P.n_early; stats[5] = P.n_old; stats[6] = P.nlevels;
     const double *vals = reinterpret_cast<const double *>(P.vals.data());
+    if (L < bs) return 16;
     const int n = n_brow * bs;
     std::vector<double> xs((size_t)n), xold;
     std::vector<char> pub((size_t)n_brow, 0), written((size_t)n_brow, 0);
@@ -67,10 +74,10 @@ extern "C" int blane_emul_sweep_f64(int n_brow, int bs, const int *bAp, const in
             if (i < 0) continue;
             if (pub[(size_t)i]) return 14;
             double nv[8];
-            for (int r = 0; r < bs; ++r) {
+            for (int q = 0; q < bs; ++q) {                             // lane q of the block row: component q, from the lane's own sums
                 double s = 0.0;
-                for (int cc = 0; cc < bs; ++cc) s = s + Dinv[(size_t)i * bs2 + r * bs + cc] * (b[(size_t)i * bs + cc] - acc[(size_t)(rr * L) * bs + cc]);
-                nv[r] = s;
+                for (int cc = 0; cc < bs; ++cc) s = s + Dinv[(size_t)i * bs2 + q * bs + cc] * (b[(size_t)i * bs + cc] - acc[(size_t)(rr * L + q) * bs + cc]);
+                nv[q] = s;
             }
             for (int r = 0; r < bs; ++r) { xs[(size_t)i * bs + r] = nv[r]; x[(size_t)i * bs + r] = nv[r]; }
             pub[(size_t)i] = 1; written[(size_t)i] = 1;
@@ -79,9 +86,27 @@ extern "C" int blane_emul_sweep_f64(int n_brow, int bs, const int *bAp, const in
         return 0;
     };
     if (waves < 1) waves = 1;
+    int64_t left = P.ngroups;
+    if (mode == 1) {
+        int64_t ticket = 0;
+        std::vector<int64_t> cur((size_t)waves), nxt((size_t)waves, -1);
+        std::vector<int> order((size_t)waves);
+        for (int w = 0; w < waves; ++w) { cur[(size_t)w] = ticket++; order[(size_t)w] = w; }
+        while (left > 0) {
+            bool progress = false;
+            std::sort(order.begin(), order.end(), [&](int a, int b) { return cur[(size_t)a] > cur[(size_t)b]; });
+            for (int w : order) {
+                if (cur[(size_t)w] >= P.ngroups) continue;
+                if (nxt[(size_t)w] < 0) nxt[(size_t)w] = ticket++;      // drawn while the current group waits
+                const int rc = run_group(cur[(size_t)w]);
+                if (rc > 0) return rc;
+                if (rc == 0) { cur[(size_t)w] = nxt[(size_t)w]; nxt[(size_t)w] = -1; --left; progress = true; }
+            }
+            if (!progress) return 20;
+        }
+    }
     std::vector<int64_t> next((size_t)waves);
     for (int w = 0; w < waves; ++w) next[(size_t)w] = w;
-    int64_t left = P.ngroups;
     while (left > 0) {
         bool progress = false;
         for (int w = waves - 1; w >= 0; --w) {

@@ -21,6 +21,8 @@ extern "C" int kz_emul_sweep_f64(int nrows, int ncols, const int *Lp, const int 
     if (build_kz_lane_plan(nrows, ncols, Lp, Lj, reinterpret_cast<const unsigned char *>(Lx), 8, start, stop, step, P)) return 2;
     const int L = P.L, K = P.K, RPW = P.RPW;
     stats[0] = L; stats[1] = K; stats[2] = P.ngroups; stats[3] = P.nslots; stats[4] = P.nlevels; stats[5] = P.max_version; stats[6] = P.max_level_groups;
+    stats[7] = 0;
+    for (int64_t e = 0; e < P.nslots; ++e) stats[7] += (P.idx[(size_t)e] & KZL_NONE) != 0;      // padding slots (of stats[3])
     const double *vals = reinterpret_cast<const double *>(P.vals.data());
     std::vector<int> version((size_t)ncols, 0);
     std::vector<char> done((size_t)nrows, 0);

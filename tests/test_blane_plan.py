@@ -48,7 +48,8 @@ def block_operator(nb, bs, per_row, seed, band=25):
     return A, np.ascontiguousarray(Dinv)
 
 
-def run(lib, A, Dinv, x, b, start, stop, step, waves, snapshot=0):
+def run(lib, A, Dinv, x, b, start, stop, step, waves, snapshot=0, want_L=8, mode=0):
+    """want_L = 8: what build_blane_part hands the planner at lane_L = 0; mode 0: the static form"""
     bs = A.blocksize[0]
     nb = A.shape[0] // bs
     xx = np.array(x, dtype=np.float64)
@@ -57,7 +58,7 @@ def run(lib, A, Dinv, x, b, start, stop, step, waves, snapshot=0):
     bAp, bAj = np.ascontiguousarray(A.indptr, dtype=np.int32), np.ascontiguousarray(A.indices, dtype=np.int32)
     bAx = np.ascontiguousarray(A.data, dtype=np.float64)
     rc = lib.blane_emul_sweep_f64(nb, bs, p(bAp), p(bAj), p(bAx), p(np.ascontiguousarray(Dinv, dtype=np.float64)), p(xx),
-                                  p(np.ascontiguousarray(b, dtype=np.float64)), start, stop, step, waves, snapshot, p(stats))
+                                  p(np.ascontiguousarray(b, dtype=np.float64)), start, stop, step, waves, snapshot, want_L, mode, p(stats))
     return rc, xx, stats
 
 
