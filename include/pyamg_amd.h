@@ -1031,6 +1031,24 @@ int pamg_solver_set_graph(pamg_solver_t S, int enable);
  * the solve again from the caller's initial guess and succeeds; pamg_solver_iterate / pcg / (f)gmres report the timeout
  * once (their state is on the device) and are safe from the next call on */
 int pamg_solver_stats(pamg_solver_t S, int64_t stats[8]);
+/* The TAIL OF THE HIERARCHY AS ONE DENSE OPERATOR.  A cycle enters every level below the finest with x = 0; smoothers, transfers and the tabulated
+ * coarsest solve are linear and stationary, so everything from a level t down is x_t = M b_t with one constant n_t x n_t matrix per kind of visit (the
+ * cycle type and cycles per level the recursion reaches level t with).  M is tabulated with the launches the cycle runs (b_t = e_j, j < n_t) at the first
+ * cycle of that kind, outside any graph capture, and checked once: a seeded random b_t through M and through the launches, relative max norm at most 1e-13
+ * (f64; the same multiple of the unit round-off in f32), else the form is declined.  The visit of level t is then one launch, x_t = M b_t; the second
+ * visits of W and F cycles run r_t = b_t - A_t x_t, x_t += M r_t.  Results agree with the launches to rounding, not bit for bit.
+ * mode 0 = automatic: t = the first level of at most max_rows rows whose parent has more than 32768 rows (an operator pays back its tabulation after some n_t cycles:
+ * the automatic form is for hierarchies whose set-up already costs seconds); 1 = off; 2 = forced: t = the first level below
+ * the finest of at most max_rows rows.  max_rows 0 = default (1024; at most 4096).  Declined -- the launches stay -- for AMLI cycles, a Krylov smoother
+ * or coarse relaxation on a level >= t, a host coarse solver, a Gauss-Seidel-family smoother in order-exact mode on a level >= t, a solver used as the
+ * collapsed part of a sharded cycle, a persistent sweep that timed out.  May be called before or after pamg_solver_finalize (then the captured graphs
+ * are dropped). */
+int pamg_solver_dense_tail(pamg_solver_t S, int mode, int max_rows);
+/* info = {operators built, reason of the last decline (0 none, 1 off, 2 no level meets the rule, 3 AMLI cycle, 4 Krylov smoother, 5 host coarse solver,
+ * 6 order-exact Gauss-Seidel, 7 sharded cycle, 8 sweep time-out during tabulation, 9 guard above its bar, 10 the solver fell back to level launches),
+ * tail level t (-1 none), rows n_t, bytes of the operators, applications enqueued (a captured cycle counts once, its replays do not), mode, max_rows,
+ * 0...}; figures (may be NULL) = {milliseconds of tabulation, the largest guard figure measured}. */
+int pamg_solver_dense_tail_info(pamg_solver_t S, int64_t info[16], double figures[2]);
 
 /* ------------------------------------------------------------------------------------------------
  * Row-sharded cycle of ONE rank (one process per GPU): MultilevelSolver.__solve (multilevel.py:584-662) and

@@ -231,6 +231,8 @@ def _declare(lib):
     f("pamg_solver_store", _vp, _vp, _vp)
     f("pamg_solver_stream", _vp, P(_vp))
     f("pamg_solver_stats", _vp, P(C.c_int64))
+    f("pamg_solver_dense_tail", _vp, _i, _i)
+    f("pamg_solver_dense_tail_info", _vp, P(C.c_int64), P(C.c_double))
     f("pamg_dist_create", P(_vp), _i, _i, _i)
     f("pamg_dist_destroy", _vp)
     f("pamg_dist_add_level", _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _i, _vp, _vp, _vp, _i, _vp, _vp)

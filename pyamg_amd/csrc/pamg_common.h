@@ -324,6 +324,13 @@ int vec_xpby(int dtype, int64_t n, double beta, const void *z, void *p, hipStrea
 int vec_axpy_ratio(int dtype, int64_t n, const double *num, const double *den, double sign, const void *x, void *y, hipStream_t s);
 int vec_fill(int dtype, int64_t n, double v, void *y, hipStream_t s);
 int dense_gemv(int dtype, int n, const void *M, const void *b, void *x, hipStream_t s);
+// the tail of a hierarchy as one dense operator (pamg_solver.hip: DenseTail): x = M b / x += M b in one launch that stages b in LDS, hence the hard limit
+// on the rows.  DENSE_TAIL_MAX_ROWS is the automatic rule's limit: a PLACEHOLDER until the scan over 256 / 512 / 1024 / 2048 rows on the device exists
+// (each application streams 8 n^2 bytes, 8 MB at 1024 rows)
+constexpr int DENSE_TAIL_HARD_MAX_ROWS = 4096;
+constexpr int DENSE_TAIL_MAX_ROWS = 1024;
+int dense_tail_apply(int dtype, int n, const void *M, const void *b, void *x, bool acc, hipStream_t s);
+int dense_transpose(int dtype, int n, const void *src, void *dst, hipStream_t s);                // dst = src^T, n x n row-major
 int block_gs_sweep(pamg_matrix_s *A, void *x, const void *b, const void *Dinv, int row_start,
                    int row_stop, int row_step, hipStream_t s);
 int block_jacobi_step(pamg_matrix_s *A, int kind, const void *Dinv, const void *xsrc, void *xdst,

@@ -1628,6 +1628,45 @@ __global__ __launch_bounds__(BLK) void dense_gemv_kernel(int n, const T *M, cons
     if (lane == 0) x[row] = (T)acc;
 }
 
+// x = M b (ACC: x += M b), dense row-major n x n: the tail of a hierarchy as one operator (pamg_solver.hip, dense tail).  One wave per row, b staged
+// in LDS once per workgroup (n values of dynamic LDS), lane k adds columns k, k + 64, ... into four partial sums by a fixed partition, then the XOR
+// butterfly of pamg_wave.h: the same bits in every run, whatever the grid looks like
+template <typename T, bool ACC>
+__global__ __launch_bounds__(BLK) void dense_tail_kernel(int n, const T *__restrict__ M, const T *__restrict__ b, T *__restrict__ x)
+{
+    extern __shared__ __align__(16) unsigned char tail_lds[];
+    T *sb = reinterpret_cast<T *>(tail_lds);
+    for (int k = threadIdx.x; k < n; k += BLK) sb[k] = b[k];
+    __syncthreads();
+    const int row = blockIdx.x * (BLK / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= n) return;                                          // (a whole wave, after the only barrier)
+    const T *Mr = M + (size_t)row * n;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int k = lane;
+    for (; k + 192 < n; k += 256) {
+        const T m0 = Mr[k], m1 = Mr[k + 64], m2 = Mr[k + 128], m3 = Mr[k + 192];
+        a0 += (double)m0 * (double)sb[k];
+        a1 += (double)m1 * (double)sb[k + 64];
+        a2 += (double)m2 * (double)sb[k + 128];
+        a3 += (double)m3 * (double)sb[k + 192];
+    }
+    for (; k < n; k += 64) a0 += (double)Mr[k] * (double)sb[k];
+    const double acc = seg_allreduce<64>((a0 + a1) + (a2 + a3));
+    if (lane == 0) x[row] = ACC ? (T)((double)x[row] + acc) : (T)acc;
+}
+
+// dst = src^T, dense n x n (once per tabulated tail operator: its columns arrive as contiguous rows)
+template <typename T>
+__global__ __launch_bounds__(BLK) void dense_transpose_kernel(int n, const T *__restrict__ src, T *__restrict__ dst)
+{
+    const int64_t nn = (int64_t)n * n;
+    for (int64_t k = (int64_t)blockIdx.x * BLK + threadIdx.x; k < nn; k += (int64_t)gridDim.x * BLK) {
+        const int64_t i = k / n, j = k - i * n;
+        dst[k] = src[j * n + i];
+    }
+}
+
 // ------------------------------------------------------------------ true block smoothers
 // One lane per block row; blocks are tiny (bs <= 8) so the dense products stay in
 // registers.  Arithmetic order follows amg_core::block_jacobi / block_gauss_seidel

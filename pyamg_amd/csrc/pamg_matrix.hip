@@ -1986,6 +1986,32 @@ int dense_gemv(int dtype, int n, const void *M, const void *b, void *x, hipStrea
     return (int)hipGetLastError();
 }
 
+// x = M b or (acc) x += M b with the dense n x n operator of a hierarchy's tail: one launch, n values of LDS
+int dense_tail_apply(int dtype, int n, const void *M, const void *b, void *x, bool acc, hipStream_t s)
+{
+    if (n <= 0) return PAMG_OK;
+    if (n > DENSE_TAIL_HARD_MAX_ROWS || !M || !b || !x) return PAMG_E_ARG;
+    const int grid = (n + (BLK / 64) - 1) / (BLK / 64);
+    const size_t lds = (size_t)n * tsize(dtype);
+    if (dtype == PAMG_F64) {
+        if (acc) hipLaunchKernelGGL((dense_tail_kernel<double, true>), dim3(grid), dim3(BLK), lds, s, n, (const double *)M, (const double *)b, (double *)x);
+        else hipLaunchKernelGGL((dense_tail_kernel<double, false>), dim3(grid), dim3(BLK), lds, s, n, (const double *)M, (const double *)b, (double *)x);
+    } else {
+        if (acc) hipLaunchKernelGGL((dense_tail_kernel<float, true>), dim3(grid), dim3(BLK), lds, s, n, (const float *)M, (const float *)b, (float *)x);
+        else hipLaunchKernelGGL((dense_tail_kernel<float, false>), dim3(grid), dim3(BLK), lds, s, n, (const float *)M, (const float *)b, (float *)x);
+    }
+    return (int)hipGetLastError();
+}
+
+int dense_transpose(int dtype, int n, const void *src, void *dst, hipStream_t s)
+{
+    if (n <= 0) return PAMG_OK;
+    const int grid = (int)std::min<int64_t>(((int64_t)n * n + BLK - 1) / BLK, 4096);
+    if (dtype == PAMG_F64) hipLaunchKernelGGL((dense_transpose_kernel<double>), dim3(grid), dim3(BLK), 0, s, n, (const double *)src, (double *)dst);
+    else hipLaunchKernelGGL((dense_transpose_kernel<float>), dim3(grid), dim3(BLK), 0, s, n, (const float *)src, (float *)dst);
+    return (int)hipGetLastError();
+}
+
 }  // namespace pamg
 
 // =============================================================================== C ABI

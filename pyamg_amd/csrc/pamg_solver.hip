@@ -6,6 +6,8 @@
 // on one stream, captured into a hipGraph per (cycle type, cycles_per_level) and replayed,
 // which removes the host launch cost of the many tiny coarse-level / GS-level kernels.
 #include <algorithm>
+#include <cfloat>
+#include <chrono>
 #include <cmath>
 #include <functional>
 #include <map>
@@ -185,7 +187,26 @@ int poly_apply(pamg_matrix_s *A, void *x, const void *b, void *work, const doubl
 
 }  // namespace
 
+// The tail of the hierarchy as one dense operator (pamg_solver_dense_tail).  A cycle enters every level below the finest with x = 0, and smoothers,
+// transfers and the tabulated coarsest solve are linear and stationary: everything from the tail level t down is x_t = M b_t with one constant
+// n_t x n_t matrix per kind of sub-cycle (key: the cycle type and cycles per level the recursion reaches level t with; 0 where t is the coarsest
+// level).  M is tabulated column by column with the launches the cycle runs, outside any graph capture, and checked against them once.
+enum { TAIL_OFF = 1, TAIL_NO_LEVEL, TAIL_AMLI, TAIL_SMOOTHER, TAIL_COARSE_HOST, TAIL_ORDER_EXACT, TAIL_DIST, TAIL_TIMEOUT, TAIL_GUARD, TAIL_FALLBACK };
+struct DenseTail {
+    int mode = 0;                         // 0 automatic, 1 off, 2 forced: the first level within max_rows
+    int max_rows = DENSE_TAIL_MAX_ROWS;
+    int level = -1;                       // t (chosen at finalize), -1 = none
+    int declined = 0;                     // TAIL_* of the last decline, 0 = none
+    bool dist = false;                    // the solver runs as the collapsed part of a sharded cycle: never
+    bool active = false;                  // the cycle being enqueued uses the operators (set per run_cycle)
+    std::map<int, void *> ops;            // key -> M (device, row-major, the solver's dtype)
+    size_t bytes = 0;
+    double tab_ms = 0.0, guard = 0.0;     // tabulation time of all operators; the largest plan-time guard figure
+    long long applications = 0;           // launches enqueued (a captured cycle counts once, its replays do not: as the sweep counters)
+};
+
 struct pamg_solver_s {
+    DenseTail tail;
     int dtype = PAMG_F64;
     std::vector<Level> levels;
     void *d_coarse = nullptr;     // dense coarse operator (row-major n_c x n_c)
@@ -395,6 +416,21 @@ int coarse_solve(pamg_solver_s *S, const void *b, void *x, hipStream_t s)
     return dense_gemv(S->dtype, S->n_c, S->d_coarse, b, x, s);
 }
 
+// ---- the dense tail: which operator a visit of level t takes
+int tail_key(const pamg_solver_s *S, int t, int type, int cpl)
+{
+    if (t == (int)S->levels.size() - 1) return 0;                 // the coarsest solve: the same map under every cycle
+    return 1 + type * 1024 + (type == PAMG_CYCLE_V ? 1 : cpl);
+}
+
+const void *tail_op(const pamg_solver_s *S, int lvl, int type, int cpl)
+{
+    const DenseTail &T = S->tail;
+    if (!T.active || lvl != T.level) return nullptr;
+    auto it = T.ops.find(tail_key(S, lvl, type, cpl));
+    return it == T.ops.end() ? nullptr : it->second;
+}
+
 // multilevel.py:584-662
 int cycle_rec(pamg_solver_s *S, int lvl, int type, int cpl, bool x_zero, hipStream_t s)
 {
@@ -406,16 +442,27 @@ int cycle_rec(pamg_solver_s *S, int lvl, int type, int cpl, bool x_zero, hipStre
     PAMG_TRY(stream_launch(L.A, EPI_RESID, L.x, L.b, L.r, 0.0, 0.0, nullptr, s));      // r = b - A x
     // b_c = R r and x_c = 0 in one launch (multilevel.py:613-615)
     PAMG_TRY(stream_launch(L.R, EPI_SET, L.r, nullptr, N.b, 0.0, 0.0, reinterpret_cast<double *>(N.x), s));
+    // the visit of level lvl + 1: the recursion (the coarsest solve on the last level), or -- where the dense tail starts there and holds the
+    // operator of this kind of visit -- one launch: from zero x = M b; a second visit of a W / F cycle r = b - A x, x += M r (exact for a
+    // stationary linear cycle)
+    auto down = [&](int ty, int c, bool xz) -> int {
+        const void *M = tail_op(S, lvl + 1, ty, c);
+        if (!M) return lvl == nlev - 2 ? coarse_solve(S, N.b, N.x, s) : cycle_rec(S, lvl + 1, ty, c, xz, s);
+        if (!xz) PAMG_TRY(stream_launch(N.A, EPI_RESID, N.x, N.b, N.r, 0.0, 0.0, nullptr, s));
+        PAMG_TRY(dense_tail_apply(S->dtype, (int)N.n, M, xz ? N.b : N.r, N.x, !xz, s));
+        S->tail.applications++;
+        return PAMG_OK;
+    };
     if (lvl == nlev - 2) {
-        PAMG_TRY(coarse_solve(S, N.b, N.x, s));
+        PAMG_TRY(down(type, cpl, true));
     } else if (type == PAMG_CYCLE_V) {
-        PAMG_TRY(cycle_rec(S, lvl + 1, PAMG_CYCLE_V, 1, true, s));
+        PAMG_TRY(down(PAMG_CYCLE_V, 1, true));
     } else if (type == PAMG_CYCLE_W) {
-        PAMG_TRY(cycle_rec(S, lvl + 1, PAMG_CYCLE_W, cpl, true, s));
-        PAMG_TRY(cycle_rec(S, lvl + 1, PAMG_CYCLE_W, cpl, false, s));
+        PAMG_TRY(down(PAMG_CYCLE_W, cpl, true));
+        PAMG_TRY(down(PAMG_CYCLE_W, cpl, false));
     } else if (type == PAMG_CYCLE_F) {
-        PAMG_TRY(cycle_rec(S, lvl + 1, PAMG_CYCLE_F, cpl, true, s));
-        for (int k = 0; k < cpl; ++k) PAMG_TRY(cycle_rec(S, lvl + 1, PAMG_CYCLE_V, 1, false, s));
+        PAMG_TRY(down(PAMG_CYCLE_F, cpl, true));
+        for (int k = 0; k < cpl; ++k) PAMG_TRY(down(PAMG_CYCLE_V, 1, false));
     } else if (type == PAMG_CYCLE_AMLI) {
         // multilevel.py:628-656: two inner corrections, each a recursive AMLI solve from an
         // initial guess of ones, A-orthogonalised against the previous one and line-searched.
@@ -471,8 +518,182 @@ int enqueue_cycle(pamg_solver_s *S, int type, int cpl, bool check, bool x_zero, 
     return reduce_partials(L0.A->d_partial, L0.A->nblk, S->d_slot, s);
 }
 
+// ---- the dense tail: level choice, tabulation, guard
+void tail_free(pamg_solver_s *S)
+{
+    DenseTail &T = S->tail;
+    for (auto &kv : T.ops) hipFree(kv.second);
+    T.ops.clear();
+    S->bytes -= std::min(S->bytes, T.bytes);
+    T.bytes = 0;
+    T.active = false;
+}
+
+// graphs captured earlier may hold launches that read the operators: they go first
+void tail_decline(pamg_solver_s *S, int why)
+{
+    if (!S->tail.ops.empty() || !S->graphs.empty()) { hipDeviceSynchronize(); drop_graphs(S); }
+    tail_free(S);
+    S->tail.level = -1;
+    S->tail.declined = why;
+}
+
+// what of the rule is known when the solver is finalized (or the mode changes): the level and the smoothers below it.
+// Automatic: the first level of at most max_rows rows whose parent has more than TAIL_PARENT_MIN_ROWS rows; forced (mode 2): the first level below the
+// finest within max_rows.  Why the parent's size: an operator costs n_t sub-cycles of the tail to tabulate and saves a fraction of one per cycle, so it
+// pays back after some n_t cycles of that kind -- the automatic form is for hierarchies whose set-up already costs seconds (a parent of more than
+// 4 x ONE_XCD_MAX_ROWS rows sits under fine levels of millions of rows) and leaves every smaller hierarchy's launches, level by level, as they are.
+constexpr int64_t TAIL_PARENT_MIN_ROWS = 4 * ONE_XCD_MAX_ROWS;
+void tail_choose(pamg_solver_s *S)
+{
+    DenseTail &T = S->tail;
+    tail_decline(S, 0);
+    if (T.mode == 1) { T.declined = TAIL_OFF; return; }
+    if (T.dist) { T.declined = TAIL_DIST; return; }
+    const int nlev = (int)S->levels.size();
+    const int64_t lim = std::min<int64_t>(T.max_rows, DENSE_TAIL_HARD_MAX_ROWS);
+    int t = -1;
+    for (int l = 1; l < nlev && t < 0; ++l)
+        if (S->levels[l].n >= 1 && S->levels[l].n <= lim && (T.mode == 2 || S->levels[l - 1].n > TAIL_PARENT_MIN_ROWS)) t = l;
+    if (t < 0) { T.declined = TAIL_NO_LEVEL; return; }
+    if (S->coarse_host) { T.declined = TAIL_COARSE_HOST; return; }
+    if (S->fallbacks) { T.declined = TAIL_FALLBACK; return; }
+    for (int l = t; l < nlev; ++l) {
+        const Level &L = S->levels[l];
+        if (l == nlev - 1 && !S->coarse_relax) break;
+        for (const Smoother *sm : {&L.pre, &L.post}) {
+            if (l == nlev - 1 && sm == &L.post) break;            // the coarsest level relaxes with its first slot only
+            if (sm->kind == PAMG_SMOOTH_KRYLOV) { T.declined = TAIL_SMOOTHER; return; }
+            const bool gs = sm->kind == PAMG_SMOOTH_GS || sm->kind == PAMG_SMOOTH_SOR || sm->kind == PAMG_SMOOTH_BLOCK_GS ||
+                            sm->kind == PAMG_SMOOTH_GS_NE || sm->kind == PAMG_SMOOTH_GS_NR;
+            // the order-exact mode keeps the reference's bits, and therefore its launches
+            if (gs && L.A->gs_order != 1) { T.declined = TAIL_ORDER_EXACT; return; }
+        }
+    }
+    T.level = t;
+}
+
+// the launches the operator replaces: the sub-cycle of level t from x_t = 0 on the level's own vectors
+int tail_subcycle(pamg_solver_s *S, int t, int type, int cpl, hipStream_t s)
+{
+    Level &L = S->levels[t];
+    PAMG_HIP(hipMemsetAsync(L.x, 0, (size_t)L.n * tsize(S->dtype), s));
+    if (t == (int)S->levels.size() - 1) return coarse_solve(S, L.b, L.x, s);
+    return cycle_rec(S, t, type, cpl, true, s);
+}
+
+// M of one key: column j = the sub-cycle's answer to b_t = e_j, then one seeded random b_t through both.  *why: 0 = built, else TAIL_*
+int tail_build(pamg_solver_s *S, int type, int cpl, hipStream_t s, void **out, int *why)
+{
+    DenseTail &T = S->tail;
+    const int t = T.level, dt = S->dtype;
+    Level &L = S->levels[t];
+    const int n = (int)L.n;
+    const size_t ts = tsize(dt), vb = (size_t)n * ts;
+    *out = nullptr; *why = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    void *Mt = nullptr, *M = nullptr;
+    PAMG_HIP(hipMalloc(&Mt, std::max<size_t>(vb * n, 256)));
+    const bool was_active = T.active;
+    T.active = false;                                            // (the launches, whatever else is built already)
+    int st = PAMG_OK;
+    for (int j = 0; j < n && st == PAMG_OK; ++j) {
+        st = (int)hipMemsetAsync(L.b, 0, vb, s);
+        if (st == PAMG_OK) st = vec_fill(dt, 1, 1.0, (char *)L.b + (size_t)j * ts, s);
+        if (st == PAMG_OK) st = tail_subcycle(S, t, type, cpl, s);
+        if (st == PAMG_OK) st = (int)hipMemcpyAsync((char *)Mt + (size_t)j * vb, L.x, vb, hipMemcpyDeviceToDevice, s);
+    }
+    // (no dalloc: its clearing memset runs on the null stream, which this stream does not wait for; the transposition writes every entry)
+    const size_t mbytes = std::max<size_t>(vb * n, 256);
+    if (st == PAMG_OK) st = (int)hipMalloc(&M, mbytes);
+    if (st == PAMG_OK) st = dense_transpose(dt, n, Mt, M, s);
+    // the guard: the launched sub-cycle against M b_t for one seeded random b_t, relative max norm
+    std::vector<double> hb((size_t)n), hx((size_t)n), hm((size_t)n);
+    std::vector<float> fb, fx, fm;
+    unsigned long long lcg = 0x9E3779B97F4A7C15ull;
+    for (int i = 0; i < n; ++i) {
+        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+        hb[i] = (double)(lcg >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0;
+    }
+    const void *src = hb.data();
+    if (dt == PAMG_F32) { fb.assign(hb.begin(), hb.end()); fx.resize(n); fm.resize(n); src = fb.data(); }
+    void *dst_x = dt == PAMG_F32 ? (void *)fx.data() : (void *)hx.data(), *dst_m = dt == PAMG_F32 ? (void *)fm.data() : (void *)hm.data();
+    if (st == PAMG_OK) st = (int)hipMemcpyAsync(L.b, src, vb, hipMemcpyHostToDevice, s);
+    if (st == PAMG_OK) st = tail_subcycle(S, t, type, cpl, s);
+    if (st == PAMG_OK) st = (int)hipMemcpyAsync(dst_x, L.x, vb, hipMemcpyDeviceToHost, s);
+    if (st == PAMG_OK) st = dense_tail_apply(dt, n, M, L.b, L.x, false, s);
+    if (st == PAMG_OK) st = (int)hipMemcpyAsync(dst_m, L.x, vb, hipMemcpyDeviceToHost, s);
+    if (st == PAMG_OK) st = (int)hipStreamSynchronize(s);
+    T.active = was_active;
+    hipFree(Mt);
+    auto give_up = [&](int reason) { if (M) hipFree(M); *why = reason; };
+    if (st != PAMG_OK) { give_up(0); return st; }
+    // a sweep that timed out left garbage in a column: the solver switches schedulers as after a solve, the form is declined
+    const int swept = check_sweeps(S);
+    if (swept == PAMG_E_TIMEOUT) {
+        give_up(TAIL_TIMEOUT);
+        if (S->fallbacks == 0) PAMG_TRY(fall_back_to_level_launches(S));
+        return PAMG_OK;
+    }
+    if (swept != PAMG_OK) { give_up(0); return swept; }
+    if (dt == PAMG_F32) for (int i = 0; i < n; ++i) { hx[i] = fx[i]; hm[i] = fm[i]; }
+    double dmax = 0.0, xmax = 0.0;
+    bool finite = true;
+    for (int i = 0; i < n; ++i) {
+        finite = finite && std::isfinite(hx[i]) && std::isfinite(hm[i]);
+        dmax = std::max(dmax, std::fabs(hx[i] - hm[i]));
+        xmax = std::max(xmax, std::fabs(hx[i]));
+    }
+    const double fig = !finite ? INFINITY : xmax > 0.0 ? dmax / xmax : (dmax > 0.0 ? INFINITY : 0.0);
+    T.guard = std::max(T.guard, fig);
+    // the project's form-against-form bar: 1e-13 in f64 (as the dense block-triangular and merged forms), the same multiple of the unit round-off in f32
+    const double bar = dt == PAMG_F64 ? 1e-13 : 1e-13 * ((double)FLT_EPSILON / DBL_EPSILON);
+    if (!(fig <= bar)) { give_up(TAIL_GUARD); return PAMG_OK; }
+    T.bytes += mbytes;
+    S->bytes += mbytes;
+    if (getenv("PAMG_TIMING"))
+        fprintf(stderr, "[pamg timing] dense tail: level %d, %d rows, cycle type %d: tabulated in %.1f ms, guard %.2e, %zu bytes\n", t, n, type,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), fig, mbytes);
+    T.tab_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *out = M;
+    return PAMG_OK;
+}
+
+// before a cycle of (type, cpl) is enqueued or captured: build what it needs (never inside a capture) and say whether this cycle uses the form
+int ensure_tail(pamg_solver_s *S, int type, int cpl, hipStream_t s)
+{
+    DenseTail &T = S->tail;
+    T.active = false;
+    if (T.level < 0) return PAMG_OK;
+    if (T.dist) { tail_decline(S, TAIL_DIST); return PAMG_OK; }
+    if (type == PAMG_CYCLE_AMLI) {                                 // not linear in b: this cycle keeps its launches
+        if (T.ops.empty()) T.declined = TAIL_AMLI;
+        return PAMG_OK;
+    }
+    if (S->fallbacks) { tail_decline(S, TAIL_FALLBACK); return PAMG_OK; }
+    // an F cycle reaches level t as an F cycle first and as V cycles afterwards
+    const int kinds[2][2] = {{type, cpl}, {PAMG_CYCLE_V, 1}};
+    const int nk = (type == PAMG_CYCLE_F && T.level < (int)S->levels.size() - 1) ? 2 : 1;
+    for (int k = 0; k < nk; ++k) {
+        const int key = tail_key(S, T.level, kinds[k][0], kinds[k][1]);
+        if (T.ops.count(key)) continue;
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        PAMG_HIP(hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone) return PAMG_OK;      // somebody else's capture: this cycle runs its launches
+        void *M = nullptr;
+        int why = 0;
+        PAMG_TRY(tail_build(S, kinds[k][0], kinds[k][1], s, &M, &why));
+        if (!M) { tail_decline(S, why); return PAMG_OK; }
+        T.ops[key] = M;
+    }
+    T.active = true;
+    T.declined = 0;
+    return PAMG_OK;
+}
+
 int run_cycle(pamg_solver_s *S, int type, int cpl, hipStream_t s, bool check = true, bool x_zero = false)
 {
+    PAMG_TRY(ensure_tail(S, type, cpl, s));
     if (!S->use_graph || S->host_sync) return enqueue_cycle(S, type, cpl, check, x_zero, s);
     const int key = ((type * 1024 + cpl) * 2 + (check ? 1 : 0)) * 2 + (x_zero ? 1 : 0);
     auto it = S->graphs.find(key);
@@ -1355,6 +1576,7 @@ int pamg_solver_destroy(pamg_solver_t S)
 {
     if (!S) return PAMG_OK;
     drop_graphs(S);
+    tail_free(S);
     for (Level &L : S->levels) {
         if (L.A) L.A->borrowed--;
         if (L.P) L.P->borrowed--;
@@ -1678,6 +1900,7 @@ int pamg_solver_finalize(pamg_solver_t S)
     PAMG_TRY(dalloc(S, (void **)&S->d_scratch, 1032 * sizeof(double)));
     PAMG_HIP(hipStreamCreateWithFlags(&S->own_stream, hipStreamNonBlocking));
     S->finalized = true;
+    tail_choose(S);                                            // the operators themselves: at the first cycle of each kind (ensure_tail)
     return PAMG_OK;
 }
 
@@ -1718,6 +1941,8 @@ int solver_cycle_inline(pamg_solver_s *S, void *x, const void *b, int cycle, int
     if (!S || !x || !b || !s) return PAMG_E_ARG;
     if (!S->finalized) return PAMG_E_STATE;
     if (cycle == PAMG_CYCLE_AMLI) return PAMG_E_UNSUPPORTED;     // its work vectors are allocated on first use
+    S->tail.dist = true;                                         // the dense tail is the resident solver's: here the launches stay
+    S->tail.active = false;
     Level &L0 = S->levels[0];
     const size_t vb = (size_t)L0.n * tsize(S->dtype);
     PAMG_HIP(hipMemcpyAsync(L0.x, x, vb, hipMemcpyDeviceToDevice, s));
@@ -1974,6 +2199,32 @@ int pamg_solver_stats(pamg_solver_t S, int64_t stats[8])
     stats[3] = (int64_t)S->graphs.size();
     stats[4] = S->fallbacks;
     stats[5] = -1; stats[6] = 0;   // (round 3's hierarchy tail in one launch: retired in round 5 -- slower than the replayed graph of small launches)
+    return PAMG_OK;
+}
+
+int pamg_solver_dense_tail(pamg_solver_t S, int mode, int max_rows)
+{
+    if (!S || mode < 0 || mode > 2 || max_rows < 0) return PAMG_E_ARG;
+    S->tail.mode = mode;
+    S->tail.max_rows = max_rows == 0 ? DENSE_TAIL_MAX_ROWS : max_rows;
+    if (S->finalized) tail_choose(S);                          // (drops the operators and the graphs that hold their launches)
+    return PAMG_OK;
+}
+
+int pamg_solver_dense_tail_info(pamg_solver_t S, int64_t info[16], double figures[2])
+{
+    if (!S || !info) return PAMG_E_ARG;
+    const DenseTail &T = S->tail;
+    for (int k = 0; k < 16; ++k) info[k] = 0;
+    info[0] = (int64_t)T.ops.size();
+    info[1] = T.declined;
+    info[2] = T.level;
+    info[3] = T.level >= 0 ? S->levels[T.level].n : 0;
+    info[4] = (int64_t)T.bytes;
+    info[5] = T.applications;
+    info[6] = T.mode;
+    info[7] = T.max_rows;
+    if (figures) { figures[0] = T.tab_ms; figures[1] = T.guard; }
     return PAMG_OK;
 }
 

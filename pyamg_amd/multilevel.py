@@ -389,6 +389,39 @@ def _set_smoother(lib, S, level, which, s: Optional[SmootherSpec], dtype, aux, f
         f"pamg_solver_set_smoother({s.kind})")
 
 
+# pamg_solver_dense_tail_info's reason codes (include/pyamg_amd.h)
+DENSE_TAIL_REASONS = (None, "off", "no level meets the rule", "AMLI cycle", "Krylov smoother", "host coarse solver", "order-exact Gauss-Seidel",
+                      "sharded cycle", "sweep time-out during tabulation", "guard above its bar", "fell back to level launches")
+DENSE_TAIL_HARD_MAX_ROWS = 4096
+
+
+def dense_tail_args(dense_tail):
+    """``DeviceMultilevelSolver(dense_tail=...)`` -> (mode, max_rows) of ``pamg_solver_dense_tail``: None = automatic with the default limit,
+    False = off, a dict with ``mode`` (0 automatic, 1 off, 2 forced; default 2: a caller who passes a dict asks for the form) and ``max_rows``
+    (1 .. 4096, default 0 = the library's).  With None, the environment's PAMG_DENSE_TAIL decides where it is set: ``0`` = off, ``auto`` or
+    ``force``, optionally with a row limit (``auto:2048``) -- for scans through tools that build their own solvers."""
+    if dense_tail is None:
+        import os
+        env = os.environ.get("PAMG_DENSE_TAIL", "").strip()
+        if env:
+            word, _, rows = env.partition(":")
+            if word not in ("0", "auto", "force") or (rows and not rows.isdigit()):
+                raise ValueError("PAMG_DENSE_TAIL must be 0, auto[:rows] or force[:rows]")
+            return dense_tail_args({"mode": {"0": 1, "auto": 0, "force": 2}[word], "max_rows": int(rows or 0)})
+    if dense_tail is None or dense_tail is True:
+        return 0, 0
+    if dense_tail is False:
+        return 1, 0
+    if not isinstance(dense_tail, dict) or set(dense_tail) - {"mode", "max_rows"}:
+        raise ValueError("dense_tail must be None, False or dict(mode=..., max_rows=...)")
+    mode, rows = int(dense_tail.get("mode", 2)), int(dense_tail.get("max_rows", 0))
+    if mode not in (0, 1, 2):
+        raise ValueError("dense_tail: mode must be 0 (automatic), 1 (off) or 2 (forced)")
+    if rows < 0 or rows > DENSE_TAIL_HARD_MAX_ROWS:
+        raise ValueError(f"dense_tail: max_rows must lie in 0 .. {DENSE_TAIL_HARD_MAX_ROWS}")
+    return mode, rows
+
+
 class DeviceMultilevelSolver:
     """MI355X-resident multigrid solve phase for a reference-built hierarchy.
 
@@ -417,13 +450,20 @@ class DeviceMultilevelSolver:
     dense_tri : None (automatic), False (off on every level) or a dict ``{level: dict(mode=..., block_rows=...)}`` -- the dense block-triangular form
         of the symmetric Gauss-Seidel sweeps (``DeviceMatrix.dense_tri``; fast order, f64).  Automatic: mid-size coarse levels (more than 8192 rows,
         inverse triangles at most 16 x the operator's bytes) smoothed by symmetric Gauss-Seidel before and after.  Agrees with the merged form to rounding.
+    dense_tail : None (automatic), False (off) or ``dict(mode=..., max_rows=...)`` -- the tail of the hierarchy as one dense operator
+        (``pamg_solver_dense_tail``): every visit of the tail level t is one launch x_t = M b_t, M tabulated once per kind of cycle with the launches it
+        replaces and checked against them.  Automatic: t = the first level of at most 1024 rows below a level of more than 32768 rows; mode 2 forces the
+        first level within ``max_rows``.  Declined (``stats()['dense_tail']['declined']`` says why) for AMLI cycles, Krylov smoothers or a host coarse
+        solver in the tail, and for ``order='exact'``.  Agrees with the launches to rounding (1e-13), not bit for bit.
     """
 
     def __init__(self, ml, device: Optional[int] = None, graph: bool = True, autotune: Optional[bool] = None,
                  level_tune=None, order: Optional[str] = None, strict: bool = True, renumber: Optional[bool] = None,
-                 schwarz_setup: str = "reference", dense_tri=None):
+                 schwarz_setup: str = "reference", dense_tri=None, dense_tail=None):
         import os
         self.fallback = None
+        self._dense_tail = dense_tail
+        tail_mode, tail_rows = dense_tail_args(dense_tail)
         if schwarz_setup not in ("reference", "device"):
             raise ValueError("schwarz_setup must be 'reference' or 'device'")
         self.schwarz_setup, self._schwarz_reports = schwarz_setup, {}
@@ -433,7 +473,7 @@ class DeviceMultilevelSolver:
             # CPU restatement of ours -- and it is announced once.
             try:
                 self.__init__(ml, device=device, graph=graph, autotune=autotune, level_tune=level_tune, order=order, strict=True, renumber=renumber,
-                              schwarz_setup=schwarz_setup, dense_tri=dense_tri)
+                              schwarz_setup=schwarz_setup, dense_tri=dense_tri, dense_tail=dense_tail)
                 return
             except NotImplementedError as e:
                 if isinstance(ml, HierarchySpec) or not hasattr(ml, "solve"):
@@ -571,6 +611,7 @@ class DeviceMultilevelSolver:
             M = np.ascontiguousarray(self.spec.coarse_op, dtype=self.dtype)     # row-major for the device gemv
             capi.check(lib.pamg_solver_set_coarse_dense(h, capi.ptr(M), n_c), "set_coarse")
         capi.check(lib.pamg_solver_set_graph(h, int(bool(graph))), "set_graph")
+        capi.check(lib.pamg_solver_dense_tail(h, tail_mode, tail_rows), "pamg_solver_dense_tail")
         capi.check(lib.pamg_solver_finalize(h), "pamg_solver_finalize")
         self.symmetric_smoothing = getattr(self.ml, "symmetric_smoothing", False)
         self._xd = capi.DeviceArray(self.shape[0], self.dtype)
@@ -604,6 +645,12 @@ class DeviceMultilevelSolver:
         capi.check(capi.lib().pamg_solver_stats(self.handle, a), "pamg_solver_stats")
         out = {"levels": int(a[0]), "gs_level_launches": int(a[1]), "hbm_bytes": int(a[2]), "graphs": int(a[3]),
                "sweep_timeouts_recovered": int(a[4])}
+        t, fig = (C.c_int64 * 16)(), (C.c_double * 2)()
+        capi.check(capi.lib().pamg_solver_dense_tail_info(self.handle, t, fig), "pamg_solver_dense_tail_info")
+        # the tail of the hierarchy as one dense operator: operators built (one per kind of cycle run so far), why it was declined (None: it was not),
+        # tail level and its rows, bytes, launches enqueued (a captured cycle counts once), tabulation time, the plan-time guard's figure
+        out["dense_tail"] = {"built": int(t[0]), "declined": DENSE_TAIL_REASONS[int(t[1])], "level": int(t[2]), "rows": int(t[3]), "bytes": int(t[4]),
+                             "applications": int(t[5]), "mode": int(t[6]), "max_rows": int(t[7]), "tabulation_ms": float(fig[0]), "guard": float(fig[1])}
         if self._schwarz_reports:
             # levels smoothed by Schwarz: what built the inverted blocks of the pre- / post-smoother ('reference': the blocks of the
             # hierarchy as given; 'device': pamg_schwarz_blocks, with its info -- entries, largest block, Jacobi sweeps of the slowest
@@ -888,7 +935,7 @@ class DeviceMultilevelSolver:
         ml = self.ml
         device, graph, autotune, level_tune = self._device, self._graph, self._autotune, self._level_tune
         self.free()
-        self.__init__(ml, device=device, graph=graph, autotune=autotune, level_tune=level_tune, order=self.order)
+        self.__init__(ml, device=device, graph=graph, autotune=autotune, level_tune=level_tune, order=self.order, dense_tail=self._dense_tail)
 
     def aspreconditioner(self, cycle="V"):
         """multilevel.py:355-396: LinearOperator applying one cycle from x = 0."""

@@ -54,7 +54,17 @@ def kernel_map(dml, smoother_kind):
     mats = list(dml._mats)
     out = []
     k = 0
+    tail = dml.stats().get("dense_tail", {})
+    t = tail["level"] if tail.get("built") and tail.get("applications") else nlev
     for i in range(nlev):
+        if i == t:
+            # the tail of the hierarchy as one dense operator (csrc/pamg_solver.hip, DenseTail): every launch of the levels >= t is replaced by
+            # x_t = M b_t -- M streamed once, b_t read, x_t written
+            n, vb = tail["rows"], dml.dtype.itemsize
+            out.append({"family": "dense_tail", "grid": (n + 3) // 4, "level": i, "op": "M", "what": "tail of the hierarchy as one dense operator",
+                        "rows": int(n), "nnz": int(n * n), "bytes_alg": int(vb * n * n + 2 * vb * n), "bytes_streamed": int(vb * n * n + 2 * vb * n),
+                        "format": f"dense {n} x {n}, row-major, one wave per row"})
+            break
         A = mats[k]; k += 1
         P = R = None
         if i < nlev - 1:

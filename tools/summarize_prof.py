@@ -85,6 +85,8 @@ def family(k):
         return "gs_tile", None
     if k.startswith("gs_gran") or k.startswith("gs_flow"):
         return "gs_gran", None
+    if k.startswith("dense_tail"):
+        return "dense_tail", None
     if k.startswith("bsr_lane"):
         return "bsr_lane", None
     if k.startswith("bsr_gran") or k.startswith("bsr_small") or k.startswith("bsr_flow"):
