@@ -394,6 +394,31 @@ int pamg_approx_ideal_restriction_pass2(const int32_t *Rp, int Rp_size, int32_t 
                                         const int32_t *Cpts, int Cpts_size, const int32_t *splitting, int splitting_size,
                                         int32_t distance, int32_t use_gmres, int32_t maxiter, int32_t precondition);
 
+/* The BLOCK (BSR) form of the AIR setup (csrc/pamg_air_block.hip, the per-row arithmetic in csrc/pamg_air_block.h over pamg_air.h).
+ * float64, square blocks of 1 .. 8 stored row-major, HOST arrays; every result is the reference's, bit for bit.  Pass 1 and the one-point
+ * interpolation of a block operator are the two calls above on its block pattern.
+ *
+ * The block measure of classical_strength_of_connection(block=True), strength.py:200-214: out[p] for the stored block p -- norm 0
+ * ('abs') the largest |a|, 1 ('min') the smallest a, 2 ('fro') the sum of a * a down the rows of every column first, then across the
+ * columns left to right (NumPy's order for blocksize <= 7; 'fro' with blocksize 8 is PAMG_E_UNSUPPORTED: NumPy sums eight values with
+ * eight accumulators) -- and +0.0 where the magnitude is below 1e-16.  The result on the block pattern goes to
+ * pamg_classical_strength_of_connection_abs ('abs', 'fro') or _min.  blocksize > 8: PAMG_E_UNSUPPORTED. */
+int pamg_block_strength_measure(int32_t n_blocks, int32_t blocksize, int32_t norm, const double *Ax, int Ax_size, double *out,
+                                int out_size);
+/* amg_core::block_approx_ideal_restriction_pass2, air.h:378-584: A and R in BSR (Ax: Ap[n] blocks of blocksize^2 values, Rx the same for
+ * Rp[Cpts_size] blocks), C the block strength pattern.  Per row the neighbourhood Nf ascending, then Cpts[r] with the identity block LAST;
+ * the N blocks solve the system of order N * blocksize for blocksize right-hand sides: ONE Householder QR, then Q^T b and upper_tri_solve
+ * per right-hand side, operation for operation; a solution entry is stored where its magnitude exceeds 1e-15 and as +0.0 otherwise.  A
+ * group of 8 / 16 / 32 / 64 lanes per row by N * blocksize; systems beyond 64 are solved by the same routine on the host threads inside
+ * the library.  Rj / Rx need no initialisation.  Rp is checked against pass 1's counts: PAMG_E_ARG, and nothing is written.
+ * use_gmres != 0 or blocksize > 8: PAMG_E_UNSUPPORTED, and nothing is written. */
+int pamg_block_approx_ideal_restriction_pass2(const int32_t *Rp, int Rp_size, int32_t *Rj, int Rj_size, double *Rx, int Rx_size,
+                                              const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *Ax,
+                                              int Ax_size, const int32_t *Cp, int Cp_size, const int32_t *Cj, int Cj_size,
+                                              const double *Cx, int Cx_size, const int32_t *Cpts, int Cpts_size,
+                                              const int32_t *splitting, int splitting_size, int32_t blocksize, int32_t distance,
+                                              int32_t use_gmres, int32_t maxiter, int32_t precondition);
+
 /* The amg_core calls of the evolution strength measure (csrc/pamg_evolution.hip, the per-row arithmetic in csrc/pamg_evolution.h).
  * float64, HOST arrays, amg_core's argument order; every result is the reference's, bit for bit.  Every pattern is checked before
  * anything is written (PAMG_E_ARG): null pointers, negative sizes, a pointer that does not start at 0 or decreases, fewer than Sp[n]

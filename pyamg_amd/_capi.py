@@ -130,6 +130,8 @@ def _declare(lib):
     f("pamg_one_point_interpolation", *(_vp, _i) * 7)
     f("pamg_approx_ideal_restriction_pass1", *(_vp, _i) * 5, _i)
     f("pamg_approx_ideal_restriction_pass2", *(_vp, _i) * 11, _i, _i, _i, _i)
+    f("pamg_block_strength_measure", _i, _i, _i, _vp, _i, _vp, _i)
+    f("pamg_block_approx_ideal_restriction_pass2", *(_vp, _i) * 11, _i, _i, _i, _i, _i)
     f("pamg_incomplete_mat_mult_csr_f64", *(_vp, _i) * 9, _i)
     f("pamg_evolution_strength_helper_f64", *(_vp, _i) * 3, _i, *(_vp, _i) * 3, _i, _i, _d)
     f("pamg_apply_distance_filter_f64", _i, _d, *(_vp, _i) * 3)

@@ -762,7 +762,7 @@ _CLASSICAL_NAMES = ("classical_strength_of_connection", "direct_interpolation", 
 
 @contextlib.contextmanager
 def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False, evolution=False,
-                 energy=False, energy_gmres=False, distance=False, cljp=False):
+                 energy=False, energy_gmres=False, distance=False, cljp=False, block_air=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -826,7 +826,16 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     pass do not depend on the order of the C-points (``pyamg_amd.classical``, csrc/pamg_cljp.h).  The ``JP`` / ``LDF`` colourings and BSR
     input go to the function that was patched out; the serial ``RS`` splitting and ``CR`` are order-dependent and stay with the reference.
     A keyword of its own so that ``classical=True`` keeps patching exactly the names it patches today; off by default for the reason
-    given for ``classical``.  With ``cljp=False`` nothing is patched or imported on its account."""
+    given for ``classical``.  With ``cljp=False`` nothing is patched or imported on its account.
+    ``block_air=True`` routes the setup of ``air_solver`` on BSR operators to ``pyamg_amd.block_air``: ``classical_strength_of_connection``,
+    ``one_point_interpolation`` and ``local_air`` in ``<pyamg>.classical.air``, and the latter two in ``.classical.interpolate`` too -- the
+    block measure, the one-point rule with identity blocks, and one dense solve of order N * b with b right-hand sides per C-point, bit
+    for bit.  Each patch wraps whatever is bound when it is applied, and it is applied after ``air``'s: what the block functions do not take
+    (CSR operators, ``block=False``, blocks beyond 8, ``norm='fro'`` with blocks of 8, ``use_gmres=True``) goes to the CSR function of
+    ``air=True`` when that keyword is on, and from there, or directly, to the reference.  The patches are undone in reverse order, so a
+    name that two keywords patched ends as it was found.  A keyword of its own so that ``air=True`` keeps patching exactly the names it
+    patches today; off by default for the reason given for ``classical`` (DESIGN 3b has the first timings).  With ``block_air=False``
+    nothing is patched or imported on its account."""
     import importlib
     from . import air as _air
     from . import classical as _cls
@@ -857,6 +866,14 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     cljp_table = ((("classical.split", "CLJP", _cls.CLJP), ("classical.split", "CLJPc", _cls.CLJPc),
                    ("classical.split", "vertex_coloring", _cls.vertex_coloring), ("graph", "vertex_coloring", _cls.vertex_coloring)) +
                   ((("classical.air", "CLJP", _cls.CLJP), ("classical.air", "CLJPc", _cls.CLJPc)) if air else ())) if cljp else ()
+    block_table = ()
+    if block_air:
+        from . import block_air as _blk
+        block_table = (("classical.air", "classical_strength_of_connection", _blk.classical_strength_of_connection),
+                       ("classical.air", "one_point_interpolation", _blk.one_point_interpolation),
+                       ("classical.interpolate", "one_point_interpolation", _blk.one_point_interpolation),
+                       ("classical.air", "local_air", _blk.local_air),
+                       ("classical.interpolate", "local_air", _blk.local_air))
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
                           ("aggregation.aggregation", "richardson_prolongation_smoother", richardson_prolongation_smoother),
@@ -877,8 +894,8 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                           ("classical.classical", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.interpolate", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.split", "PMIS", _cls.PMIS),
-                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table + distance_table + cljp_table:
-        of_air = (mod, name, fn) in air_table
+                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table + distance_table + cljp_table + block_table:
+        of_air = (mod, name, fn) in air_table or (mod, name, fn) in block_table
         if not classical and name in _CLASSICAL_NAMES and not of_air:
             continue                            # (before the import: with classical=False nothing of <pyamg>.classical is touched)
         try:
@@ -911,5 +928,5 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     finally:
         _HANDOFF[0] = was
         _clear_resident()
-        for m, name, old in targets:
+        for m, name, old in reversed(targets):      # (two keywords may have patched one name: the last patch is undone first)
             setattr(m, name, old)

@@ -7,9 +7,9 @@ Same signatures, same error types, same return formats, and the reference's arra
 is csrc/pamg_air.h).  The strength matrix of ``local_air`` comes from ``pyamg_amd.classical``, and ``R.eliminate_zeros()`` stays with SciPy
 on the host, where the reference has it.
 
-Float64 CSR operators.  What the device path does not take (BSR operators, other formats and dtypes, ``use_gmres=True``, index arrays
-beyond int32) raises ``NotImplementedError``; ``aggregation.device_setup(pyamg, air=True)`` then hands the call to the reference function
-it patched out.
+Float64 CSR operators; BSR operators have a module of their own, ``pyamg_amd.block_air`` (``device_setup(pyamg, block_air=True)``), and
+are refused here.  What the device path does not take (other formats and dtypes, ``use_gmres=True``, index arrays beyond int32) raises
+``NotImplementedError``; ``aggregation.device_setup(pyamg, air=True)`` then hands the call to the reference function it patched out.
 """
 from __future__ import annotations
 

@@ -20,6 +20,7 @@ __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_
            "cljp_naive_splitting", "vertex_coloring_mis", "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2", "remove_strong_FF_connections",
            "rs_classical_interpolation_pass1", "rs_classical_interpolation_pass2",
            "one_point_interpolation", "approx_ideal_restriction_pass1", "approx_ideal_restriction_pass2",
+           "block_strength_measure", "block_approx_ideal_restriction_pass2",
            "incomplete_mat_mult_csr", "evolution_strength_helper", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
            "evolution_strength_vector", "relaxation_vectors", "distance_measure", "distance_strength", "vertex_distance", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "satisfy_constraints", "energy_cg", "energy_gmres"]
 
@@ -367,6 +368,31 @@ def approx_ideal_restriction_pass2(Rp, Rj, Rx, Ap, Aj, Ax, Cp, Cj, Cx, Cpts, spl
     capi.check(capi.lib().pamg_approx_ideal_restriction_pass2(*_pairs(Rp, Rj, Rx, Ap, Aj, Ax, Cp, Cj, Cx, Cpts, splitting), int(distance),
                                                              int(bool(use_gmres)), int(maxiter), int(bool(precondition))),
                "approx_ideal_restriction_pass2")
+
+
+# ------------------------------------------------------------------ block (BSR) AIR setup: csrc/pamg_air_block.hip
+BLOCK_NORMS = {"abs": 0, "min": 1, "fro": 2}
+
+
+def block_strength_measure(blocksize, norm, Ax, out):
+    """the block measure of classical_strength_of_connection(block=True) (strength.py:200-214; no amg_core twin: the reference composes
+    it in NumPy): ``out[p]`` for the stored block ``Ax[p * blocksize**2:(p + 1) * blocksize**2]``, ``norm`` one of 'abs', 'min', 'fro',
+    with magnitudes below 1e-16 as 0.0.  'fro' with blocksize 8 and blocks beyond 8 raise NotImplementedError."""
+    _f64(Ax, out)
+    if norm not in BLOCK_NORMS:
+        raise ValueError("Invalid choice of norm.")
+    capi.check(capi.lib().pamg_block_strength_measure(int(out.size), int(blocksize), BLOCK_NORMS[norm], *_pairs(Ax, out)), "block_strength_measure")
+
+
+def block_approx_ideal_restriction_pass2(Rp, Rj, Rx, Ap, Aj, Ax, Cp, Cj, Cx, Cpts, splitting, blocksize, distance=2, use_gmres=0, maxiter=10,
+                                         precondition=1):
+    """amg_core.block_approx_ideal_restriction_pass2 (air.h:378-584): one QR of the system of order N * blocksize per C-point and
+    blocksize right-hand sides; ``use_gmres`` and blocks beyond 8 raise NotImplementedError.  Rx need not be zeroed."""
+    _idx(Rp, Rj, Ap, Aj, Cp, Cj, Cpts, splitting)
+    _f64(Rx, Ax, Cx)
+    capi.check(capi.lib().pamg_block_approx_ideal_restriction_pass2(*_pairs(Rp, Rj, Rx, Ap, Aj, Ax, Cp, Cj, Cx, Cpts, splitting), int(blocksize),
+                                                                   int(distance), int(bool(use_gmres)), int(maxiter), int(bool(precondition))),
+               "block_approx_ideal_restriction_pass2")
 
 
 # ------------------------------------------------------------------ evolution strength of connection: csrc/pamg_evolution.hip

@@ -242,6 +242,19 @@ PYBIND11_MODULE(_amg_core_pybind, m)
              "approx_ideal_restriction_pass2");
     }, nc("Rp"), nc("Rj"), nc("Rx"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Cp"), nc("Cj"), nc("Cx"), nc("Cpts"), nc("splitting"),
        py::arg("distance") = 2, py::arg("use_gmres") = 0, py::arg("maxiter") = 10, py::arg("precondition") = 1);
+    // the block (BSR) AIR setup, float64 (air_bind.cpp): csrc/pamg_air_block.hip.  norm: 0 'abs', 1 'min', 2 'fro'
+    m.def("block_strength_measure", [](int blocksize, int norm, D &Ax, D &out) {
+        done(pamg_block_strength_measure(len(out), blocksize, norm, Ax.data(), len(Ax), out.mutable_data(), len(out)), "block_strength_measure");
+    }, py::arg("blocksize"), py::arg("norm"), nc("Ax"), nc("out"));
+    m.def("block_approx_ideal_restriction_pass2", [](Idx &Rp, Idx &Rj, D &Rx, Idx &Ap, Idx &Aj, D &Ax, Idx &Cp, Idx &Cj, D &Cx, Idx &Cpts,
+                                                      Idx &splitting, int blocksize, int distance, int use_gmres, int maxiter, int precondition) {
+        done(pamg_block_approx_ideal_restriction_pass2(Rp.data(), len(Rp), Rj.mutable_data(), len(Rj), Rx.mutable_data(), len(Rx), Ap.data(), len(Ap),
+                                                       Aj.data(), len(Aj), Ax.data(), len(Ax), Cp.data(), len(Cp), Cj.data(), len(Cj), Cx.data(),
+                                                       len(Cx), Cpts.data(), len(Cpts), splitting.data(), len(splitting), blocksize, distance,
+                                                       use_gmres, maxiter, precondition),
+             "block_approx_ideal_restriction_pass2");
+    }, nc("Rp"), nc("Rj"), nc("Rx"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Cp"), nc("Cj"), nc("Cx"), nc("Cpts"), nc("splitting"), py::arg("blocksize"),
+       py::arg("distance") = 2, py::arg("use_gmres") = 0, py::arg("maxiter") = 10, py::arg("precondition") = 1);
     // the evolution strength measure, float64 (evolution_strength_bind.cpp): csrc/pamg_evolution.hip
     m.def("incomplete_mat_mult_csr", [](Idx &Ap, Idx &Aj, D &Ax, Idx &Bp, Idx &Bj, D &Bx, Idx &Sp, Idx &Sj, D &Sx, int num_rows) {
         done(pamg_incomplete_mat_mult_csr_f64(Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), Bp.data(), len(Bp), Bj.data(), len(Bj),

@@ -147,8 +147,10 @@ int launch_solve(Bufs &d, int nlist, const int *rows, const int *Ap, const int *
     return PAMG_OK;
 }
 
+}  // namespace
+
 // N of every C-row: the device's counts, and the host threads for what did not fit its slots
-int neighbourhood_counts(int n, int nc, const int *Cp, const int *Cj, const int *Cpts, const int *splitting, int distance, const int *dCp,
+int pamg::air_neighbourhood_counts(int n, int nc, const int *Cp, const int *Cj, const int *Cpts, const int *splitting, int distance, const int *dCp,
                          const int *dCj, const int *dCpts, const int *dsp, Bufs &d, std::vector<int> &cnt)
 {
     cnt.assign((size_t)nc, 0);
@@ -170,14 +172,12 @@ int neighbourhood_counts(int n, int nc, const int *Cp, const int *Cj, const int 
     return PAMG_OK;
 }
 
-int check_cf(int n, const int *Cpts, int Cpts_size, const int *splitting, int splitting_size)
+int pamg::air_check_cf(int n, const int *Cpts, int Cpts_size, const int *splitting, int splitting_size)
 {
     if (Cpts_size < 0 || (Cpts_size && !Cpts) || splitting_size < n || (n && !splitting)) return PAMG_E_ARG;
     for (int r = 0; r < Cpts_size; ++r) if (Cpts[r] < 0 || Cpts[r] >= n) return PAMG_E_ARG;
     return PAMG_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -224,7 +224,7 @@ int pamg_approx_ideal_restriction_pass1(int32_t *Rp, int Rp_size, const int32_t 
     const int n = Cp_size - 1, nc = Cpts_size;
     int64_t nnz = 0;
     PAMG_TRY(check_pattern(n, n, Cp, Cp_size, Cj, Cj_size, &nnz));
-    PAMG_TRY(check_cf(n, Cpts, Cpts_size, splitting, splitting_size));
+    PAMG_TRY(air_check_cf(n, Cpts, Cpts_size, splitting, splitting_size));
     if (!Rp || Rp_size < nc + 1) return PAMG_E_ARG;
     Rp[0] = 0;
     if (nc == 0) return PAMG_OK;
@@ -234,7 +234,7 @@ int pamg_approx_ideal_restriction_pass1(int32_t *Rp, int Rp_size, const int32_t 
     PAMG_TRY(d.put(&dCp, Cp, (size_t)n + 1)); PAMG_TRY(d.put(&dCj, Cj, (size_t)nnz)); PAMG_TRY(d.put(&dCpts, Cpts, (size_t)nc));
     PAMG_TRY(d.put(&dsp, splitting, (size_t)n));
     std::vector<int> cnt;
-    PAMG_TRY(neighbourhood_counts(n, nc, Cp, Cj, Cpts, splitting, distance, dCp, dCj, dCpts, dsp, d, cnt));
+    PAMG_TRY(air_neighbourhood_counts(n, nc, Cp, Cj, Cpts, splitting, distance, dCp, dCj, dCpts, dsp, d, cnt));
     for (int &c : cnt) c += 1;                              // the identity entry
     return scan_host(nc, cnt.data(), Rp);
 }
@@ -251,7 +251,7 @@ int pamg_approx_ideal_restriction_pass2(const int32_t *Rp, int Rp_size, int32_t 
     int64_t nnzA = 0, nnzC = 0;
     PAMG_TRY(check_pattern(n, n, Ap, Ap_size, Aj, Aj_size, &nnzA));
     PAMG_TRY(check_pattern(n, n, Cp, Cp_size, Cj, Cj_size, &nnzC));
-    PAMG_TRY(check_cf(n, Cpts, Cpts_size, splitting, splitting_size));
+    PAMG_TRY(air_check_cf(n, Cpts, Cpts_size, splitting, splitting_size));
     if (nnzA > Ax_size || (nnzA && !Ax) || !Rp || Rp_size < nc + 1 || Rp[0] != 0) return PAMG_E_ARG;
     if (nc == 0) return PAMG_OK;
     const int nnzR = Rp[nc];
@@ -265,7 +265,7 @@ int pamg_approx_ideal_restriction_pass2(const int32_t *Rp, int Rp_size, int32_t 
     PAMG_TRY(d.put(&dsp, splitting, (size_t)n));
     // the rows of R must be the rows pass 1 counted: nothing below writes outside [Rp[row], Rp[row + 1])
     std::vector<int> cnt;
-    PAMG_TRY(neighbourhood_counts(n, nc, Cp, Cj, Cpts, splitting, distance, dCp, dCj, dCpts, dsp, d, cnt));
+    PAMG_TRY(air_neighbourhood_counts(n, nc, Cp, Cj, Cpts, splitting, distance, dCp, dCj, dCpts, dsp, d, cnt));
     for (int r = 0; r < nc; ++r) if (Rp[r + 1] - Rp[r] != cnt[(size_t)r] + 1) return PAMG_E_ARG;
     PAMG_TRY(d.put(&dAp, Ap, (size_t)n + 1)); PAMG_TRY(d.put(&dAj, Aj, (size_t)nnzA)); PAMG_TRY(d.put(&dAx, Ax, (size_t)nnzA));
     PAMG_TRY(d.put(&dRp, Rp, (size_t)nc + 1)); PAMG_TRY(d.get(&dRj, (size_t)nnzR)); PAMG_TRY(d.get(&dRx, (size_t)nnzR)); PAMG_TRY(d.get(&dflag, 1));

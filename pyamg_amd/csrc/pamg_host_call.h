@@ -63,6 +63,13 @@ inline int check_pattern(int n, int ncol, const int *Ap, int Ap_size, const int 
 // row is not reproducible.
 int device_transposed_pattern(int n, int64_t nnz, const int *dSp, const int *dSj, int *ddeg, int *dTp, int *dTj, int *dcur, unsigned *dflag);
 
+// What the scalar and the block AIR entry points share (pamg_air.hip).  air_check_cf: the C-point list and the splitting of an n-row
+// pattern.  air_neighbourhood_counts: cnt[r] = the size N of the neighbourhood of Cpts[r] (pamg_air.h) -- the device's counts, and the
+// host threads for what did not fit its 64-entry slots; dCp / dCj / dCpts / dsp are the device copies of the host arrays beside them.
+int air_check_cf(int n, const int *Cpts, int Cpts_size, const int *splitting, int splitting_size);
+int air_neighbourhood_counts(int n, int nc, const int *Cp, const int *Cj, const int *Cpts, const int *splitting, int distance, const int *dCp,
+                             const int *dCj, const int *dCpts, const int *dsp, Bufs &d, std::vector<int> &cnt);
+
 // workgroups of a grid-stride launch over n items, per_block of them per workgroup and pass
 inline int launch_grid(int64_t n, int per_block, int cap) { return (int)std::min<int64_t>(cap, std::max<int64_t>(1, (n + per_block - 1) / per_block)); }
 
