@@ -344,6 +344,28 @@ int pamg_cljp_splitting(int32_t n, const int32_t *Sp, int Sp_size, const int32_t
  * x [num_rows] receives the colours; info [2] (may be null): colours, rounds.  Self loops are ignored; the pattern need not be symmetric. */
 int pamg_vertex_coloring_mis(int32_t num_rows, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, int32_t *x, int x_size,
                              int32_t *info);
+/* amg_core::bellman_ford (graph.h:670-697) and amg_core::most_interior_nodes (graph.h:842-889), the reference's argument order, and the
+ * resident loop of pyamg.graph.lloyd_cluster (csrc/pamg_lloyd.hip; the rules, the argument and its limit in csrc/pamg_lloyd.h).  The
+ * reference's in-place serial loop has a closed form -- the unique distances, then for every node the first row that wrote its final value
+ * (sweep and row, a min-fixed-point), then the labels down the predecessor chains -- which order-free rounds of plain launches compute.
+ * The closed form needs exact sums, so every stored weight must be an integer-valued double in [1, 2^31] with n * max(weight) < 2^53, and
+ * the centres unique: otherwise PAMG_E_UNSUPPORTED.  Sizes, null pointers, a column or a centre out of range: PAMG_E_ARG.  All checks
+ * come before any device work and before anything is written; n == 0 returns at once.  Rows need not be sorted.
+ *   pamg_bellman_ford         d [n] in/out: 0 at the sources, +inf elsewhere (anything else: PAMG_E_UNSUPPORTED); m, p [n] in/out: written
+ *                             for the nodes reached through an edge.  info [2] (may be null): distance rounds, stamp rounds
+ *   pamg_most_interior_nodes  m [n] in/out with labels -1 .. c_size-1, p [n] in/out, d [n] out, c [c_size] in/out.  info [3] (may be null):
+ *                             distance rounds, stamp rounds, centres moved (the reference returns "moved != 0")
+ *   pamg_lloyd_cluster        c [c_size] in/out, clusters [n] out: up to maxiter times bellman_ford from the centres and
+ *                             most_interior_nodes, the graph uploaded once, one int read back per iteration beside the round flags.
+ *                             info [4] (may be null): Lloyd iterations run, distance rounds, stamp rounds (of all Bellman-Fords
+ *                             together), centres moved in the last iteration
+ * A Bellman-Ford takes at most n distance rounds and n stamp rounds (more: PAMG_E_NOCONV). */
+int pamg_bellman_ford(int32_t num_nodes, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *Ax, int Ax_size,
+                      const int32_t *c, int c_size, double *d, int d_size, int32_t *m, int m_size, int32_t *p, int p_size, int32_t *info);
+int pamg_most_interior_nodes(int32_t num_nodes, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *Ax, int Ax_size,
+                             int32_t *c, int c_size, double *d, int d_size, int32_t *m, int m_size, int32_t *p, int p_size, int32_t *info);
+int pamg_lloyd_cluster(int32_t num_nodes, const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const double *Ax, int Ax_size,
+                       int32_t *c, int c_size, int32_t maxiter, int32_t *clusters, int clusters_size, int32_t *info);
 /* amg_core::rs_direct_interpolation_pass1 / _pass2, ruge_stuben.h:777-907.  Sx holds the values of A on the pattern of the strength
  * matrix.  Pass 2 checks Pp against pass 1's counts (PAMG_E_ARG).  Rows need not be sorted; no row may hold a column twice. */
 int pamg_rs_direct_interpolation_pass1(int32_t n_nodes, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size,

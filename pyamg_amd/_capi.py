@@ -121,6 +121,9 @@ def _declare(lib):
     f("pamg_pmis_splitting", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, P(_i))
     f("pamg_cljp_splitting", _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp)
     f("pamg_vertex_coloring_mis", _i, _vp, _i, _vp, _i, _vp, _i, _vp)
+    for nm in ("bellman_ford", "most_interior_nodes"):
+        f(f"pamg_{nm}", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp)
+    f("pamg_lloyd_cluster", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp)
     for nm in ("direct", "classical"):
         f(f"pamg_rs_{nm}_interpolation_pass1", _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i)
     interp2 = (_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i)

@@ -762,7 +762,7 @@ _CLASSICAL_NAMES = ("classical_strength_of_connection", "direct_interpolation", 
 
 @contextlib.contextmanager
 def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False, evolution=False,
-                 energy=False, energy_gmres=False, distance=False, cljp=False, block_air=False):
+                 energy=False, energy_gmres=False, distance=False, cljp=False, block_air=False, lloyd=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -835,7 +835,16 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     ``air=True`` when that keyword is on, and from there, or directly, to the reference.  The patches are undone in reverse order, so a
     name that two keywords patched ends as it was found.  A keyword of its own so that ``air=True`` keeps patching exactly the names it
     patches today; off by default for the reason given for ``classical`` (DESIGN 3b has the first timings).  With ``block_air=False``
-    nothing is patched or imported on its account."""
+    nothing is patched or imported on its account.
+    ``lloyd=True`` routes ``lloyd_aggregation`` (in ``<pyamg>.aggregation.aggregation``, ``.aggregation.rootnode`` and
+    ``.aggregation.aggregate``), ``lloyd_cluster`` (in ``.aggregation.aggregate``, where ``lloyd_aggregation`` resolves it, and in
+    ``<pyamg>.graph``) and ``bellman_ford`` (in ``<pyamg>.graph``) to ``pyamg_amd.graph``: ``smoothed_aggregation_solver(aggregate='lloyd')``
+    and ``rootnode_solver(aggregate='lloyd')`` then aggregate on the device, with the reference's arrays and the reference's draw from
+    NumPy's global stream.  The reference's in-place Bellman-Ford has a closed form that order-free rounds compute, but only with exact
+    sums (``pyamg_amd.graph``, csrc/pamg_lloyd.h): integer-valued weights in [1, 2^31] -- ``measure='unit'``, the default, always --, CSR,
+    int32 indices, unique centres.  Real-valued measures, explicit zeros, float32 or complex data, CSC input and ``method='balanced'`` go
+    to the function that was patched out, before anything is drawn.  Off by default for the reason given for ``classical``; with
+    ``lloyd=False`` nothing is patched or imported on its account."""
     import importlib
     from . import air as _air
     from . import classical as _cls
@@ -874,6 +883,15 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                        ("classical.interpolate", "one_point_interpolation", _blk.one_point_interpolation),
                        ("classical.air", "local_air", _blk.local_air),
                        ("classical.interpolate", "local_air", _blk.local_air))
+    lloyd_table = ()
+    if lloyd:
+        from . import graph as _gr
+        lloyd_table = (("aggregation.aggregation", "lloyd_aggregation", _gr.lloyd_aggregation),
+                       ("aggregation.rootnode", "lloyd_aggregation", _gr.lloyd_aggregation),
+                       ("aggregation.aggregate", "lloyd_aggregation", _gr.lloyd_aggregation),
+                       ("aggregation.aggregate", "lloyd_cluster", _gr.lloyd_cluster),
+                       ("graph", "lloyd_cluster", _gr.lloyd_cluster),
+                       ("graph", "bellman_ford", _gr.bellman_ford))
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
                           ("aggregation.aggregation", "richardson_prolongation_smoother", richardson_prolongation_smoother),
@@ -894,7 +912,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                           ("classical.classical", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.interpolate", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.split", "PMIS", _cls.PMIS),
-                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table + distance_table + cljp_table + block_table:
+                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table + distance_table + cljp_table + block_table + lloyd_table:
         of_air = (mod, name, fn) in air_table or (mod, name, fn) in block_table
         if not classical and name in _CLASSICAL_NAMES and not of_air:
             continue                            # (before the import: with classical=False nothing of <pyamg>.classical is touched)
@@ -916,7 +934,8 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
             elif name == "schwarz_parameters":
                 setattr(m, name, _schwarz_parameters_or_reference(old))
             elif name in ("standard_aggregation", "fit_candidates", "evolution_strength_of_connection") or name in _CLASSICAL_NAMES or of_air or \
-                    (mod, name, fn) in energy_table or (mod, name, fn) in distance_table or (mod, name, fn) in cljp_table:
+                    (mod, name, fn) in energy_table or (mod, name, fn) in distance_table or (mod, name, fn) in cljp_table or \
+                    (mod, name, fn) in lloyd_table:
                 setattr(m, name, _device_or_reference(fn, old))
             else:
                 setattr(m, name, fn)

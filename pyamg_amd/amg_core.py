@@ -17,7 +17,7 @@ __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_
            "jacobi", "bsr_jacobi", "block_jacobi", "block_jacobi_indexed", "block_gauss_seidel", "jacobi_indexed", "gauss_seidel_indexed", "overlapping_schwarz_csr", "extract_subblocks", "gauss_seidel_ne",
            "gauss_seidel_nr", "jacobi_ne", "pinv_array", "standard_aggregation", "fit_candidates",
            "classical_strength_of_connection_abs", "classical_strength_of_connection_min", "maximal_independent_set_parallel", "pmis_splitting",
-           "cljp_naive_splitting", "vertex_coloring_mis", "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2", "remove_strong_FF_connections",
+           "cljp_naive_splitting", "vertex_coloring_mis", "bellman_ford", "most_interior_nodes", "lloyd_cluster", "rs_direct_interpolation_pass1", "rs_direct_interpolation_pass2", "remove_strong_FF_connections",
            "rs_classical_interpolation_pass1", "rs_classical_interpolation_pass2",
            "one_point_interpolation", "approx_ideal_restriction_pass1", "approx_ideal_restriction_pass2",
            "block_strength_measure", "block_approx_ideal_restriction_pass2",
@@ -313,6 +313,47 @@ def vertex_coloring_mis(num_rows, Ap, Aj, x, info=None):
     if info is not None:
         info.append(tuple(int(v) for v in out))
     return int(out[0])
+
+
+def _f64(*arrs):
+    for a in arrs:
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.c_contiguous:
+            raise TypeError("incompatible function arguments (float64 only on the device path)")
+
+
+def bellman_ford(num_nodes, Ap, Aj, Ax, c, d, m, p, info=None):
+    """amg_core.bellman_ford (graph.h:670-697), in place on ``d``, ``m``, ``p``.  Exact weights only (csrc/pamg_lloyd.h): anything else
+    raises NotImplementedError.  ``info``: a list that receives (distance rounds, stamp rounds)."""
+    _idx(Ap, Aj, c, m, p)
+    _f64(Ax, d)
+    out = np.zeros(2, dtype=np.int32)
+    capi.check(capi.lib().pamg_bellman_ford(int(num_nodes), *_pairs(Ap, Aj, Ax, c, d, m, p), capi.ptr(out)), "bellman_ford")
+    if info is not None:
+        info.append(tuple(int(v) for v in out))
+
+
+def most_interior_nodes(num_nodes, Ap, Aj, Ax, c, d, m, p, info=None):
+    """amg_core.most_interior_nodes (graph.h:842-889), in place on ``c``, ``d``, ``m``, ``p``; returns whether a centre moved.  ``info``: a
+    list that receives (distance rounds, stamp rounds, centres moved)."""
+    _idx(Ap, Aj, c, m, p)
+    _f64(Ax, d)
+    out = np.zeros(3, dtype=np.int32)
+    capi.check(capi.lib().pamg_most_interior_nodes(int(num_nodes), *_pairs(Ap, Aj, Ax, c, d, m, p), capi.ptr(out)), "most_interior_nodes")
+    if info is not None:
+        info.append(tuple(int(v) for v in out))
+    return bool(out[2])
+
+
+def lloyd_cluster(num_nodes, Ap, Aj, Ax, c, maxiter, clusters, info=None):
+    """the loop of pyamg.graph.lloyd_cluster (graph.py:270-284) with the graph resident, in place on ``c`` and ``clusters``.  ``info``: a
+    list that receives (Lloyd iterations, distance rounds, stamp rounds, centres moved in the last iteration)."""
+    _idx(Ap, Aj, c, clusters)
+    _f64(Ax)
+    out = np.zeros(4, dtype=np.int32)
+    capi.check(capi.lib().pamg_lloyd_cluster(int(num_nodes), *_pairs(Ap, Aj, Ax, c), int(maxiter), *_pairs(clusters), capi.ptr(out)),
+               "lloyd_cluster")
+    if info is not None:
+        info.append(tuple(int(v) for v in out))
 
 
 def rs_direct_interpolation_pass1(n_nodes, Sp, Sj, splitting, Pp):

@@ -200,6 +200,23 @@ PYBIND11_MODULE(_amg_core_pybind, m)
         done(pamg_vertex_coloring_mis(num_rows, Ap.data(), len(Ap), Aj.data(), len(Aj), x.mutable_data(), len(x), info), "vertex_coloring_mis");
         return info[0];                                      // the number of colours, as the reference returns it
     }, py::arg("num_rows"), nc("Ap"), nc("Aj"), nc("x"));
+    m.def("bellman_ford", [](int num_nodes, Idx &Ap, Idx &Aj, Vec<double> &Ax, Idx &c, Vec<double> &d, Idx &mm, Idx &p) {
+        int info[2] = {0, 0};
+        done(pamg_bellman_ford(num_nodes, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), c.data(), len(c), d.mutable_data(), len(d),
+                               mm.mutable_data(), len(mm), p.mutable_data(), len(p), info), "bellman_ford");
+    }, py::arg("num_nodes"), nc("Ap"), nc("Aj"), nc("Ax"), nc("c"), nc("d"), nc("m"), nc("p"));
+    m.def("most_interior_nodes", [](int num_nodes, Idx &Ap, Idx &Aj, Vec<double> &Ax, Idx &c, Vec<double> &d, Idx &mm, Idx &p) {
+        int info[3] = {0, 0, 0};
+        done(pamg_most_interior_nodes(num_nodes, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), c.mutable_data(), len(c),
+                                      d.mutable_data(), len(d), mm.mutable_data(), len(mm), p.mutable_data(), len(p), info), "most_interior_nodes");
+        return info[2] != 0;                                 // whether a centre moved, as the reference returns it
+    }, py::arg("num_nodes"), nc("Ap"), nc("Aj"), nc("Ax"), nc("c"), nc("d"), nc("m"), nc("p"));
+    m.def("lloyd_cluster", [](int num_nodes, Idx &Ap, Idx &Aj, Vec<double> &Ax, Idx &c, int maxiter, Idx &clusters) {
+        int info[4] = {0, 0, 0, 0};
+        done(pamg_lloyd_cluster(num_nodes, Ap.data(), len(Ap), Aj.data(), len(Aj), Ax.data(), len(Ax), c.mutable_data(), len(c), maxiter,
+                                clusters.mutable_data(), len(clusters), info), "lloyd_cluster");
+        return py::make_tuple(info[0], info[1], info[2], info[3]);
+    }, py::arg("num_nodes"), nc("Ap"), nc("Aj"), nc("Ax"), nc("c"), py::arg("maxiter"), nc("clusters"));
     m.def("rs_direct_interpolation_pass1", [](int n_nodes, Idx &Sp, Idx &Sj, Idx &splitting, Idx &Pp) {
         done(pamg_rs_direct_interpolation_pass1(n_nodes, Sp.data(), len(Sp), Sj.data(), len(Sj), splitting.data(), len(splitting), Pp.mutable_data(),
                                                 len(Pp)), "rs_direct_interpolation_pass1");
