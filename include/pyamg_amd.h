@@ -68,6 +68,9 @@ const char *pamg_version(void);
  * dependency analysis of the order-exact sweeps.  PAMG_L1_CACHE=0 in the environment disables it. */
 int pamg_l1_cache_clear(void);
 int pamg_l1_cache_size(int *entries);
+/* How many Layer-1 Schwarz sweeps (pamg_overlapping_schwarz_csr_*) were repeated as one launch per dependency level because a wave
+ * of the persistent sweep gave up waiting (the caller gets the repeated sweep's result and status 0). */
+int pamg_l1_schwarz_reruns(int64_t *count);
 const char *pamg_status_string(int status);
 int pamg_device_count(int *count);
 /* Measured bandwidth ceiling of the current device: kind 0 = copy c = a (16 bytes per element moved), 1 = triad
@@ -153,7 +156,10 @@ int pamg_jacobi_indexed_f32(const int32_t *Ap, int Ap_size, const int32_t *Aj, i
                             const float *b, int b_size, const int32_t *indices, int indices_size,
                             const float *omega, int omega_size);
 /* amg_core::overlapping_schwarz_csr, relaxation.h:1420-1434 (Tx/Tp: the inverted diagonal blocks of the subdomains,
- * row-major, and their offsets; Sj/Sp: the rows of every subdomain, sorted and unique) */
+ * row-major, and their offsets; Sj/Sp: the rows of every subdomain, in any order -- the reference needs them neither
+ * sorted nor unique: a row listed twice takes both increments one after another, in list order, and so it does here).
+ * Subdomains of more than 2048 rows: PAMG_E_UNSUPPORTED, x is left alone.  A persistent sweep that gives up waiting
+ * is repeated as one launch per dependency level from the caller's x (pamg_l1_schwarz_reruns counts them). */
 int pamg_overlapping_schwarz_csr_f64(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size,
                                      const double *Ax, int Ax_size, double *x, int x_size,
                                      const double *b, int b_size, const double *Tx, int Tx_size,
@@ -965,11 +971,21 @@ int pamg_schwarz_destroy(pamg_schwarz_t h);
 int pamg_schwarz_sweep(pamg_schwarz_t h, void *x, const void *b, int row_start, int row_stop, int row_step,
                        pamg_stream_t s);
 int pamg_schwarz_info(pamg_schwarz_t h, int64_t info[4]);   /* subdomains, largest, dependency levels fwd / bwd */
+/* What a (start, stop, step) schedule runs as.  which: 0 / 1 = the handle's two cached schedules (pamg_schwarz_info's fwd / bwd for
+ * a smoother; in general the first schedule swept and the latest other one), -1 = the schedule of the last sweep.  PAMG_E_STATE when
+ * there is none.  info: [0] versioned (the persistent form is available) 1 / 0, [1] the planner's reason where it is not (1 = a row
+ * is updated more than 255 times, 2 = tables too large, 3 = a subdomain lists a row twice), [2] dependency levels, [3] subdomains of
+ * the widest level, [4] slots of the hand-off buffer, [5] reads with a version code ([4], [5]: 0 unless versioned), [6] workgroups of
+ * the schedule's last persistent launch (0 = none yet), [7] its last sweep: 0 = none yet, 1 = one persistent launch, 2 = one launch
+ * per dependency level. */
+int pamg_schwarz_schedule_info(pamg_schwarz_t h, int which, int64_t info[8]);
 /* Scheduler of the sweep: 0 (default) = ONE persistent launch per sweep -- every update of a row gets its own slot of a hand-off buffer
  * (version v of row i), every read is told which version the reference's sequential sweep would find, co-resident waves walk the
  * subdomains in level order and poll the slots they read (csrc/pamg_schwarz.hip); 1 = one launch per dependency level (always live;
  * what pamg_solver_solve switches to after a PAMG_E_TIMEOUT, and what a schedule runs as when a row is updated more than 255 times, a
- * subdomain lists a row twice or the version table would exceed a gigabyte).  Same arithmetic, same bits.  PAMG_SCHWARZ_LEVELS=1 forces 1.
+ * subdomain lists a row twice or the version table would exceed a gigabyte; a schedule of ONE level has nothing to hand over and runs as
+ * its one launch too).  Same arithmetic, same bits -- a subdomain that lists a row twice has its increments added by one lane in list
+ * order, as the reference's sequential loop adds them.  PAMG_SCHWARZ_LEVELS=1 forces 1.
  * pamg_schwarz_error: after a synchronising call -- did a wave of a persistent sweep give up waiting (1) since the last query? */
 int pamg_schwarz_set_mode(pamg_schwarz_t h, int mode);
 int pamg_schwarz_error(pamg_schwarz_t h, int *error);

@@ -192,6 +192,8 @@ def _declare(lib):
     f("pamg_schwarz_destroy", _vp)
     f("pamg_schwarz_sweep", _vp, _vp, _vp, _i, _i, _i, _vp)
     f("pamg_schwarz_info", _vp, P(C.c_int64))
+    f("pamg_schwarz_schedule_info", _vp, _i, P(C.c_int64))
+    f("pamg_l1_schwarz_reruns", P(C.c_int64))
     f("pamg_schwarz_set_mode", _vp, _i)
     f("pamg_schwarz_error", _vp, P(_i))
     f("pamg_solver_set_schwarz_smoother", _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp)

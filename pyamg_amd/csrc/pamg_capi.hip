@@ -240,6 +240,17 @@ int l1_gs_indexed(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size
     return PAMG_OK;
 }
 
+int64_t l1_schwarz_reruns = 0;        // Layer-1 Schwarz sweeps repeated as per-level launches after a time-out (under l1_mu)
+
+// test hook, like check_sweeps of pamg_solver.hip: PAMG_FORCE_TIMEOUT=N reports the first N checks as timed out (caller holds l1_mu)
+bool l1_schwarz_forced_timeout()
+{
+    static int forced = [] { const char *e = getenv("PAMG_FORCE_TIMEOUT"); return e ? atoi(e) : 0; }();
+    if (forced <= 0) return false;
+    --forced;
+    return true;
+}
+
 // amg_core::overlapping_schwarz_csr (relaxation.h:1420-1492)
 template <typename T>
 int l1_schwarz(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, const T *Ax, int Ax_size, T *x, int x_size,
@@ -262,6 +273,18 @@ int l1_schwarz(const int32_t *Ap, int Ap_size, const int32_t *Aj, int Aj_size, c
     if (!st) st = db.put(b, sizeof(T) * (size_t)n);
     if (!st) st = schwarz_sweep(h, dx.p, db.p, row_start, row_stop, row_step, nullptr);
     if (!st) st = (int)hipDeviceSynchronize();
+    // a wave of the persistent sweep gave up waiting: dx holds unfilled slots.  Like pamg_solver_solve: one launch per dependency level
+    // from the caller's x again
+    bool timed_out = false;
+    if (!st) st = schwarz_error(h, &timed_out);
+    if (!st && l1_schwarz_forced_timeout()) timed_out = true;
+    if (!st && timed_out) {
+        schwarz_level_launches(h);
+        ++l1_schwarz_reruns;
+        st = dx.put(x, sizeof(T) * (size_t)n);
+        if (!st) st = schwarz_sweep(h, dx.p, db.p, row_start, row_stop, row_step, nullptr);
+        if (!st) st = (int)hipDeviceSynchronize();
+    }
     if (!st) st = dx.get(x, sizeof(T) * (size_t)n);
     pamg_schwarz_destroy(h);
     return st;
@@ -524,6 +547,14 @@ int pamg_l1_cache_size(int *entries)
     if (!entries) return PAMG_E_ARG;
     std::lock_guard<std::mutex> lock(l1_mu);
     *entries = (int)l1_entries.size();
+    return PAMG_OK;
+}
+
+int pamg_l1_schwarz_reruns(int64_t *count)
+{
+    if (!count) return PAMG_E_ARG;
+    std::lock_guard<std::mutex> lock(l1_mu);
+    *count = l1_schwarz_reruns;
     return PAMG_OK;
 }
 

@@ -37,7 +37,11 @@ struct SchwarzSchedule {
     int *d_order = nullptr;           // subdomains, level after level (sweep order inside a level)
     // the versioned form (persistent sweep); versioned == false: this schedule runs as one launch per level
     bool versioned = false;
+    int declined = 0;                 // why not (SchwarzVersions::declined), 0 = versioned
     int64_t nslots = 0;               // updates of the sweep = slots of the hand-off buffer
+    int64_t nreads = 0;               // stored entries of all member rows = bytes of d_rver
+    int last_grid = 0;                // workgroups of the last persistent launch of this schedule, 0 = none yet
+    int last_form = 0;                // the last sweep of this schedule: 0 = none yet, 1 = one persistent launch, 2 = one launch per level
     int *d_ebase = nullptr;           // [m + 1] first (position, local row) entry of every position of d_order
     int *d_wslot = nullptr;           // [E] slot this update writes
     int *d_prev = nullptr;            // [E] where the row's value before this update is: slot >= 0, or ~row = x itself
@@ -55,7 +59,9 @@ struct pamg_schwarz_s {
     std::vector<int> h_Sp, h_Sj;
     int *d_Sp = nullptr, *d_Sj = nullptr, *d_Tp = nullptr;
     void *d_Tx = nullptr;
+    unsigned char *d_dup = nullptr;   // [nsub] 1 = the subdomain lists a row twice (nullptr: none does)
     pamg::SchwarzSchedule sched[2];
+    int last = -1;                    // the schedule the last sweep ran
     void *d_xs = nullptr;             // hand-off buffer of the persistent sweep: one slot per update (largest schedule)
     int64_t xs_cap = 0;
     unsigned *d_err = nullptr;        // [1] a wave of the persistent sweep gave up waiting
@@ -71,10 +77,10 @@ namespace {
 constexpr int SW_THREADS = 64;        // one wave per subdomain
 constexpr int SW_MAX = 2048;          // rows per subdomain (LDS: one residual each)
 
+// one subdomain of one dependency level per workgroup.  dup: nullptr, or per subdomain 1 = it lists a row twice (the LDS array is then sized twice)
 template <typename T>
-__global__ __launch_bounds__(SW_THREADS) void schwarz_level_kernel(const int *order, int first, const int *Sp, const int *Sj,
-                                                                   const int *Tp, const T *Tx, const int *Ap, const int *Aj,
-                                                                   const T *Ax, T *x, const T *b)
+__device__ __forceinline__ void schwarz_level_body(const int *order, int first, const int *Sp, const int *Sj, const int *Tp, const T *Tx, const int *Ap,
+                                                   const int *Aj, const T *Ax, T *x, const T *b, const unsigned char *dup)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     T *r = reinterpret_cast<T *>(smem);
@@ -89,6 +95,24 @@ __global__ __launch_bounds__(SW_THREADS) void schwarz_level_kernel(const int *or
     }
     __syncthreads();                                      // every residual is formed before x changes
     const T *Tinv = Tx + Tp[d];
+    if (dup && dup[d]) {
+        // the subdomain lists a row twice: the reference adds the increments one after another in list order (x[Sj[j]] += ...), so both land.
+        // The products are formed side by side into the second half of the LDS array (sized for it when dup is given), one lane adds them
+        T *u = r + size;
+        for (int i = threadIdx.x; i < size; i += SW_THREADS) {
+            T s = T(0);
+            const T *ti = Tinv + (size_t)i * size;
+            for (int k = 0; k < size; ++k) s += ti[k] * r[k];
+            u[i] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < size; ++i) {
+                const int row = Sj[s0 + i];
+                x[row] = x[row] + u[i];
+            }
+        return;
+    }
     for (int i = threadIdx.x; i < size; i += SW_THREADS) {
         T s = T(0);
         const T *ti = Tinv + (size_t)i * size;
@@ -96,6 +120,35 @@ __global__ __launch_bounds__(SW_THREADS) void schwarz_level_kernel(const int *or
         const int row = Sj[s0 + i];
         x[row] = x[row] + s;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(SW_THREADS) void schwarz_level_kernel(const int *order, int first, const int *Sp, const int *Sj,
+                                                                   const int *Tp, const T *Tx, const int *Ap, const int *Aj,
+                                                                   const T *Ax, T *x, const T *b)
+{
+    schwarz_level_body<T>(order, first, Sp, Sj, Tp, Tx, Ap, Aj, Ax, x, b, nullptr);
+}
+
+// the same for a handle in which some subdomain lists a row twice
+template <typename T>
+__global__ __launch_bounds__(SW_THREADS) void schwarz_level_dup_kernel(const int *order, int first, const int *Sp, const int *Sj,
+                                                                       const int *Tp, const T *Tx, const int *Ap, const int *Aj,
+                                                                       const T *Ax, T *x, const T *b, const unsigned char *dup)
+{
+    schwarz_level_body<T>(order, first, Sp, Sj, Tp, Tx, Ap, Aj, Ax, x, b, dup);
+}
+
+template <typename T>
+void launch_level(const pamg_schwarz_s *h, const SchwarzSchedule &g, int first, int count, size_t lds, void *x, const void *b, hipStream_t s)
+{
+    const pamg_matrix_s *A = h->A;
+    if (h->d_dup)
+        hipLaunchKernelGGL((schwarz_level_dup_kernel<T>), dim3(count), dim3(SW_THREADS), 2 * lds, s, (const int *)g.d_order, first, h->d_Sp, h->d_Sj, h->d_Tp,
+                           (const T *)h->d_Tx, A->d_Ap, A->d_Aj, (const T *)A->d_Ax, (T *)x, (const T *)b, (const unsigned char *)h->d_dup);
+    else
+        hipLaunchKernelGGL((schwarz_level_kernel<T>), dim3(count), dim3(SW_THREADS), lds, s, (const int *)g.d_order, first, h->d_Sp, h->d_Sj, h->d_Tp,
+                           (const T *)h->d_Tx, A->d_Ap, A->d_Aj, (const T *)A->d_Ax, (T *)x, (const T *)b);
 }
 
 
@@ -306,17 +359,20 @@ __global__ __launch_bounds__(SW_THREADS) void schwarz_versioned_kernel(const int
 }
 
 // the version table of a sweep (pamg_schwarz_plan.h) on the device.  Leaves g.versioned false (the schedule then runs as one launch per
-// level) when the planner declines: a subdomain lists a row twice, a row is updated more than 255 times, tables beyond a gigabyte.
+// level) when the planner declines: a subdomain lists a row twice, a row is updated more than 255 times, tables beyond a gigabyte
+// (g.declined keeps the reason for pamg_schwarz_schedule_info).
 int upload_versions(pamg_schwarz_s *h, SchwarzSchedule &g, const SchwarzLevels &lv)
 {
     const pamg_matrix_s *A = h->A;
     const int n = (int)A->nrows, m = g.m;
     g.versioned = false;
+    g.declined = 0; g.nslots = 0; g.nreads = 0;
     for (void *p : {(void *)g.d_ebase, (void *)g.d_wslot, (void *)g.d_prev, (void *)g.d_roff, (void *)g.d_rver, (void *)g.d_vbase, (void *)g.d_last}) hipFree(p);
     g.d_ebase = g.d_wslot = g.d_prev = g.d_roff = g.d_vbase = g.d_last = nullptr;
     g.d_rver = nullptr;
     SchwarzVersions V;
     schwarz_versions(n, A->h_Ap.data(), A->h_Aj.data(), h->nsub, h->h_Sp.data(), h->h_Sj.data(), g.start, g.step, lv, V);
+    g.declined = V.declined;
     if (!V.ok) return PAMG_OK;
     const int64_t E = V.nslots, R = V.nreads;
     auto up = [](auto **dp, const void *src, size_t bytes) -> hipError_t {
@@ -331,7 +387,7 @@ int upload_versions(pamg_schwarz_s *h, SchwarzSchedule &g, const SchwarzLevels &
     PAMG_HIP(up(&g.d_rver, V.rver.data(), (size_t)R));
     PAMG_HIP(up(&g.d_vbase, V.vbase.data(), sizeof(int) * (size_t)n));
     PAMG_HIP(up(&g.d_last, V.last.data(), sizeof(int) * (size_t)n));
-    g.nslots = E;
+    g.nslots = E; g.nreads = R;
     if (E > h->xs_cap) {
         hipFree(h->d_xs);
         h->d_xs = nullptr;
@@ -352,6 +408,7 @@ int build_schedule(pamg_schwarz_s *h, int start, int stop, int step, SchwarzSche
     g.start = start; g.stop = stop; g.step = step;
     g.level_ptr = lv.level_ptr;
     g.nlevels = lv.nlevels; g.m = lv.m; g.max_width = lv.max_width;
+    g.last_grid = 0; g.last_form = 0;
     if (lv.m == 0) return PAMG_OK;
     hipFree(g.d_order);
     g.d_order = nullptr;
@@ -400,6 +457,7 @@ int schwarz_sweep(pamg_schwarz_s *h, void *x, const void *b, int start, int stop
         g = h->sched[0].d_order ? &h->sched[1] : &h->sched[0];
         PAMG_TRY(build_schedule(h, start, stop, step, *g));
     }
+    h->last = (int)(g - h->sched);
     const pamg_matrix_s *A = h->A;
     const size_t lds = (size_t)std::max(1, h->max_size) * tsize(A->dtype);
     static const int force_levels = [] { const char *e = getenv("PAMG_SCHWARZ_LEVELS"); return (e && *e && *e != '0') ? 1 : 0; }();
@@ -423,18 +481,16 @@ int schwarz_sweep(pamg_schwarz_s *h, void *x, const void *b, int start, int stop
                 hipLaunchKernelGGL((schwarz_close_kernel<float>), dim3(close_grid), dim3(256), 0, s, (const float *)h->d_xs, (const int *)g->d_last, (float *)x, (int)A->nrows);
             }
             PAMG_HIP(hipGetLastError());
+            g->last_grid = grid; g->last_form = 1;
             return PAMG_OK;
         }
     }
+    g->last_form = 2;
     for (int l = 0; l < g->nlevels; ++l) {
         const int first = g->level_ptr[l], count = g->level_ptr[l + 1] - first;
         if (count <= 0) continue;
-        if (A->dtype == PAMG_F64)
-            hipLaunchKernelGGL((schwarz_level_kernel<double>), dim3(count), dim3(SW_THREADS), lds, s, (const int *)g->d_order, first, h->d_Sp, h->d_Sj,
-                               h->d_Tp, (const double *)h->d_Tx, A->d_Ap, A->d_Aj, (const double *)A->d_Ax, (double *)x, (const double *)b);
-        else
-            hipLaunchKernelGGL((schwarz_level_kernel<float>), dim3(count), dim3(SW_THREADS), lds, s, (const int *)g->d_order, first, h->d_Sp, h->d_Sj,
-                               h->d_Tp, (const float *)h->d_Tx, A->d_Ap, A->d_Aj, (const float *)A->d_Ax, (float *)x, (const float *)b);
+        if (A->dtype == PAMG_F64) launch_level<double>(h, *g, first, count, lds, x, b, s);
+        else launch_level<float>(h, *g, first, count, lds, x, b, s);
         PAMG_HIP(hipGetLastError());
     }
     return PAMG_OK;
@@ -507,6 +563,11 @@ int pamg_schwarz_create(pamg_schwarz_t *out, pamg_matrix_t A, int nsub, const in
     if (e == hipSuccess) e = hipMemcpy(h->d_Tp, Tp, sizeof(int) * ((size_t)nsub + 1), hipMemcpyHostToDevice);
     if (e == hipSuccess && ns) e = hipMemcpy(h->d_Sj, Sj, sizeof(int) * (size_t)ns, hipMemcpyHostToDevice);
     if (e == hipSuccess && nt) e = hipMemcpy(h->d_Tx, Tx, nt * ts, hipMemcpyHostToDevice);
+    std::vector<unsigned char> dup;
+    if (e == hipSuccess && schwarz_duplicates(n, nsub, Sp, Sj, dup) > 0) {
+        e = hipMalloc((void **)&h->d_dup, (size_t)nsub);
+        if (e == hipSuccess) e = hipMemcpy(h->d_dup, dup.data(), (size_t)nsub, hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) { pamg_schwarz_destroy(h); return (int)e; }
     h->bytes = sizeof(int) * (2 * ((size_t)nsub + 1) + (size_t)ns) + nt * ts;
     *out = h;
@@ -516,7 +577,7 @@ int pamg_schwarz_create(pamg_schwarz_t *out, pamg_matrix_t A, int nsub, const in
 int pamg_schwarz_destroy(pamg_schwarz_t h)
 {
     if (!h) return PAMG_OK;
-    hipFree(h->d_Sp); hipFree(h->d_Sj); hipFree(h->d_Tp); hipFree(h->d_Tx);
+    hipFree(h->d_Sp); hipFree(h->d_Sj); hipFree(h->d_Tp); hipFree(h->d_Tx); hipFree(h->d_dup);
     for (auto &c : h->sched) {
         hipFree(c.d_order); hipFree(c.d_ebase); hipFree(c.d_wslot); hipFree(c.d_prev); hipFree(c.d_roff); hipFree(c.d_rver); hipFree(c.d_vbase); hipFree(c.d_last);
     }
@@ -551,6 +612,17 @@ int pamg_schwarz_info(pamg_schwarz_t h, int64_t info[4])
 {
     if (!h || !info) return PAMG_E_ARG;
     info[0] = h->nsub; info[1] = h->max_size; info[2] = h->sched[0].nlevels; info[3] = h->sched[1].nlevels;
+    return PAMG_OK;
+}
+
+int pamg_schwarz_schedule_info(pamg_schwarz_t h, int which, int64_t info[8])
+{
+    if (!h || !info || which < -1 || which > 1) return PAMG_E_ARG;
+    if (which < 0) which = h->last;
+    if (which < 0 || !h->sched[which].d_order) return PAMG_E_STATE;
+    const SchwarzSchedule &g = h->sched[which];
+    info[0] = g.versioned ? 1 : 0; info[1] = g.declined; info[2] = g.nlevels; info[3] = g.max_width;
+    info[4] = g.nslots; info[5] = g.nreads; info[6] = g.last_grid; info[7] = g.last_form;
     return PAMG_OK;
 }
 

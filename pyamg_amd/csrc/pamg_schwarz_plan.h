@@ -66,6 +66,22 @@ inline int schwarz_levels(int n, const int *Ap, const int *Aj, int nsub, const i
     return 0;
 }
 
+// the subdomains that list a row twice (dup[d] = 1); returns how many.  The reference adds such a row's increments one after another; the
+// per-level kernel does the same for the flagged subdomains, the version table declines them (code 3)
+inline int schwarz_duplicates(int n, int nsub, const int *Sp, const int *Sj, std::vector<unsigned char> &dup)
+{
+    dup.assign((size_t)std::max(nsub, 1), 0);
+    std::vector<int> seen((size_t)n, -1);
+    int count = 0;
+    for (int d = 0; d < nsub; ++d)
+        for (int q = Sp[d]; q < Sp[d + 1]; ++q) {
+            const int row = Sj[q];
+            if (seen[(size_t)row] == d) { if (!dup[(size_t)d]) ++count; dup[(size_t)d] = 1; }
+            seen[(size_t)row] = d;
+        }
+    return count;
+}
+
 struct SchwarzVersions {
     bool ok = false;                  // false: the schedule runs as one launch per level (why: `declined`)
     int declined = 0;                 // 1 = a row is updated more than 255 times, 2 = tables beyond 31-bit offsets / a gigabyte, 3 = a subdomain lists a row twice
