@@ -268,7 +268,7 @@ struct pamg_matrix_s {
     int dtri_mode = 0;               // 0 = automatic (a solver's levels that meet the rule: dtri_auto_eligible), 1 = off, 2 = on wherever the form fits
     int dtri_block_rows = 0;         // rows per block (0 = DTRI_BLOCK_ROWS)
     struct pamg::DtriSched *dtri = nullptr;
-    bool dtri_unfit = false;         // its planner declined (no unique non-zero diagonal, too large, growth bound)
+    bool dtri_unfit = false;         // its planner declined (no unique non-zero diagonal, a non-finite stored value, too large, growth bound)
     bool dtri_declined_growth = false;
     double dtri_growth = 0.0;        // the guard's figure of the last build: max_i sum_j |W_ij| |a_jj|
     size_t dtri_bytes = 0;           // what the form added to `bytes`

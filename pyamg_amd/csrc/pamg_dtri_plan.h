@@ -35,7 +35,7 @@ constexpr double DTRI_GROWTH_CAP = 1e3;          // the bound build_lanem_plan i
 constexpr int DTRI_BLOCK_ROWS = 2048;            // default block size (profiles/r17_microbench_dtri_scan.json)
 constexpr int DTRI_MAX_BLOCK_ROWS = 8192;
 
-enum : int { DTRI_OK = 0, DTRI_E_SHAPE = 1, DTRI_E_DIAGONAL = 2, DTRI_E_GROWTH = 3 };
+enum : int { DTRI_OK = 0, DTRI_E_SHAPE = 1, DTRI_E_DIAGONAL = 2, DTRI_E_GROWTH = 3, DTRI_E_NONFINITE = 4 };
 
 // first slot of local row i of a packed triangle, and the slots of a triangle of m rows
 PAMG_DTRI_HD int64_t dtri_row_off(int64_t i) { const int64_t p = i >> 1; return (i & 1) ? 2 * (p + 1) * (p + 1) : 2 * p * (p + 1); }
@@ -53,7 +53,10 @@ struct DtriPlan {
 };
 
 // Partition, slices and bookkeeping.  DTRI_E_DIAGONAL: a row without exactly one stored diagonal entry, or a zero / non-finite diagonal value;
-// DTRI_E_SHAPE: nothing to plan.  (The growth guard needs the inverses: dtri_host_growth here, a kernel on the device.)
+// DTRI_E_NONFINITE (a status of its own, not DTRI_E_DIAGONAL): a stored off-diagonal value, in a block or off it, is NaN or infinite -- a dense
+// triangle multiplies its stored zeros by such a value and spreads it over rows the sequential sweep leaves finite, and the growth guard sees
+// in-block values only; DTRI_E_SHAPE: nothing to plan.  The first offending row in row order decides the status.  (The growth guard needs the
+// inverses: dtri_host_growth here, a kernel on the device.)
 inline int build_dtri_plan(int n, const int *Ap, const int *Aj, const double *Ax, int B, DtriPlan &P)
 {
     if (n < 1 || B < 1) return DTRI_E_SHAPE;
@@ -65,14 +68,17 @@ inline int build_dtri_plan(int n, const int *Ap, const int *Aj, const double *Ax
     for (int i = 0; i < n; ++i) {
         const int lo = (i / B) * B, hi = (int)std::min<int64_t>((int64_t)lo + B, n);
         int nd = 0, cl = 0, cu = 0;
+        bool finite = true;
         for (int p = Ap[i]; p < Ap[i + 1]; ++p) {
             const int j = Aj[p];
             if (j < 0 || j >= n) return DTRI_E_SHAPE;
             if (j == i) { ++nd; P.diag[(size_t)i] = Ax[p]; }
+            else finite = finite && std::isfinite(Ax[p]);
             cl += j < lo; cu += j >= hi;
         }
         const double d = P.diag[(size_t)i];
         if (nd != 1 || !(d != 0.0) || !std::isfinite(d)) return DTRI_E_DIAGONAL;
+        if (!finite) return DTRI_E_NONFINITE;
         P.Lp[(size_t)i + 1] = P.Lp[(size_t)i] + cl;
         P.Up[(size_t)i + 1] = P.Up[(size_t)i] + cu;
     }
