@@ -77,6 +77,10 @@ int pamg_device_count(int *count);
  * c = a + s b (24 bytes), n doubles per vector, 16-byte accesses, `reps` timed launches; *gbps = bytes moved / time.
  * bench.py reports it beside the datasheet peak ("also measure an on-device copy/triad ceiling"). */
 int pamg_bandwidth_probe(int kind, int64_t n, int reps, double *gbps);
+/* The register-only segmented inclusive scan of the cluster layout's row sums (seg_scan_incl, csrc/pamg_wave.h) on its own: each of `nwaves`
+ * waves loads 64 (key, value) pairs, scans them and stores the 64 results.  Equal keys on consecutive lanes form one segment.  keys, vals and
+ * out are HOST arrays of 64 * nwaves entries.  Test infrastructure (tests/test_gpu_segscan.py). */
+int pamg_segscan_probe(int64_t nwaves, const unsigned *keys, const double *vals, double *out);
 int pamg_set_device(int device);
 int pamg_get_device(int *device);
 int pamg_device_name(int device, char *buf, int buflen);

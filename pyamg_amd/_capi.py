@@ -70,6 +70,7 @@ def _declare(lib):
     f("pamg_set_device", _i)
     f("pamg_get_device", P(_i))
     f("pamg_bandwidth_probe", _i, C.c_int64, _i, P(C.c_double))
+    f("pamg_segscan_probe", C.c_int64, _vp, _vp, _vp)
     f("pamg_device_name", _i, C.c_char_p, _i)
     f("pamg_malloc", P(_vp), _sz)
     f("pamg_free", _vp)
@@ -388,6 +389,16 @@ def bandwidth_probe(kind: str = "copy", n: int = 1 << 27, reps: int = 20) -> flo
     kinds = {"copy": 0, "triad": 1, "copy1": 2, "copy4": 3, "copy4nt": 4, "copy8": 5, "read": 6, "write": 7, "memcpy": 8, "copy8b": 9, "copy8bnt": 10, "copy1nt": 11, "read_one_xcd": 12, "read_one_xcd_2wg": 13}
     check(lib().pamg_bandwidth_probe(kinds[kind], int(n), int(reps), C.byref(out)), "pamg_bandwidth_probe")
     return float(out.value)
+
+
+def segscan_probe(keys, vals):
+    """the device's segmented inclusive scan (seg_scan_incl of csrc/pamg_wave.h) of (nwaves, 64) uint32 keys and float64 values, one wave per row"""
+    keys, vals = np.ascontiguousarray(keys, dtype=np.uint32), np.ascontiguousarray(vals, dtype=np.float64)
+    if keys.shape != vals.shape or keys.ndim != 2 or keys.shape[1] != 64:
+        raise ValueError("keys and vals are (nwaves, 64) arrays")
+    out = np.empty_like(vals)
+    check(lib().pamg_segscan_probe(keys.shape[0], keys.ctypes.data, vals.ctypes.data, out.ctypes.data), "pamg_segscan_probe")
+    return out
 
 
 def sync():

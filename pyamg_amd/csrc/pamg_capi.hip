@@ -720,6 +720,40 @@ int pamg_bandwidth_probe(int kind, int64_t n, int reps, double *gbps)
     return PAMG_OK;
 }
 
+// ---- the segmented scan of the cluster layout (pamg_wave.h) on its own: one wave per 64 (key, value) pairs
+extern "C++" {
+namespace {
+__global__ __launch_bounds__(256) void segscan_probe_kernel(const unsigned *__restrict__ keys, const double *__restrict__ vals, double *__restrict__ out, int64_t nwaves)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= nwaves) return;                                                             // (wave-uniform: a wave that stays is whole)
+    const int64_t i = w * 64 + lane;
+    out[i] = seg_scan_incl(vals[i], keys[i], lane);
+}
+}  // namespace
+}  // extern "C++"
+
+int pamg_segscan_probe(int64_t nwaves, const unsigned *keys, const double *vals, double *out)
+{
+    if (nwaves < 1 || nwaves > ((int64_t)1 << 24) || !keys || !vals || !out) return PAMG_E_ARG;
+    const size_t n = (size_t)nwaves * 64;
+    unsigned *dk = nullptr;
+    double *dv = nullptr, *dout = nullptr;
+    PAMG_HIP(hipMalloc((void **)&dk, n * sizeof(unsigned)));
+    if (hipMalloc((void **)&dv, n * 8) != hipSuccess) { hipFree(dk); return PAMG_E_ALLOC; }
+    if (hipMalloc((void **)&dout, n * 8) != hipSuccess) { hipFree(dk); hipFree(dv); return PAMG_E_ALLOC; }
+    hipError_t err = hipMemcpy(dk, keys, n * sizeof(unsigned), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(dv, vals, n * 8, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(segscan_probe_kernel, dim3((unsigned)((nwaves + 3) / 4)), dim3(256), 0, 0, (const unsigned *)dk, (const double *)dv, dout, nwaves);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost);
+    hipFree(dk); hipFree(dv); hipFree(dout);
+    return (int)err;
+}
+
 int pamg_device_count(int *count)
 {
     if (!count) return PAMG_E_ARG;

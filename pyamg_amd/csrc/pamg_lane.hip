@@ -572,6 +572,11 @@ __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const i
     else bv = a.b[row];
     T xo = T(0);                                                // used by rows without a diagonal only
     if constexpr (!(ACC && PH == 1)) xo = coh ? __hip_atomic_load(a.xold + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.xold[row];
+    // the rows' first lanes (static plan data): exchanged here, in front of the waits, so that no lane exchange but the sums' stands between the
+    // last operand and the publishing store.  The empty asm keeps the compiler from sinking the exchange behind the poll loop; the mask lives
+    // through the loop in scalar registers (the kernels are at their 128 vector registers)
+    unsigned long long heads = seg_scan_heads(si[0] & ((7u << LANEC_ROWSHIFT) | LANEC_UNUSED), lane);
+    asm volatile("" : "+s"(heads));
     unsigned pend = 0;
 #pragma unroll
     for (int k = 0; k < LANEC_K; ++k)
@@ -607,6 +612,8 @@ __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const i
             }
         }
     }
+    asm volatile("" : "+s"(heads));                              // (the lanes' part of the bookkeeping: in the shadow of the LDS round trip)
+    const int seglo = seg_scan_first(heads, lane);
     // values -> LDS (an idle operand is a zero: padding, and every OLD operand where x is known to be zero), slots <- LDS
 #pragma unroll
     for (int k = 0; k < LANEC_K; ++k)
@@ -620,16 +627,8 @@ __device__ __forceinline__ void c_group(const LaneMArgs &a, double *lds, const i
         const T pr = sv[k] * lds[si[k] & LANEC_IDX];
         s = s + ((si[k] & LANEC_PAD) ? T(0) : pr);
     }
-    // segmented inclusive scan over the lanes of a row
-    const unsigned key = si[0] & ((7u << LANEC_ROWSHIFT) | LANEC_UNUSED);
-    const unsigned left = (unsigned)__shfl_up((int)key, 1);
-    const unsigned long long heads = __builtin_amdgcn_ballot_w64(lane == 0 || left != key);
-    const int seglo = 63 - __builtin_clzll(heads & (~0ull >> (63 - lane)));
-#pragma unroll
-    for (int d = 1; d < 64; d *= 2) {
-        const T o = __shfl_up(s, d);
-        s = s + ((lane - d >= seglo) ? o : T(0));
-    }
+    // segmented inclusive scan over the lanes of a row, in registers (pamg_wave.h)
+    s = seg_scan_incl(s, seglo, lane);
     const bool tail = ((((heads >> 1) | (1ull << 63)) >> lane) & 1ull) != 0;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // the next group's values overwrite what was read here
     __builtin_amdgcn_wave_barrier();

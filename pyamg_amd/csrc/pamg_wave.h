@@ -92,6 +92,71 @@ __device__ __forceinline__ T seg_allreduce(T v)
     return v;
 }
 
+// ---- segmented inclusive scan over the 64 lanes of a wave, in registers (the cluster layout of the merged lane sweep: a lane serves one row, a
+//      row owns consecutive lanes, the row's LAST lane ends up with the row's sum).  The additions and their association are those of the loop
+//          for (d = 1; d < 64; d *= 2) s[i] = s[i] + (i - d >= seglo[i] ? s[i - d] : 0)          (all lanes at once)
+//      -- only the way lane i gets lane i - d's value is chosen here: no ds_bpermute / ds_swizzle, no LDS, no wait per step.
+// the value of lane - 16 (rows 1 .. 3 of 16 lanes; row 0 gets nothing it may use): v_permlane16_swap leaves the even rows' values in the odd rows
+// of one copy (rows 1 and 3 are served) and the odd rows' values in the even rows of the other, whose lower half v_permlane32_swap hands to row 2
+__device__ __forceinline__ double lane_shr16(double v, int lane)
+{
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);         // a[0]: rows (0, 0, 2, 2) of v, a[1]: rows (1, 1, 3, 3)
+    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    const auto c = __builtin_amdgcn_permlane32_swap(a[1], a[1], false, false);     // c[0]: rows (1, 1, 1, 1)
+    const auto d = __builtin_amdgcn_permlane32_swap(b[1], b[1], false, false);
+    const bool row2 = (lane & 48) == 32;
+    return __hiloint2double((int)(row2 ? d[0] : b[0]), (int)(row2 ? c[0] : a[0]));
+}
+// the value of lane - 32 (lanes 32 .. 63): the copy of v_permlane32_swap that holds the lower half everywhere
+__device__ __forceinline__ double lane_shr32(double v)
+{
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return __hiloint2double((int)b[0], (int)a[0]);
+}
+// the value of lane - D, D = 2, 4, 8 (lanes >= D): DPP row_ror:D rotates inside the rows of 16 lanes -- the lanes whose value stays in the row send
+// their own, the last D lanes of a row send what lane - 16 holds, which is what the first D lanes of the NEXT row are to receive
+template <int D>
+__device__ __forceinline__ double lane_shr(double v, int lane)
+{
+    static_assert(D == 2 || D == 4 || D == 8, "1: wave_shr, 16 / 32: the permlane swaps");
+    const double below = lane_shr16(v, lane);
+    return dpp_mov<0x120 + D>((lane & 15) < 16 - D ? v : below);
+}
+
+// the row boundaries from the lanes' keys (equal keys on consecutive lanes = one row; static plan data, so a sweep forms them BEFORE it waits for
+// its operands): seg_scan_heads = the mask of the rows' first lanes (wave-uniform: a pair of scalar registers is all that has to live through the
+// waits), seg_scan_first = the first lane of the calling lane's row
+__device__ __forceinline__ unsigned long long seg_scan_heads(unsigned key, int lane)
+{
+    const unsigned left = (unsigned)__builtin_amdgcn_update_dpp(0, (int)key, 0x138, 0xF, 0xF, true);      // wave_shr:1 (lane 0 is a head anyway)
+    return __builtin_amdgcn_ballot_w64(lane == 0 || left != key);
+}
+__device__ __forceinline__ int seg_scan_first(unsigned long long heads, int lane) { return 63 - __builtin_clzll(heads & (~0ull >> (63 - lane))); }
+__device__ __forceinline__ double seg_scan_incl(double s, int seglo, int lane)
+{
+    // (every exchange is a statement of its own, in front of the select: all 64 lanes take part in it, also those that add a zero)
+    const double o1 = dpp_mov<0x138>(s);                                           // wave_shr:1
+    s = s + ((lane - 1 >= seglo) ? o1 : 0.0);
+    const double o2 = lane_shr<2>(s, lane);
+    s = s + ((lane - 2 >= seglo) ? o2 : 0.0);
+    const double o4 = lane_shr<4>(s, lane);
+    s = s + ((lane - 4 >= seglo) ? o4 : 0.0);
+    const double o8 = lane_shr<8>(s, lane);
+    s = s + ((lane - 8 >= seglo) ? o8 : 0.0);
+    const double o16 = lane_shr16(s, lane);
+    s = s + ((lane - 16 >= seglo) ? o16 : 0.0);
+    const double o32 = lane_shr32(s);
+    s = s + ((lane - 32 >= seglo) ? o32 : 0.0);
+    return s;
+}
+__device__ __forceinline__ double seg_scan_incl(double s, unsigned key, int lane)
+{
+    return seg_scan_incl(s, seg_scan_first(seg_scan_heads(key, lane), lane), lane);
+}
+
 // ---- the one-XCD forms: the first workgroup to arrive claims its XCD as the home (*slot = XCD + 1, zero before the launch), workgroups
 // elsewhere leave.  home_xcd_vote: the calling thread's answer for its workgroup
 __device__ __forceinline__ bool home_xcd_vote(unsigned *slot)
