@@ -580,6 +580,33 @@ int pamg_energy_gmres_f64(int32_t n_brow, int32_t n_bcol, int32_t r, int32_t c, 
                           const double *PIx, int32_t maxiter, double tol, int32_t *iterations, double *normrs, int32_t *n_normrs,
                           double *H);
 
+/* The setup of rootnode_solver around the energy-minimisation loop (csrc/pamg_rootnode.hip, the arithmetic in csrc/pamg_rootnode.h).
+ * float64, HOST arrays; at most 6 candidates, 6 columns per block of the pattern, 6 x 6 blocks of T (beyond: PAMG_E_UNSUPPORTED).
+ * Patterns are checked as above before anything is written.
+ *
+ * amg_core::calc_BtB, smoothed_aggregation.h:829-907, with its argument order: b = Bsq [rows of B, BsqCols], BsqCols = NullDim
+ * (NullDim + 1) / 2, x <- BtB [Nnodes, NullDim, NullDim], a block in column-major order.  An entry is summed over the pattern row's
+ * stored blocks in stored order and the columns of a block ascending: the reference's result bit for bit. */
+int pamg_calc_BtB_f64(int32_t NullDim, int32_t Nnodes, int32_t cols_per_block, const double *b, int b_size, int32_t BsqCols, double *x,
+                      int x_size, const int32_t *Sp, int Sp_size, const int32_t *Sj, int Sj_size);
+/* util/utils.py compute_BtBinv whole: calc_BtB with the products formed from B [rows, NullDim] where they are used, the deep transpose
+ * and pinv_array, BtB staying on the device.  NullDim == 1: reciprocal, zero stays zero, bit for bit.  NullDim > 1: a one-sided Jacobi
+ * SVD with gelss' rank rule at cond = 1e6 eps; equal to LAPACK's blocks to rounding. */
+int pamg_compute_BtBinv_f64(int32_t NullDim, int32_t Nnodes, int32_t cols_per_block, const double *B, int64_t B_size, const int32_t *Sp,
+                            int Sp_size, const int32_t *Sj, int Sj_size, double *BtBinv, int64_t BtBinv_size);
+/* The projection of util/utils.py filter_operator on the arrays of A expanded onto C's pattern: diff = S @ B - Bf with the product in
+ * the order of SciPy's bsr_matvecs, then satisfy_constraints_helper with diff in the place of U @ B, in one kernel.  B [n_bcol *
+ * cols_per_block, NullDim], Bf [num_block_rows * rows_per_block, NullDim].  Bit for bit. */
+int pamg_filter_constraints_f64(int32_t rows_per_block, int32_t cols_per_block, int32_t num_block_rows, int32_t NullDim, const double *B,
+                                int B_size, const double *Bf, int Bf_size, const double *BtBinv, int BtBinv_size, const int32_t *Sp,
+                                int Sp_size, const int32_t *Sj, int Sj_size, double *Sx, int Sx_size);
+/* util/utils.py scale_T on T's arrays (n_brow x n_bcol blocks of blocksize x blocksize): Tx <- I_F (T pinv(P_I^T T)) + P_I on T's
+ * structure.  Cnodes [n_bcol]: the block row of every aggregate's root node; that row must hold the aggregate's block and nothing
+ * else (otherwise PAMG_E_UNSUPPORTED).  The block products run in the order of SciPy's bsr_matmat; a root row receives the identity
+ * block.  Bit for bit for blocksize 1, to rounding through the pseudo-inverse otherwise. */
+int pamg_scale_T_f64(int32_t n_brow, int32_t n_bcol, int32_t blocksize, const int32_t *Tp, int Tp_size, const int32_t *Tj, int Tj_size,
+                     double *Tx, int64_t Tx_size, const int32_t *Cnodes, int Cnodes_size);
+
 /* ------------------------------------------------------ Layer 2: resident engine (HBM) */
 /* Operator handle: uploads CSR/BSR arrays (HOST pointers) to HBM once and analyses them
  * (row-block plan for the LDS-streamed kernels; dependency-level schedules for the

@@ -17,8 +17,8 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libpyamg_amd.so"
-SOURCES = ["pamg_matrix.hip", "pamg_solver.hip", "pamg_capi.hip", "pamg_setup.hip", "pamg_schwarz.hip", "pamg_dist.hip", "pamg_aggregate.hip", "pamg_lane.hip", "pamg_line.hip", "pamg_kz.hip", "pamg_blane.hip", "pamg_block.hip", "pamg_renumber.hip", "pamg_krylov.hip", "pamg_schwarz_setup.hip", "pamg_classical.hip", "pamg_air.hip", "pamg_air_block.hip", "pamg_evolution.hip", "pamg_energy.hip", "pamg_dtri.hip", "pamg_distance.hip", "pamg_cljp.hip", "pamg_lloyd.hip"]
-HEADERS = ["pamg_common.h", "pamg_kernels.h", "pamg_tile_kernels.h", "pamg_tile_plan.h", "pamg_lane_plan.h", "pamg_lanem_plan.h", "pamg_schwarz_plan.h", "pamg_line_plan.h", "pamg_kz_plan.h", "pamg_blane_plan.h", "pamg_spg_plan.h", "pamg_stream_plan.h", "pamg_rowmask_map.h", "pamg_plan_vec.h", "pamg_host_threads.h", "pamg_dense_pinv.h", "pamg_classical.h", "pamg_air.h", "pamg_air_block.h", "pamg_jacobi_svd.h", "pamg_evolution.h", "pamg_energy.h", "pamg_host_call.h", "pamg_wave.h", "pamg_sweep_host.h", "pamg_dtri_plan.h", "pamg_distance.h", "pamg_cljp.h", "pamg_lloyd.h", "amg_core_bind.cpp", "../../include/pyamg_amd.h"]
+SOURCES = ["pamg_matrix.hip", "pamg_solver.hip", "pamg_capi.hip", "pamg_setup.hip", "pamg_schwarz.hip", "pamg_dist.hip", "pamg_aggregate.hip", "pamg_lane.hip", "pamg_line.hip", "pamg_kz.hip", "pamg_blane.hip", "pamg_block.hip", "pamg_renumber.hip", "pamg_krylov.hip", "pamg_schwarz_setup.hip", "pamg_classical.hip", "pamg_air.hip", "pamg_air_block.hip", "pamg_evolution.hip", "pamg_energy.hip", "pamg_dtri.hip", "pamg_distance.hip", "pamg_cljp.hip", "pamg_lloyd.hip", "pamg_rootnode.hip"]
+HEADERS = ["pamg_common.h", "pamg_kernels.h", "pamg_tile_kernels.h", "pamg_tile_plan.h", "pamg_lane_plan.h", "pamg_lanem_plan.h", "pamg_schwarz_plan.h", "pamg_line_plan.h", "pamg_kz_plan.h", "pamg_blane_plan.h", "pamg_spg_plan.h", "pamg_stream_plan.h", "pamg_rowmask_map.h", "pamg_plan_vec.h", "pamg_host_threads.h", "pamg_dense_pinv.h", "pamg_classical.h", "pamg_air.h", "pamg_air_block.h", "pamg_jacobi_svd.h", "pamg_evolution.h", "pamg_energy.h", "pamg_host_call.h", "pamg_wave.h", "pamg_sweep_host.h", "pamg_dtri_plan.h", "pamg_distance.h", "pamg_cljp.h", "pamg_lloyd.h", "pamg_rootnode.h", "amg_core_bind.cpp", "../../include/pyamg_amd.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 

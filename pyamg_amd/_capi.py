@@ -155,6 +155,10 @@ def _declare(lib):
       _vp, _i, _vp, _vp, _i, _d, P(_i), _vp, P(_i))
     f("pamg_energy_gmres_f64", _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, C.c_int64, _vp, _i, _vp, _i, _vp, C.c_int64, _vp, _i, _vp, C.c_int64,
       _vp, _i, _vp, _vp, _i, _d, P(_i), _vp, P(_i), _vp)
+    f("pamg_calc_BtB_f64", _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i)
+    f("pamg_compute_BtBinv_f64", _i, _i, _i, _vp, C.c_int64, _vp, _i, _vp, _i, _vp, C.c_int64)
+    f("pamg_filter_constraints_f64", _i, _i, _i, _i, *(_vp, _i) * 6)
+    f("pamg_scale_T_f64", _i, _i, _i, _vp, _i, _vp, _i, _vp, C.c_int64, _vp, _i)
     f("pamg_fit_tentative_f64", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d)
     f("pamg_fit_tentative_f32", _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float)
     f("pamg_matrix_create", P(_vp), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp)

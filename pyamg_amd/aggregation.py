@@ -762,7 +762,7 @@ _CLASSICAL_NAMES = ("classical_strength_of_connection", "direct_interpolation", 
 
 @contextlib.contextmanager
 def device_setup(pyamg, prolongation=True, products=True, aggregation=False, schwarz=False, classical=False, air=False, evolution=False,
-                 energy=False, energy_gmres=False, distance=False, cljp=False, block_air=False, lloyd=False):
+                 energy=False, energy_gmres=False, distance=False, cljp=False, block_air=False, lloyd=False, rootnode=False):
     """Run the setup pieces above inside a reference package the CALLER imported::
 
         with pyamg_amd.aggregation.device_setup(pyamg):
@@ -844,7 +844,19 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
     sums (``pyamg_amd.graph``, csrc/pamg_lloyd.h): integer-valued weights in [1, 2^31] -- ``measure='unit'``, the default, always --, CSR,
     int32 indices, unique centres.  Real-valued measures, explicit zeros, float32 or complex data, CSC input and ``method='balanced'`` go
     to the function that was patched out, before anything is drawn.  Off by default for the reason given for ``classical``; with
-    ``lloyd=False`` nothing is patched or imported on its account."""
+    ``lloyd=False`` nothing is patched or imported on its account.
+    ``rootnode=True`` routes what one pass of ``rootnode_solver``'s ``_extend_hierarchy`` still ran on the host to ``pyamg_amd.rootnode``:
+    ``compute_BtBinv`` (in ``<pyamg>.aggregation.smooth`` and in ``.util.utils``, where ``filter_operator`` resolves it), ``filter_operator`` (in
+    ``.aggregation.smooth``), ``scale_T`` (in ``.aggregation.rootnode``) and ``relaxation_as_linear_operator`` (in ``.aggregation.rootnode`` and
+    ``.aggregation.aggregation``), the candidate improvement.  It also binds ``fit_candidates``, ``symmetric_strength_of_connection`` and, with
+    ``aggregation=True``, ``standard_aggregation`` into ``.aggregation.rootnode``, which resolves these names by itself and so never saw the
+    device versions.  ``BtB``, the filtered operator given the same ``BtBinv``, 1 x 1 ``scale_T`` and the relaxed candidates are the
+    reference's bit for bit -- the smoother is set up by the caller's package, with its ``Dinv``, ``omega`` and random draws; the
+    pseudo-inverses of blocks larger than 1 x 1 agree with LAPACK's to rounding (a one-sided Jacobi SVD with the same rank rule).  Non-float64
+    or complex data, more than 6 candidates, blocks beyond 6, other relaxation methods and whatever else the device path does not take go to
+    the function that was patched out; ``get_Cpt_params``, the row filters and the CGNR variant stay in the reference.  A keyword of its own
+    so that every name patched today stays patched exactly as it is; off by default for the reason given for ``classical``.  With
+    ``rootnode=False`` nothing is patched or imported on its account."""
     import importlib
     from . import air as _air
     from . import classical as _cls
@@ -892,6 +904,20 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                        ("aggregation.aggregate", "lloyd_cluster", _gr.lloyd_cluster),
                        ("graph", "lloyd_cluster", _gr.lloyd_cluster),
                        ("graph", "bellman_ford", _gr.bellman_ford))
+    rootnode_table, rootnode_direct = (), ()
+    if rootnode:
+        import functools
+        from . import rootnode as _rn
+        relax = functools.partial(_rn.relaxation_as_linear_operator, pyamg=pyamg)
+        rootnode_table = (("aggregation.smooth", "compute_BtBinv", _rn.compute_BtBinv),
+                          ("util.utils", "compute_BtBinv", _rn.compute_BtBinv),
+                          ("aggregation.smooth", "filter_operator", _rn.filter_operator),
+                          ("aggregation.rootnode", "scale_T", _rn.scale_T),
+                          ("aggregation.rootnode", "relaxation_as_linear_operator", relax),
+                          ("aggregation.aggregation", "relaxation_as_linear_operator", relax),
+                          ("aggregation.rootnode", "fit_candidates", fit_candidates),
+                          ("aggregation.rootnode", "standard_aggregation", standard_aggregation))
+        rootnode_direct = (("aggregation.rootnode", "symmetric_strength_of_connection", symmetric_strength_of_connection),)
     targets = []
     for mod, name, fn in (("aggregation.aggregation", "jacobi_prolongation_smoother", jacobi_prolongation_smoother),
                           ("aggregation.aggregation", "richardson_prolongation_smoother", richardson_prolongation_smoother),
@@ -912,7 +938,8 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                           ("classical.classical", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.interpolate", "classical_interpolation", _cls.classical_interpolation),
                           ("classical.split", "PMIS", _cls.PMIS),
-                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table + distance_table + cljp_table + block_table + lloyd_table:
+                          ("classical.split", "MIS", _cls.MIS)) + air_table + evo_table + energy_table + distance_table + cljp_table + block_table + lloyd_table + \
+            rootnode_table + rootnode_direct:
         of_air = (mod, name, fn) in air_table or (mod, name, fn) in block_table
         if not classical and name in _CLASSICAL_NAMES and not of_air:
             continue                            # (before the import: with classical=False nothing of <pyamg>.classical is touched)
@@ -935,7 +962,7 @@ def device_setup(pyamg, prolongation=True, products=True, aggregation=False, sch
                 setattr(m, name, _schwarz_parameters_or_reference(old))
             elif name in ("standard_aggregation", "fit_candidates", "evolution_strength_of_connection") or name in _CLASSICAL_NAMES or of_air or \
                     (mod, name, fn) in energy_table or (mod, name, fn) in distance_table or (mod, name, fn) in cljp_table or \
-                    (mod, name, fn) in lloyd_table:
+                    (mod, name, fn) in lloyd_table or (mod, name, fn) in rootnode_table:
                 setattr(m, name, _device_or_reference(fn, old))
             else:
                 setattr(m, name, fn)

@@ -22,7 +22,8 @@ __all__ = ["csr_matvec", "bsr_matvec", "gauss_seidel", "sor_gauss_seidel", "bsr_
            "one_point_interpolation", "approx_ideal_restriction_pass1", "approx_ideal_restriction_pass2",
            "block_strength_measure", "block_approx_ideal_restriction_pass2",
            "incomplete_mat_mult_csr", "evolution_strength_helper", "apply_distance_filter", "apply_absolute_distance_filter", "min_blocks",
-           "evolution_strength_vector", "relaxation_vectors", "distance_measure", "distance_strength", "vertex_distance", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "satisfy_constraints", "energy_cg", "energy_gmres"]
+           "evolution_strength_vector", "relaxation_vectors", "distance_measure", "distance_strength", "vertex_distance", "incomplete_mat_mult_bsr", "satisfy_constraints_helper", "satisfy_constraints", "energy_cg", "energy_gmres",
+           "calc_BtB", "compute_BtBinv", "filter_constraints", "scale_T"]
 
 
 def _sfx(Ax, *vals):
@@ -582,3 +583,38 @@ def energy_gmres(n_brow, n_bcol, r, c, NullDim, Ap, Aj, Ax, Sp, Sj, Tx, B, BtBin
                                                p(cmask), p(PIx), int(maxiter), float(tol), ctypes.byref(its), p(normrs), ctypes.byref(ns), p(H)),
                "energy_gmres")
     return int(its.value), normrs[:int(ns.value)].copy()
+
+
+# ------------------------------------------------------------------ the setup of rootnode_solver: csrc/pamg_rootnode.hip
+def calc_BtB(NullDim, Nnodes, cols_per_block, b, BsqCols, x, Sp, Sj):
+    """amg_core.calc_BtB (smoothed_aggregation.h:829-907): x <- BtB [Nnodes, NullDim, NullDim], a block column-major, from b = Bsq ravelled;
+    at most 6 candidates and 6 columns per block."""
+    _idx(Sp, Sj)
+    _f64(b, x)
+    capi.check(capi.lib().pamg_calc_BtB_f64(int(NullDim), int(Nnodes), int(cols_per_block), capi.ptr(b), b.size, int(BsqCols), *_pairs(x, Sp, Sj)),
+               "calc_BtB")
+
+
+def compute_BtBinv(NullDim, Nnodes, cols_per_block, B, Sp, Sj, BtBinv):
+    """util.utils.compute_BtBinv on the raw arrays: BtBinv [Nnodes, NullDim, NullDim] <- pinv of every node's B_i^H B_i, BtB staying on the
+    device.  (The reference composes this in Python; it has no amg_core twin.)"""
+    _idx(Sp, Sj)
+    _f64(B, BtBinv)
+    capi.check(capi.lib().pamg_compute_BtBinv_f64(int(NullDim), int(Nnodes), int(cols_per_block), *_pairs(B, Sp, Sj, BtBinv)), "compute_BtBinv")
+
+
+def filter_constraints(rows_per_block, cols_per_block, num_block_rows, NullDim, B, Bf, BtBinv, Sp, Sj, Sx):
+    """The projection of util.utils.filter_operator on the raw arrays: diff = S @ B - Bf in the order of SciPy's bsr_matvecs, then
+    satisfy_constraints_helper with diff, as one kernel, in place on Sx.  (No amg_core twin in the reference.)"""
+    _idx(Sp, Sj)
+    _f64(B, Bf, BtBinv, Sx)
+    capi.check(capi.lib().pamg_filter_constraints_f64(int(rows_per_block), int(cols_per_block), int(num_block_rows), int(NullDim),
+                                                     *_pairs(B, Bf, BtBinv, Sp, Sj, Sx)), "filter_constraints")
+
+
+def scale_T(n_brow, n_bcol, blocksize, Tp, Tj, Tx, Cnodes):
+    """util.utils.scale_T on T's arrays, in place on Tx: T pinv(P_I^T T) with the identity block in every root row; Cnodes: the block row
+    of every aggregate's root node.  (No amg_core twin in the reference.)"""
+    _idx(Tp, Tj, Cnodes)
+    _f64(Tx)
+    capi.check(capi.lib().pamg_scale_T_f64(int(n_brow), int(n_bcol), int(blocksize), *_pairs(Tp, Tj, Tx, Cnodes)), "scale_T")

@@ -367,5 +367,24 @@ PYBIND11_MODULE(_amg_core_pybind, m)
     }, py::arg("n_brow"), py::arg("n_bcol"), py::arg("r"), py::arg("c"), py::arg("NullDim"), nc("Ap"), nc("Aj"), nc("Ax"), nc("Sp"), nc("Sj"), nc("Tx"),
        nc("B"), nc("BtBinv"), nc("Dinv"), py::arg("cmask").noconvert().none(true), py::arg("PIx").noconvert().none(true), py::arg("maxiter"),
        py::arg("tol"), py::arg("H").noconvert().none(true) = py::none());
+    // the setup of rootnode_solver, float64 (smoothed_aggregation_bind.cpp for calc_BtB; the other two have no amg_core twin): csrc/pamg_rootnode.hip
+    m.def("calc_BtB", [](int NullDim, int Nnodes, int cols_per_block, D &b, int BsqCols, D &x, Idx &Sp, Idx &Sj) {
+        done(pamg_calc_BtB_f64(NullDim, Nnodes, cols_per_block, b.data(), len(b), BsqCols, x.mutable_data(), len(x), Sp.data(), len(Sp), Sj.data(),
+                               len(Sj)), "calc_BtB");
+    }, py::arg("NullDim"), py::arg("Nnodes"), py::arg("cols_per_block"), nc("b"), py::arg("BsqCols"), nc("x"), nc("Sp"), nc("Sj"));
+    m.def("compute_BtBinv", [](int NullDim, int Nnodes, int cols_per_block, D &B, Idx &Sp, Idx &Sj, D &BtBinv) {
+        done(pamg_compute_BtBinv_f64(NullDim, Nnodes, cols_per_block, B.data(), (int64_t)B.size(), Sp.data(), len(Sp), Sj.data(), len(Sj),
+                                     BtBinv.mutable_data(), (int64_t)BtBinv.size()), "compute_BtBinv");
+    }, py::arg("NullDim"), py::arg("Nnodes"), py::arg("cols_per_block"), nc("B"), nc("Sp"), nc("Sj"), nc("BtBinv"));
+    m.def("filter_constraints", [](int rows_per_block, int cols_per_block, int num_block_rows, int NullDim, D &B, D &Bf, D &BtBinv, Idx &Sp, Idx &Sj,
+                                   D &Sx) {
+        done(pamg_filter_constraints_f64(rows_per_block, cols_per_block, num_block_rows, NullDim, B.data(), len(B), Bf.data(), len(Bf), BtBinv.data(),
+                                         len(BtBinv), Sp.data(), len(Sp), Sj.data(), len(Sj), Sx.mutable_data(), len(Sx)), "filter_constraints");
+    }, py::arg("rows_per_block"), py::arg("cols_per_block"), py::arg("num_block_rows"), py::arg("NullDim"), nc("B"), nc("Bf"), nc("BtBinv"), nc("Sp"),
+       nc("Sj"), nc("Sx"));
+    m.def("scale_T", [](int n_brow, int n_bcol, int blocksize, Idx &Tp, Idx &Tj, D &Tx, Idx &Cnodes) {
+        done(pamg_scale_T_f64(n_brow, n_bcol, blocksize, Tp.data(), len(Tp), Tj.data(), len(Tj), Tx.mutable_data(), (int64_t)Tx.size(), Cnodes.data(),
+                              len(Cnodes)), "scale_T");
+    }, py::arg("n_brow"), py::arg("n_bcol"), py::arg("blocksize"), nc("Tp"), nc("Tj"), nc("Tx"), nc("Cnodes"));
     m.def("version", [] { return std::string(pamg_version()); });
 }

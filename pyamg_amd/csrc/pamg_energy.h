@@ -21,7 +21,7 @@
 #include <cstdint>
 
 #if defined(__HIPCC__)
-#define PAMG_EN_HD __host__ __device__
+#define PAMG_EN_HD __host__ __device__ inline          // (inline: pamg_rootnode.hip includes this header too)
 #else
 #define PAMG_EN_HD inline
 #endif

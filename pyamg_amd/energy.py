@@ -13,7 +13,8 @@ and per iteration one int comes back (the loop's exit).  Everything local to a b
 projection, the updates -- is computed in the reference's order; the two Frobenius inner products are summed by a fixed tree over the
 block rows where the reference sums in SciPy's and NumPy's order, so ``newsum`` and T agree with the reference to rounding, not bit for
 bit.  The row weights ``Dinv`` are formed on the host with the reference's own expressions.  What stays with the caller
-(``energy_prolongation_smoother``): ``compute_BtBinv``, ``filter_operator``, ``get_Cpt_params``, the pattern and the filters.
+(``energy_prolongation_smoother``): ``compute_BtBinv`` and ``filter_operator`` (device paths of their own: ``pyamg_amd.rootnode``),
+``get_Cpt_params``, the pattern and the filters.
 
 The loop's head is the reference's: it runs while ``i < maxiter`` and the stored size of R exceeds ``tol`` (R's all-zero blocks not
 counted, as SciPy's subtraction drops them), and leaves at the first ``newsum < tol``.
