@@ -207,25 +207,29 @@ def pinv_array(AA, m, n, TransA="T"):
 
 def standard_aggregation(Ap, Aj):
     """(x, y, count): amg_core.standard_aggregation (smoothed_aggregation.h:137-268)"""
-    n = Ap.size - 1
+    # _ptr keeps an address only: the converted arrays must outlive the call, so they are held in locals
+    Ap32 = np.ascontiguousarray(Ap, dtype=np.int32)
+    Aj32 = np.ascontiguousarray(Aj, dtype=np.int32)
+    n = Ap32.size - 1
     x = np.empty(n, dtype=np.int32)
     y = np.empty(max(n, 1), dtype=np.int32)
     fn = lib().orc_standard_aggregation
     fn.restype = C.c_int
-    cnt = fn(_I(n), _ptr(np.ascontiguousarray(Ap, dtype=np.int32)), _ptr(np.ascontiguousarray(Aj, dtype=np.int32)), _ptr(x), _ptr(y))
+    cnt = fn(_I(n), _ptr(Ap32), _ptr(Aj32), _ptr(x), _ptr(y))
     return x, y[:cnt], int(cnt)
 
 
 def fit_candidates(n_col, K1, K2, Ap, Ai, B, tol):
     """(Ax, R): amg_core.fit_candidates (smoothed_aggregation.h:484-610) on the CSC arrays of AggOp"""
     B = np.ascontiguousarray(B)
-    Ax = np.empty((Ai.size, K1, K2), dtype=B.dtype)
+    Ap32 = np.ascontiguousarray(Ap, dtype=np.int32)          # held in locals: _ptr keeps an address only
+    Ai32 = np.ascontiguousarray(Ai, dtype=np.int32)
+    Ax = np.empty((Ai32.size, K1, K2), dtype=B.dtype)
     R = np.empty((n_col, K2, K2), dtype=B.dtype)
     sfx, ct = _sfx(B.dtype)
     fn = getattr(lib(), f"orc_fit_candidates_{sfx}")
     fn.restype = None
-    fn(_I(n_col), _I(K1), _I(K2), _ptr(np.ascontiguousarray(Ap, dtype=np.int32)), _ptr(np.ascontiguousarray(Ai, dtype=np.int32)),
-       _ptr(Ax), _ptr(B), _ptr(R), ct(tol))
+    fn(_I(n_col), _I(K1), _I(K2), _ptr(Ap32), _ptr(Ai32), _ptr(Ax), _ptr(B), _ptr(R), ct(tol))
     return Ax, R
 
 

@@ -466,7 +466,8 @@ def standard_aggregation(C):
     on the device (``pamg_standard_aggregation``: the reference's three passes, the sequential first one ordered by per-node
     turn counters -- the same aggregates with the same numbers, the same C-points).  Returns (AggOp, Cpts) like the
     reference.  A strength matrix that ``symmetric_strength_of_connection`` of this module just produced is still resident
-    and is not shipped again."""
+    and is not shipped again.  Patterns that are not symmetric or hold duplicate entries, and rows of more than 4096 stored
+    entries (the rows are sorted by one lane each), raise NotImplementedError."""
     if not sp.issparse(C) or C.format != "csr":
         raise TypeError("expected csr_array")
     if C.shape[0] != C.shape[1]:
@@ -509,7 +510,8 @@ def fit_candidates(AggOp, B, tol=1e-10):
     candidates R with ``Q @ R = B`` on the aggregates, ``Q.T @ Q = I`` -- per aggregate the reference's modified
     Gram-Schmidt (amg_core.fit_candidates, smoothed_aggregation.h:484-610) on the device, one lane per aggregate, the sums
     in the reference's order.  The blocks come back in AggOp's row order, which is what ``Q.T.tobsr()`` of the reference
-    stores, so no transposes are formed on the host."""
+    stores, so no transposes are formed on the host.  An aggregate of more than 4096 nodes raises NotImplementedError (its
+    node list is sorted by one lane)."""
     if not sp.issparse(AggOp) or AggOp.format != "csr":
         raise TypeError("expected csr_array for argument AggOp")
     B = np.asarray(B)

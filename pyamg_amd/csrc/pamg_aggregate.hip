@@ -110,6 +110,17 @@ int pamg_dev_pinv_array(int dtype, void *AA, int64_t m, int n, int transA, pamg_
 namespace {
 
 constexpr int AGG_ISO = INT32_MIN;          // isolated vertex (the reference's x = -n_row)
+// The per-row sort of agg_lists_kernel and the per-aggregate sort of fit_candidates_kernel are insertion sorts by one lane:
+// quadratic in the worst case.  A row / an aggregate of more entries than this is refused (PAMG_E_UNSUPPORTED) before any
+// sorting kernel is launched -- the bound transpose_host below puts on a column for the same reason.
+constexpr int SORT_MAX = 4096;
+
+__global__ __launch_bounds__(BLK) void agg_maxrow_kernel(int n, const int *Ap, int *out)
+{
+    int v = 0;
+    for (int i = blockIdx.x * BLK + threadIdx.x; i < n; i += gridDim.x * BLK) v = max(v, Ap[i + 1] - Ap[i]);
+    if (v) atomicMax(out, v);
+}
 
 // Member lists: Ns[Ap[v] + v ...] = {v} + row(v) sorted ascending, nsize[v] members.  flags: bit 0 pattern not symmetric,
 // bit 1 duplicate entries.  Isolated vertices (no neighbour but themselves) are marked at once and take no part.
@@ -258,11 +269,22 @@ __global__ __launch_bounds__(BLK) void agg_final_kernel(int n, const int *mark, 
 
 int agg_grid(int64_t n, int cap = 4096) { return launch_grid(n, BLK, cap); }
 
-// device arrays Ap[n+1], Aj[nnz] -> device x[n], y[n]; *count
-int standard_aggregation_device(int n, const int *d_Ap, const int *d_Aj, int64_t nnz, int *d_x, int *d_y, int *count)
+// device arrays Ap[n+1], Aj[nnz] -> device x[n], y[n]; *count.  maxrow: the longest row's stored entries when the caller
+// knows it (Ap on the host), -1: found here
+int standard_aggregation_device(int n, const int *d_Ap, const int *d_Aj, int64_t nnz, int *d_x, int *d_y, int *count, int maxrow)
 {
     *count = 0;
     if (n == 0) return PAMG_OK;
+    if (maxrow < 0) {
+        Bufs m;
+        int *d_mx;
+        PAMG_TRY(m.get(&d_mx, 1));
+        PAMG_HIP(hipMemset(d_mx, 0, sizeof(int)));
+        hipLaunchKernelGGL(agg_maxrow_kernel, dim3(launch_grid(n, BLK, 4096)), dim3(BLK), 0, 0, n, d_Ap, d_mx);
+        PAMG_HIP(hipGetLastError());
+        PAMG_HIP(hipMemcpy(&maxrow, d_mx, sizeof(int), hipMemcpyDeviceToHost));
+    }
+    if (maxrow > SORT_MAX) return PAMG_E_UNSUPPORTED;             // the one-lane row sort below is quadratic
     Bufs d;
     int *Ns, *nsize, *cnt, *pend, *mark, *rid, *bsum, *wl;
     unsigned *ctl;                                               // [0] flags, [1] live vertices, [2] vertices done, [4..6] work-list sizes
@@ -444,7 +466,10 @@ int fit_tentative_host(int n_fine, int n_coarse, int K1, int K2, const int32_t *
     PAMG_HIP(hipGetLastError());
     std::vector<int> cp((size_t)n_coarse + 1, 0);
     PAMG_TRY(Bufs::fetch(cp.data() + 1, dCur, (size_t)n_coarse));
-    for (int a = 0; a < n_coarse; ++a) cp[(size_t)a + 1] += cp[(size_t)a];
+    for (int a = 0; a < n_coarse; ++a) {
+        if (cp[(size_t)a + 1] > SORT_MAX) return PAMG_E_UNSUPPORTED;                          // the one-lane sort of an aggregate's nodes is quadratic
+        cp[(size_t)a + 1] += cp[(size_t)a];
+    }
     PAMG_HIP(hipMemcpy(dCp, cp.data(), sizeof(int) * ((size_t)n_coarse + 1), hipMemcpyHostToDevice));
     PAMG_HIP(hipMemset(dCur, 0, sizeof(int) * (size_t)n_coarse));
     if (n_fine) hipLaunchKernelGGL(agglist_fill_kernel, dim3(agg_grid(n_fine)), dim3(BLK), 0, 0, n_fine, (const int *)dTp, (const int *)dTj, (const int *)dCp, dCur, dCi);
@@ -467,7 +492,8 @@ int pamg_standard_aggregation(int32_t n_row, const int32_t *Ap, int Ap_size, con
     if (n_row < 0 || !Ap || Ap_size != n_row + 1 || x_size < n_row || y_size < n_row || !naggs || (n_row && (!x || !y))) return PAMG_E_ARG;
     const int64_t nnz = Ap[n_row];
     if (nnz < 0 || nnz != Aj_size || (nnz && !Aj) || Ap[0] != 0) return PAMG_E_ARG;
-    for (int i = 0; i < n_row; ++i) if (Ap[i + 1] < Ap[i]) return PAMG_E_ARG;
+    int maxrow = 0;
+    for (int i = 0; i < n_row; ++i) { if (Ap[i + 1] < Ap[i]) return PAMG_E_ARG; maxrow = std::max(maxrow, Ap[i + 1] - Ap[i]); }
     for (int64_t p = 0; p < nnz; ++p) if (Aj[p] < 0 || Aj[p] >= n_row) return PAMG_E_ARG;
     *naggs = 0;
     if (n_row == 0) return PAMG_OK;
@@ -476,7 +502,7 @@ int pamg_standard_aggregation(int32_t n_row, const int32_t *Ap, int Ap_size, con
     PAMG_TRY(d.put(&dAp, Ap, (size_t)n_row + 1)); PAMG_TRY(d.put(&dAj, Aj, (size_t)nnz));
     PAMG_TRY(d.get(&dx, (size_t)n_row)); PAMG_TRY(d.get(&dy, (size_t)n_row));
     int count = 0;
-    PAMG_TRY(standard_aggregation_device(n_row, dAp, dAj, nnz, dx, dy, &count));
+    PAMG_TRY(standard_aggregation_device(n_row, dAp, dAj, nnz, dx, dy, &count, maxrow));
     PAMG_TRY(Bufs::fetch(x, dx, (size_t)n_row));
     PAMG_TRY(Bufs::fetch(y, dy, (size_t)count));
     *naggs = count;
@@ -498,7 +524,7 @@ int pamg_csr_standard_aggregation(pamg_csr_t C, int32_t *x, int32_t *y, int32_t 
     int *dx, *dy;
     PAMG_TRY(d.get(&dx, (size_t)n)); PAMG_TRY(d.get(&dy, (size_t)n));
     int count = 0;
-    PAMG_TRY(standard_aggregation_device(n, a.p, a.j, a.nnz, dx, dy, &count));
+    PAMG_TRY(standard_aggregation_device(n, a.p, a.j, a.nnz, dx, dy, &count, -1));
     PAMG_TRY(Bufs::fetch(x, dx, (size_t)n));
     PAMG_TRY(Bufs::fetch(y, dy, (size_t)count));
     *naggs = count;
@@ -598,7 +624,7 @@ int transpose_host(int n_brow, int n_bcol, int R, int C, const int32_t *Ap, cons
     int64_t acc = 0;
     for (int j = 0; j < n_bcol; ++j) { const int c = cnt[(size_t)j]; mx = std::max(mx, c); Bp[j] = (int)acc; acc += c; }
     Bp[n_bcol] = (int)acc;
-    if (mx > 4096) return PAMG_E_UNSUPPORTED;                      // a column of thousands of blocks: the per-column sort is quadratic
+    if (mx > SORT_MAX) return PAMG_E_UNSUPPORTED;                    // a column of thousands of blocks: the per-column sort is quadratic
     PAMG_HIP(hipMemcpy(dBp, Bp, sizeof(int) * ((size_t)n_bcol + 1), hipMemcpyHostToDevice));
     PAMG_HIP(hipMemset(dCur, 0, sizeof(int) * ((size_t)n_bcol + 1)));
     hipLaunchKernelGGL(tr_fill_kernel, dim3(grid), dim3(BLK), 0, 0, nblk, (const int *)dAj, (const int *)dBp, dCur, dSrc);
